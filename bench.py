@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- MPix/s encoded at --quality 95 on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run times the headline leg alone: the process's first encode (untimed), W warm-up steps, K
+timed steps, and one JSON line (metric, value, unit, ms_per_step, dtype, config, step_ms).  The
+output is not checked there.  `--full` adds every other leg and check listed under "Also on the JSON
+line" below: the output hashes against the reference's, the other sizes and batches, rooflines,
+config 5, the box calibration and the CPU baseline.  `--dump-outputs DIR` writes the JPEG bytes that
+rank 0's last timed headline step returned (DIR/jpeg_bytes.npy, float32; dump_outputs).
 
 Workload of `value` (BASELINE.json configs[2], north_star's target size and the rocprof config): one
 3840x2160 sRGB image (tests/golden/bees.png tiled from the origin), --quality 95
@@ -23,7 +30,7 @@ the unmodified reference, one thread of the survey container's Xeon @ 2.10 GHz: 
 `vs_reference_same_box` = value / the same reference on one thread of the bench box's kind of host CPU
 (profiles/r05_reference_cpu_4k.json).
 
-Also on the JSON line:
+Also on the JSON line (with --full):
   value_workload -- "3840x2160" (or "1920x1080" with --no-4k): which size `value` is.  `value_4k`
                   and `value_1080p` (+ ms_per_step_4k / _1080p) are ALWAYS emitted under those names,
                   whatever the headline, so that rounds compare like with like (until round 3
@@ -528,6 +535,80 @@ def roofline_of(L, rgb, device, iters, warm):
     return ms, achieved
 
 
+TIMER_KEYS = ("total", "phase_b_host", "compare", "block_search", "jpeg_write", "create+encode",
+              "select_quant_matrix", "pb_device_partitions", "pb_device_descents",
+              "pb_device_fetches", "pb_loop_codes")
+
+
+def leg_record(w, h, seconds, jpeg, inf, which, world, args, quality, checked):
+    """value / ms_per_step / config of one timed size (every size is timed identically).  checked: the
+    output's SHA-256 was compared with the reference's (--full)."""
+    return (round(world * args.steps * w * h / 1e6 / seconds, 4), round(seconds / args.steps * 1e3, 2),
+            {"workload": f"single {w}x{h} sRGB image, --quality {quality:g} (BASELINE {which}), whole "
+                         "guetzli::Process per step (host RGB in, JPEG bytes out), 1 image per GPU "
+                         f"per step; {args.steps} timed steps after {args.warmup} warm-up between "
+                         "barrier + synchronise, max over ranks",
+             "butteraugli_target": TARGET_Q95, "images_per_gpu": 1, "steps": args.steps,
+             "warmup": args.warmup, "output_bytes": len(jpeg),
+             "output_sha256_matches_reference": checked,
+             "iterations": inf["counters"].get("number of iterations"),
+             # host threads of one encode: the search driver's own + the size model's code-refresh
+             # helpers (guetzli_amd/host/code_refresh.h; `pb_loop_codes` is the driver WAITING for them)
+             "host_code_refresh_threads": inf["counters"].get("phase B code refresh threads"),
+             "host_timers_s": {k: round(v, 3) for k, v in inf["timers"].items() if k in TIMER_KEYS}})
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, rank, jpeg):
+    """--dump-outputs DIR: what the headline leg's last timed step returned on rank 0 -- the JPEG bytes, one
+    float32 per byte, as DIR/jpeg_bytes.npy.  Past 64 MB: a fixed, seeded sample of the bytes
+    (jpeg_bytes_sample.npy, positions ascending) and the length (jpeg_size.npy)."""
+    if not d or rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    a = np.frombuffer(jpeg, np.uint8).astype(np.float32)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "jpeg_bytes.npy"), a)
+        return
+    idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_BYTES // 8, replace=False))
+    np.save(os.path.join(d, "jpeg_bytes_sample.npy"), a[idx])
+    np.save(os.path.join(d, "jpeg_size.npy"), np.array([a.size], np.float64))
+
+
+def headline_only(env, args, host, images, size, quality):
+    """The plain run: the headline leg alone -- the process's first encode (start-up, pools) untimed as in
+    --full, then --warmup and --steps steps exactly as `value` is timed there -- and its result line."""
+    w, h = size
+    rgb = images.shifted(images.tiled(w, h), env.rank)
+
+    def step():
+        return host.process(rgb, quality=quality, device=env.device)
+
+    t0 = time.perf_counter()
+    step()
+    env.sync()
+    first_encode_s = time.perf_counter() - t0
+    dt, (jpg, info) = timed_steps(env, step, args.steps, args.warmup)
+    dump_outputs(args.dump_outputs, env.rank, jpg)
+    if env.rank != 0:
+        return
+    value, ms, cfg = leg_record(w, h, dt, jpg, info, "configs[1]" if args.no_4k else "configs[2]", env.world, args,
+                                quality, checked=False)
+    cfg["output_sha256"] = hashlib.sha256(jpg).hexdigest()
+    print(json.dumps({
+        "metric": "MPix/s encoded at --quality 95", "value": value, "value_workload": f"{w}x{h}",
+        "unit": "MPix/s", "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None if env.emulate else round(value / env.world / BASELINE_MD_MPIX_S[f"{w}x{h}"], 1),
+        "dtype": "f32+f64 (butteraugli), int32/int16 (DCT/quantize/entropy coding)",
+        "data": f"synthetic (tests/golden/bees.png tiled to {w}x{h}, SURVEY 8d)",
+        "config": cfg, "step_ms": list(STEP_MS), "setup_encode_s": round(first_encode_s, 3),
+        "note": "the headline leg alone; --full adds every other leg, the reference checks and the baselines"}),
+        flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -556,7 +637,15 @@ def main():
     ap.add_argument("--emulate", action="store_true",
                     help="CPU dry run of the control flow (gloo + the test-suite's emulation of the "
                          "kernels, tiny images): measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg of the line: the 1080p and 1 MPix legs, rooflines, batches, other configs, "
+                         "config 5, output hashes checked against the reference's, box calibration, CPU baseline "
+                         "(without it: only the headline leg and its result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline leg's last timed step returned to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config5:
+        ap.error("--dump-outputs: not available with --config5")
 
     env = Env(args)
     import images
@@ -566,6 +655,10 @@ def main():
     W, H = (40, 32) if emu else (1920, 1080)
     W4, H4 = (48, 40) if emu else (3840, 2160)
     quality = 84.0 if emu else QUALITY   # (the dry run: the shortest search)
+    if not args.full and not args.config5:
+        headline_only(env, args, host, images, (W, H) if args.no_4k else (W4, H4), quality)
+        env.finish()
+        return
     size5 = (W4, H4) if args.size == "4k" else (W, H)
     if emu:
         args.images_per_gpu = min(args.images_per_gpu, 2)
@@ -602,6 +695,8 @@ def main():
 
     dt, (jpg, info) = timed_steps(env, step, args.steps, args.warmup)
     step_ms_1080p = list(STEP_MS)
+    if args.no_4k:
+        dump_outputs(args.dump_outputs, rank, jpg)
     dt4k = jpg4k = info4k = step_ms_4k = first_encode_4k_s = compares_4k = None
     if not args.no_4k:
         # the process's first encode at this size, on its own like the 1080p one above: the pools grow from
@@ -615,6 +710,7 @@ def main():
         cc0 = L.compare_counters(all=True)
         dt4k, (jpg4k, info4k) = timed_steps(env, step4k, args.steps, args.warmup)
         step_ms_4k = list(STEP_MS)
+        dump_outputs(args.dump_outputs, rank, jpg4k)
         # how many of the encodes' Compares ran without their full reconstruction (gz_config.patch_reconstruct: the
         # calls that change the candidate keep its linear planes current); `roofline` always times the whole chain
         # (... and, for a lone context, their opsin image: gz_config.opsin_ahead)
@@ -762,25 +858,8 @@ def main():
             if jpg4k is not None:
                 sha = hashlib.sha256(jpg4k).hexdigest()
                 assert sha == GOLDEN_SHA_4K[95], f"3840x2160 output JPEG differs from the reference: {sha}"
-        timer_keys = ("total", "phase_b_host", "compare", "block_search", "jpeg_write", "create+encode",
-                      "select_quant_matrix", "pb_device_partitions", "pb_device_descents",
-                      "pb_device_fetches", "pb_loop_codes")
-
         def leg(w, h, seconds, jpeg, inf, which):
-            """value / ms_per_step / config of one timed size (both sizes are timed identically)."""
-            return (round(world * args.steps * w * h / 1e6 / seconds, 4), round(seconds / args.steps * 1e3, 2),
-                    {"workload": f"single {w}x{h} sRGB image, --quality {quality:g} (BASELINE {which}), whole "
-                                 "guetzli::Process per step (host RGB in, JPEG bytes out), 1 image per GPU "
-                                 f"per step; {args.steps} timed steps after {args.warmup} warm-up between "
-                                 "barrier + synchronise, max over ranks",
-                     "butteraugli_target": TARGET_Q95, "images_per_gpu": 1, "steps": args.steps,
-                     "warmup": args.warmup, "output_bytes": len(jpeg),
-                     "output_sha256_matches_reference": not emu,
-                     "iterations": inf["counters"].get("number of iterations"),
-                     # host threads of one encode: the search driver's own + the size model's code-refresh
-                     # helpers (guetzli_amd/host/code_refresh.h; `pb_loop_codes` is the driver WAITING for them)
-                     "host_code_refresh_threads": inf["counters"].get("phase B code refresh threads"),
-                     "host_timers_s": {k: round(v, 3) for k, v in inf["timers"].items() if k in timer_keys}})
+            return leg_record(w, h, seconds, jpeg, inf, which, world, args, quality, checked=not emu)
 
         def roof(w, h, ms_c, ach, key):
             t = traffic.get(key, {})

@@ -24,14 +24,14 @@ def _free_port():
         return str(so.getsockname()[1])
 
 
-def _run(world, extra=()):
+def _run(world, extra=(), full=True, steps=1):
     sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
     import build_emu
     build_emu.build_host()   # (built once here, not by two ranks at the same time)
     port = _free_port()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
-    args = [os.path.join(ROOT, "bench.py"), "--emulate", "--gpus", str(world), "--steps", "1",
-            "--warmup", "0", "--no-cpu-baseline"] + list(extra)
+    args = [os.path.join(ROOT, "bench.py"), "--emulate", "--gpus", str(world), "--steps", str(steps),
+            "--warmup", "0", "--no-cpu-baseline"] + (["--full"] if full else []) + list(extra)
     if world == 1:
         cmd = [sys.executable] + args
     else:
@@ -82,6 +82,28 @@ def test_bench_main_eight_ranks_gloo():
     assert c5["images"] == 8 and c5["n_ranks_seen"] == 8 and c5["ranks_in_records"] == list(range(8))
     assert c5["images_per_rank"] == {str(k): 1 for k in range(8)} and c5["distinct_outputs"] == 8
     assert r["scale_value"] == c5["value"]
+
+
+def test_bench_plain_run_is_the_headline_leg_alone(tmp_path):
+    """Without --full: the headline leg and its line, --steps timed steps, nothing else; --dump-outputs writes
+    the last timed step's JPEG, the same bytes from run to run and the same as --full's headline."""
+    import numpy as np
+    r = _run(1, ["--dump-outputs", str(tmp_path / "a")], full=False, steps=2)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in r, k
+    assert r["steps"] == 2 and len(r["step_ms"]) == 2 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert "configs[2]" in r["config"]["workload"] and r["value_workload"] == "48x40"
+    for k in ("roofline", "value_1080p", "other_configs", "scale_value", "cpu_baseline", "box", "config_1mpix"):
+        assert k not in r, k
+    a = np.load(tmp_path / "a" / "jpeg_bytes.npy")
+    assert a.dtype == np.float32 and a.size == r["config"]["output_bytes"]
+    assert a[:2].tolist() == [0xFF, 0xD8] and a[-2:].tolist() == [0xFF, 0xD9]   # SOI ... EOI
+    import hashlib
+    assert hashlib.sha256(a.astype(np.uint8).tobytes()).hexdigest() == r["config"]["output_sha256"]
+    _run(1, ["--dump-outputs", str(tmp_path / "b")], full=False)
+    assert np.array_equal(np.load(tmp_path / "b" / "jpeg_bytes.npy"), a)
+    f = _run(1, ["--dump-outputs", str(tmp_path / "c"), "--no-1mpix", "--no-config5", "--batch-images", "0"])
+    assert "roofline" in f and np.array_equal(np.load(tmp_path / "c" / "jpeg_bytes.npy"), a)
 
 
 def test_bench_config5_only_two_ranks_gloo():

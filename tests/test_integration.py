@@ -18,7 +18,7 @@ from checkers import ref
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "emu"))
-BUILD = os.path.join(HERE, "integration", "_build")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "integration")   # (reference binaries: built with oracle/_ref, travel with it)
 
 
 def _load(path):
@@ -65,7 +65,7 @@ def test_reference_processor_through_the_comparator_seam_in_emulation(kw):
     import build_emu
     out = os.path.join(BUILD, "libgz_integration_emu.so")
     if not _make(build_emu.build(), out):
-        pytest.skip("tests/integration/_build not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/integration not built (needs the reference tree)")
     lib = _load(out)
     rgb = images.crop(40, 32, 100, 60)
     target = ref._butteraugli_score_for_quality(95.0)
@@ -88,7 +88,7 @@ def test_patched_reference_processor_with_the_batched_hook_in_emulation(kw):
     import build_emu
     out = os.path.join(BUILD, "libgz_integration_batched_emu.so")
     if not _make(build_emu.build(), out, batched=True):
-        pytest.skip("tests/integration/_build not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/integration not built (needs the reference tree)")
     lib = _load(out)
     rgb = images.crop(40, 32, 100, 60)
     target = ref._butteraugli_score_for_quality(95.0)
@@ -104,7 +104,7 @@ def _gpu_lib(batched=False):
     from guetzli_amd import build as gzbuild
     out = os.path.join(BUILD, "libgz_integration_batched.so" if batched else "libgz_integration.so")
     if not _make(gzbuild.LIB, out, batched=batched):
-        pytest.skip("tests/integration/_build not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/integration not built (needs the reference tree)")
     assert guetzli_amd.load().device_count() >= 1
     return _load(out)
 
@@ -188,7 +188,7 @@ def test_unmodified_front_end_over_the_drop_in_process_in_emulation(tmp_path):
     import build_emu
     exe = os.path.join(BUILD, "guetzli_emu")
     if not _make_cli(build_emu.build_host(), exe):
-        pytest.skip("tests/integration/_build not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/integration not built (needs the reference tree)")
     rgb = images.crop(40, 32, 100, 60)
     for q in (95, 84):
         exp_jpg, exp_trace = ref.process(rgb, ref._butteraugli_score_for_quality(float(q)), want_trace=True)
@@ -219,7 +219,7 @@ def test_unmodified_front_end_over_the_drop_in_process_bees(tmp_path):
     from guetzli_amd import build as gzbuild
     exe = os.path.join(BUILD, "guetzli_hip")
     if not _make_cli(gzbuild.HOST_LIB, exe):
-        pytest.skip("tests/integration/_build not built (needs /root/reference)")
+        pytest.skip("oracle/_ref/integration not built (needs the reference tree)")
     data = open(images.BEES, "rb").read()
     rc, jpg, err = _cli(exe, [], data, tmp_path)
     assert rc == 0, err

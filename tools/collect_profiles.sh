@@ -16,7 +16,7 @@ stamp $T/pmc/block_search_pmc.csv $P/${RN}_block_search_pmc.csv "rocprofv3 --pmc
 EV=$(grep -o "[0-9]* CompareBlock evaluations" $T/pmc/search_1080p.log | head -1 | cut -d" " -f1)
 [ -n "$EV" ] && sed -i "1a # evaluations per launch $EV" $P/${RN}_block_search_pmc.csv
 python3 tools/pmc_traffic_json.py $T/pmc/compare_4k_pmc.csv $T/pmc/compare_1080p_pmc.csv $T/pmc/bw_pmc.csv | python3 -c "import json,sys; d=json.load(sys.stdin); d['head']='$H'; print(json.dumps(d, indent=1))" > $P/${RN}_compare_pmc_traffic.json
-stamp $T/bench_kernel_stats.csv $P/${RN}_bench_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-config5 --batch-images 0"
+stamp $T/bench_kernel_stats.csv $P/${RN}_bench_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-config5 --batch-images 0"
 python3 -c "import json; d=json.load(open('$T/bench.json')); d['head']='$H'; print(json.dumps(d))" > $P/${RN}_bench.json
 cp $T/compare_chain.log $P/${RN}_compare_chain.log
 cp $T/encode_timers.log $P/${RN}_encode_timers.log

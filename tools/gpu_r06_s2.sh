@@ -18,4 +18,4 @@ for rep in 1 2; do
   done
 done
 } 2>&1 | tee $O/coresidency.log
-python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err

@@ -19,4 +19,4 @@ done
 echo "== single encodes"
 for cfg in "GZ_NONE=1" "GZ_CODE_THREADS=3"; do echo "== $cfg"; env $cfg python tools/encode_time.py 3840 2160 95 4 2>&1 | tail -2; env $cfg python tools/encode_time.py 1024 1024 95 6 2>&1 | tail -2; done
 } 2>&1 | tee $O/threads.log
-python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
