@@ -29,11 +29,7 @@ ARCH = "gfx950"
 # (1080p) with it off (profiles/r02_packed_blur_and_malta_diff_experiments.log, section 8).  The
 # kernels that want packed arithmetic ask for it explicitly (gz_f2).  Same results either way.
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-         "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-mllvm", "-vectorize-slp=false",
-         # the fused blurs' taps in vector registers (gz_common.h GZ_IN_VGPR: a scalar-register operand
-         # makes v_mul_f32 a 4-cycle instruction, tools/ubench/issue.hip): chain -0.7 % at 4K beside
-         # Malta, nothing serialised (profiles/r05_variants.log)
-         "-DGZ_TAPS_VGPR"]
+         "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-mllvm", "-vectorize-slp=false"]
 
 
 def _newer_than_lib():
@@ -165,9 +161,11 @@ def build_host(force=False, verbose=False, device_lib=None, out=None):
         f, first[0] = first[0], False
         return (force and f) or not os.path.exists(out) or \
             any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps if os.path.exists(d))
+    # $ORIGIN first: a copy of the tree must load the device library beside it, not the one of the directory it was
+    # built in (two copies in one process: the host driver's kernels and the caller's counters in different ones)
     return locked_compile(out, stale, lambda tmp: ["g++"] + HOST_FLAGS + srcs +
-                          ["-o", tmp, "-L" + libdir, "-l:" + libname, "-Wl,-rpath," + libdir,
-                           "-Wl,-rpath,$ORIGIN", "-lz"], verbose)
+                          ["-o", tmp, "-L" + libdir, "-l:" + libname, "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath," + libdir, "-lz"], verbose)
 
 
 if __name__ == "__main__":

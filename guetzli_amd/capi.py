@@ -25,7 +25,7 @@ _I = C.c_int
 class GzConfig(C.Structure):
     """gz_config of include/guetzli_amd.h."""
     _fields_ = [("struct_size", _I), ("blur_packed", _I), ("tile_rows", _I), ("single_stream", _I),
-                ("store_distmap", _I), ("side_small", _I), ("malta_pad_bytes", _I), ("patch_reconstruct", _I), ("opsin_ahead", _I)]
+                ("store_distmap", _I), ("patch_reconstruct", _I), ("opsin_ahead", _I)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

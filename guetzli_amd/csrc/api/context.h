@@ -107,20 +107,34 @@ struct HandlePool {
   std::multimap<int, hipEvent_t> events;
 };
 HandlePool& handle_pool() { static HandlePool p; return p; }
-// prio: 0 = default, +1 = the device's highest priority, -1 = its lowest.  Who takes which:
-// create_context.
-static bool stream_priorities() {   // GZ_STREAM_PRIO=0: no priority stream even for a lone context (A/B)
-  static const bool v = [] { const char* e = getenv("GZ_STREAM_PRIO"); return e ? atoi(e) != 0 : true; }();
-  return v;
+// Slots of the contexts alive per device (the lowest free one first).  A context's slot picks the rotation of its
+// stream set (create_context), and the number of slots taken says whether the device has company (chain.h).
+struct DeviceSlots {
+  std::mutex mu;
+  std::map<int, std::vector<bool> > used;
+};
+inline DeviceSlots& device_slots() { static DeviceSlots s; return s; }
+// Takes the lowest free slot on `device`; *taken_before = the slots that were taken before.
+inline int slot_take(int device, int* taken_before) {
+  DeviceSlots& ds = device_slots();
+  std::lock_guard<std::mutex> lk(ds.mu);
+  std::vector<bool>& u = ds.used[device];
+  *taken_before = (int)std::count(u.begin(), u.end(), true);
+  for (size_t i = 0; i < u.size(); ++i) if (!u[i]) { u[i] = true; return (int)i; }
+  u.push_back(true);
+  return (int)u.size() - 1;
 }
-// Contexts alive per device: adds `delta`, returns the count before.
-static int live_contexts(int device, int delta) {
-  static std::mutex mu;
-  static std::map<int, int> live;
-  std::lock_guard<std::mutex> lk(mu);
-  const int before = live[device];
-  live[device] = before + delta;
-  return before;
+inline void slot_release(int device, int slot) {
+  DeviceSlots& ds = device_slots();
+  std::lock_guard<std::mutex> lk(ds.mu);
+  std::vector<bool>& u = ds.used[device];
+  if (slot >= 0 && (size_t)slot < u.size()) u[(size_t)slot] = false;
+}
+inline int slots_taken(int device) {
+  DeviceSlots& ds = device_slots();
+  std::lock_guard<std::mutex> lk(ds.mu);
+  const std::vector<bool>& u = ds.used[device];
+  return (int)std::count(u.begin(), u.end(), true);
 }
 // A context's four streams are created, pooled and reused TOGETHER.  The HIP runtime spreads streams
 // over its hardware queues (GPU_MAX_HW_QUEUES, 4 by default) in creation order, so four streams made
@@ -131,116 +145,35 @@ static int live_contexts(int device, int delta) {
 // quality-84 encode 0.177 instead of 0.150 s (profiles/r05_chain_experiments.log, section 10).
 struct StreamSet {
   hipStream_t own = nullptr, side = nullptr, side2 = nullptr, entropy = nullptr;
-  int rot = 0;   // position of `own` in the set's creation order = the hardware queue (mod 4) its main stream sits on
 };
 struct StreamSetPool {
   std::mutex mu;
-  std::multimap<int, StreamSet> sets;   // stream_set_key(): device, CU class, main stream at the highest priority
+  std::multimap<int, StreamSet> sets;   // stream_set_key(): device, rotation, main stream at the highest priority (bit 0)
 };
 inline StreamSetPool& stream_set_pool() { static StreamSetPool p; return p; }
+inline int stream_set_key(int device, bool prio_main, int rot) { return (device * 4 + rot) * 2 + (prio_main ? 1 : 0); }
 
-// CU-partitioned stream sets (round 6; GZ_CU_PARTITION = P in {2, 4, 8}, default off): the contexts alive on a
-// device take SLOTS (the lowest free one), and the four streams of the context in slot s are created with
-// hipExtStreamCreateWithCUMask on the (s mod P)-th P-th of the device's CUs, so that P images in flight
-// run on disjoint CUs instead of time-sharing all of them.  Which CUs a run of mask bits names: the
-// kernel driver deals the bits round-robin over the XCDs and, inside an XCD, over its shader engines
-// (bit i -> XCD i mod 8, engine (i / 8) mod 4), so a contiguous P-th of the 256 bits is 32 / P CUs of
-// EVERY XCD, spread over its engines -- every stream still sees all eight L2s and a dispatch's
-// round-robin of workgroups over the XCDs finds CUs on each (tools/ubench/cumask.hip prints the map).
-// GZ_CU_MAIN / GZ_CU_SIDE = "lo:hi" (bit ranges; experiments on ONE image: the chain's main stream and
-// its two side streams on separate CUs).  CU class 0 = no mask.
-struct CuPlan { int parts = 0; int main_lo = -1, main_hi = -1, side_lo = -1, side_hi = -1; };
-inline const CuPlan& cu_plan() {
-  static const CuPlan plan = [] {
-    CuPlan p;
-    if (const char* e = getenv("GZ_CU_PARTITION")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) p.parts = v; }
-    if (const char* e = getenv("GZ_CU_MAIN")) (void)sscanf(e, "%d:%d", &p.main_lo, &p.main_hi);
-    if (const char* e = getenv("GZ_CU_SIDE")) (void)sscanf(e, "%d:%d", &p.side_lo, &p.side_hi);
-    return p;
-  }();
-  return plan;
-}
-// Slots of the contexts alive per device (lowest free first).
-struct CuSlots {
-  std::mutex mu;
-  std::map<int, std::vector<bool> > used;
-};
-inline CuSlots& cu_slots() { static CuSlots s; return s; }
-inline int cu_slot_take(int device) {
-  CuSlots& cs = cu_slots();
-  std::lock_guard<std::mutex> lk(cs.mu);
-  std::vector<bool>& u = cs.used[device];
-  for (size_t i = 0; i < u.size(); ++i) if (!u[i]) { u[i] = true; return (int)i; }
-  u.push_back(true);
-  return (int)u.size() - 1;
-}
-inline void cu_slot_release(int device, int slot) {
-  CuSlots& cs = cu_slots();
-  std::lock_guard<std::mutex> lk(cs.mu);
-  std::vector<bool>& u = cs.used[device];
-  if (slot >= 0 && (size_t)slot < u.size()) u[(size_t)slot] = false;
-}
-#ifndef GZ_EMU
-static hipError_t create_stream_on_cus(hipStream_t* out, int lo, int hi) {
-  hipDeviceProp_t prop;
-  int device = 0;
-  (void)hipGetDevice(&device);
-  hipError_t e = hipGetDeviceProperties(&prop, device);
-  if (e != hipSuccess) return e;
-  const int ncu = prop.multiProcessorCount;
-  lo = std::max(0, std::min(lo, ncu)); hi = std::max(lo, std::min(hi, ncu));
-  if (hi - lo <= 0 || hi - lo >= ncu) return hipStreamCreate(out);
-  std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-  for (int i = lo; i < hi; ++i) mask[(size_t)i >> 5] |= 1u << (i & 31);
-  return hipExtStreamCreateWithCUMask(out, (uint32_t)mask.size(), mask.data());
-}
-#endif
-inline int stream_set_key(int device, bool prio_main, int cu_class) {
-  return (device * 64 + cu_class) * 2 + (prio_main && stream_priorities() ? 1 : 0);
-}
-
-// want_rot >= 0 (the default; GZ_SET_SLOT=0 switches it off): a set whose main stream sits on that hardware queue -- the contexts alive on a
-// device take slots, slot s asks for rotation s mod 4, so that four images in flight have their main streams on four
-// different queues whatever order the images finished in.
-hipError_t pool_stream_set_create(StreamSet* out, bool prio_main, int cu_class, int want_rot = -1) {
+// A set of rotation `rot` (0..3) is created in an order rotated by `rot`: its MAIN stream at position `rot` -- the
+// hardware queue (mod 4) it sits on -- and its three other streams on the three other queues.  With every set made in
+// the same order the main streams of the four images in flight all shared one queue, and a batch of eight 4K images
+// fell from 39 to 32 MPix/s (section 10 of the experiment log).  prio_main: the main stream at the device's highest
+// priority (who takes one: create_context).  Up to 4 idle sets are kept per key, 16 per device and priority.
+hipError_t pool_stream_set_create(StreamSet* out, bool prio_main, int rot) {
 #ifndef GZ_EMU
   int device = 0;
   (void)hipGetDevice(&device);
-  const int key = stream_set_key(device, prio_main, cu_class);
   StreamSetPool& p = stream_set_pool();
   std::lock_guard<std::mutex> lk(p.mu);   // (also keeps two threads' creations from interleaving)
-  {
-    auto range = p.sets.equal_range(key);
-    for (auto it = range.first; it != range.second; ++it)
-      if (want_rot < 0 || it->second.rot == want_rot) { *out = it->second; p.sets.erase(it); return hipSuccess; }
-  }
-  // The k-th set is created in an order rotated by k, so that the k-th context's MAIN stream sits on
-  // hardware queue k mod 4 and its three other streams on the three other queues: with every set made
-  // in the same order the main streams of the four images in flight all shared one queue, and a batch
-  // of eight 4K images fell from 39 to 32 MPix/s (section 10 of the experiment log).
-  static int serial = 0;
-  const int rot = want_rot >= 0 ? (want_rot & 3) : ((serial++) & 3);
-  out->rot = rot;
-  hipStream_t* slot[4] = {&out->own, &out->side, &out->side2, &out->entropy};
+  auto it = p.sets.find(stream_set_key(device, prio_main, rot));
+  if (it != p.sets.end()) { *out = it->second; p.sets.erase(it); return hipSuccess; }
+  hipStream_t* dst[4] = {&out->own, &out->side, &out->side2, &out->entropy};
   int least = 0, greatest = 0;
-  const bool prio = (key & 1) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
-  const CuPlan& cp = cu_plan();
+  const bool prio = prio_main && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
   hipError_t e = hipSuccess;
   for (int j = 0; j < 4 && e == hipSuccess; ++j) {
     const int which = (j + 4 - rot) & 3;   // position j of the creation order takes stream `which`: own at position rot
-    if (cu_class > 0 && cp.parts > 0) {        // a batch's image: all four streams on its share of the CUs
-      int ncu = 256;
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-      const int per = ncu / cp.parts, s = (cu_class - 1) % cp.parts;
-      e = create_stream_on_cus(slot[which], s * per, (s + 1) * per);
-    } else if (cu_class > 0 && which == 0 && cp.main_lo >= 0) {
-      e = create_stream_on_cus(slot[which], cp.main_lo, cp.main_hi);
-    } else if (cu_class > 0 && (which == 1 || which == 2) && cp.side_lo >= 0) {
-      e = create_stream_on_cus(slot[which], cp.side_lo, cp.side_hi);
-    } else {
-      e = which == 0 && prio ? hipStreamCreateWithPriority(slot[which], hipStreamDefault, greatest)
-                             : hipStreamCreate(slot[which]);
-    }
+    e = which == 0 && prio ? hipStreamCreateWithPriority(dst[which], hipStreamDefault, greatest)
+                           : hipStreamCreate(dst[which]);
   }
   return e;
 #else
@@ -251,15 +184,15 @@ hipError_t pool_stream_set_create(StreamSet* out, bool prio_main, int cu_class, 
   return e;
 #endif
 }
-void pool_stream_set_destroy(const StreamSet& s_, bool prio_main, int cu_class) {
+void pool_stream_set_destroy(const StreamSet& s_, bool prio_main, int rot) {
 #ifndef GZ_EMU
   if (s_.own && s_.side && s_.side2 && s_.entropy && pool_limit_bytes() != 0) {
     int device = 0;
     (void)hipGetDevice(&device);
-    const int key = stream_set_key(device, prio_main, cu_class);
+    const int key = stream_set_key(device, prio_main, rot);
     StreamSetPool& p = stream_set_pool();
     std::lock_guard<std::mutex> lk(p.mu);
-    if (p.sets.count(key) < 16) { p.sets.insert(std::make_pair(key, s_)); return; }
+    if (p.sets.count(key) < 4) { p.sets.insert(std::make_pair(key, s_)); return; }
   }
 #endif
   if (s_.own) (void)hipStreamDestroy(s_.own);
@@ -326,12 +259,10 @@ struct gz_ctx {
   // second stream for the branch of Compare that does not depend on the Malta path (the
   // mask: DiffPrecompute + three blurs), forked and joined with events
   hipStream_t side_stream = nullptr, side_stream2 = nullptr;
-  bool prio_streams = false, counted_live = false;   // (see create_context)
+  bool prio_streams = false;   // (see create_context)
   bool single_now = false;   // (chain.h choose_streams: this Compare's kernels on the main stream only)
-  bool side_small = false;   // (chain.h: set while the side branches' launches are made, cfg.side_small)
   gz_config cfg;             // run-time configuration (include/guetzli_amd.h): the environment's, read once at gz_create
-  int set_rot = 0;           // the stream set's rotation (goes back to the pool with it)
-  int cu_slot = -1, cu_class = 0;   // CU-partitioned stream sets (cu_plan): the context's slot; 0 = unmasked streams
+  int slot = -1;             // the context's slot on its device (slot_take); its stream set has rotation slot % 4
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_mask_pre = nullptr;
   hipEvent_t ev_next_cand = nullptr;   // next_cand uploaded beside a Compare chain in flight
   hipEvent_t ev_xyb = nullptr, ev_lfy = nullptr;   // B plane's LF blur on side stream 2 (stage_separate)

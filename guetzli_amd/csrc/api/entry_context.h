@@ -6,7 +6,7 @@
 extern "C" {
 
 
-int gz_abi_version(void) { return 5; }
+int gz_abi_version(void) { return 6; }
 
 int gz_config_from_environment(gz_config* out) {
   if (!out) return GZ_E_ARG;
@@ -19,8 +19,6 @@ int gz_config_from_environment(gz_config* out) {
   if (const char* e = getenv("GZ_TILE_ROWS")) { const int v = atoi(e); if (v == 16 || v == 32) c.tile_rows = v; }
   if (const char* e = getenv("GZ_SINGLE_STREAM")) c.single_stream = atoi(e) != 0;
   if (const char* e = getenv("GZ_STORE_DISTMAP")) c.store_distmap = atoi(e) != 0;
-  if (const char* e = getenv("GZ_SIDE_SMALL")) c.side_small = atoi(e) != 0;
-  if (const char* e = getenv("GZ_MALTA_PAD")) c.malta_pad_bytes = std::max(0, std::min(64 << 10, atoi(e)));
   c.patch_reconstruct = 1;
   if (const char* e = getenv("GZ_PATCH_RECON")) { const int v = atoi(e); if (v >= 0 && v <= 2) c.patch_reconstruct = v; }
   c.opsin_ahead = 1;
@@ -36,7 +34,7 @@ int gz_get_config(const gz_ctx* c, gz_config* out) {
 int gz_set_config(gz_ctx* c, const gz_config* in) {
   if (!c || !in || in->struct_size != (int)sizeof(gz_config)) return GZ_E_ARG;
   if (in->blur_packed < -1 || in->blur_packed > 1 || in->single_stream < -1 || in->single_stream > 1 || (in->tile_rows != 0 && in->tile_rows != 16 && in->tile_rows != 32) ||
-      in->malta_pad_bytes < 0 || in->malta_pad_bytes > (64 << 10) || in->patch_reconstruct < 0 || in->patch_reconstruct > 2)
+      in->patch_reconstruct < 0 || in->patch_reconstruct > 2)
     return GZ_E_ARG;
   if (c->compare_pending || c->scan_pending || c->order_pending || c->desc_pending) {
     c->err = "gz_set_config while work of the context is in flight";
@@ -172,26 +170,17 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, floa
   // image's low-priority entropy coder starves behind the other images' chains while its host
   // thread waits for it: 16 x 1080p, 8 in flight, 21.8 -> 7.5-13.5 MPix/s with main = highest and
   // entropy = lowest on every context; profiles/r03_stream_priorities.log).
-  c->prio_streams = live_contexts(device, +1) == 0 && images_in_flight_hint().load(std::memory_order_relaxed) <= 1;
-  c->counted_live = true;
+  int taken_before = 0;
+  c->slot = slot_take(device, &taken_before);
+  c->prio_streams = taken_before == 0 && images_in_flight_hint().load(std::memory_order_relaxed) <= 1;
   {
-    const CuPlan& cp = cu_plan();
-    if (cp.parts > 0) {
-      c->cu_slot = cu_slot_take(device);
-      c->cu_class = 1 + c->cu_slot % cp.parts;
-    } else if (cp.main_lo >= 0 || cp.side_lo >= 0) {
-      c->cu_class = 1;
-    }
     StreamSet ss;
     // The contexts alive on a device take slots (lowest free first) and slot s gets a stream set whose MAIN stream
     // sits on hardware queue s mod 4: four images in flight then have their main streams on four different queues
     // whatever order the images before them finished in (handed out by availability, two mains could share a queue:
     // the "40 or 44-46 MPix/s" of a 4K batch from process to process; 16 x 1080p 35.4 -> 39.7 MPix/s, 12 x 1440p 38.9 ->
-    // 40.2, 8 x 4K 42.4 -> 43.6, nothing at 1 MPix and below: r06_chain_experiments.log, section 12).  GZ_SET_SLOT=0: as before.
-    static const bool set_slot = [] { const char* e = getenv("GZ_SET_SLOT"); return e ? atoi(e) != 0 : true; }();
-    if (set_slot && c->cu_slot < 0) c->cu_slot = cu_slot_take(device);
-    const hipError_t se = pool_stream_set_create(&ss, c->prio_streams, c->cu_class, set_slot ? c->cu_slot % 4 : -1);
-    c->set_rot = ss.rot;
+    // 40.2, 8 x 4K 42.4 -> 43.6, nothing at 1 MPix and below: r06_chain_experiments.log, section 12).
+    const hipError_t se = pool_stream_set_create(&ss, c->prio_streams, c->slot % 4);
     c->own_stream = ss.own; c->side_stream = ss.side; c->side_stream2 = ss.side2; c->entropy_stream = ss.entropy;
     c->stream = c->own_stream;
     CHK0(se);
@@ -337,11 +326,9 @@ void gz_destroy(gz_ctx* c) {
   {   // the four streams go back as the set they were made as (own_stream: synchronised at the top of gz_destroy)
     StreamSet ss;
     ss.own = c->own_stream; ss.side = c->side_stream; ss.side2 = c->side_stream2; ss.entropy = c->entropy_stream;
-    ss.rot = c->set_rot;
-    pool_stream_set_destroy(ss, c->prio_streams, c->cu_class);
+    pool_stream_set_destroy(ss, c->prio_streams, c->slot % 4);
   }
-  if (c->cu_slot >= 0) cu_slot_release(c->device, c->cu_slot);
-  if (c->counted_live) (void)live_contexts(c->device, -1);
+  if (c->slot >= 0) slot_release(c->device, c->slot);
   delete c;
 }
 

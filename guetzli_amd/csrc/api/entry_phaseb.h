@@ -349,10 +349,6 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
     // (persistent workgroups: four per CU's worth at most, each wavefront taking several blocks)
     // (the kernel reads the staging buffer itself -- page-locked and mapped: a copy command in front of
     // it costs more in hand-overs between commands than the 8 bytes per block cost over the bus)
-#ifdef GZ_STEPS_COPY_IN   // (A/B: the copy command in front of the kernel)
-    HIPCHK(c, hipMemcpyAsync(d_blocks, h, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    h = d_blocks;
-#endif
     // the touched block positions of the candidate's linear planes are transformed again behind the statistics
     // (chain.h, enqueue_compare), while they are a minority: beyond that the next Compare reconstructs the image
     const bool patch = patch_wanted(c, n);

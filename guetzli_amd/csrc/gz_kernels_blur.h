@@ -717,13 +717,11 @@ __global__ __launch_bounds__(256, 4) void k_blur2d(SrcPack<Src, NC> src, Post po
       if (c == k) s = src.s[k];
     if (c > 0) __syncthreads();   // the column pass of the previous plane is done with the tile
     if (interior) {
-#ifdef GZ_TAPS_VGPR
+      // the taps in vector registers (GZ_IN_VGPR: a scalar-register operand makes v_mul_f32 a 4-cycle instruction,
+      // tools/ubench/issue.hip): chain -0.7 % at 4K beside Malta, nothing serialised (profiles/r05_variants.log)
       float kv[2 * R + 1];
 #pragma unroll
       for (int j = 0; j <= 2 * R; ++j) kv[j] = GZ_IN_VGPR(taps.ks[j]);
-#else
-      const float* kv = taps.ks;
-#endif
       // ---- stage: aligned 16-byte loads, all of a thread's loads in flight before the
       // first LDS store (compile-time trip counts: the loads are issued back to back)
       constexpr int NV = IH * (IW / 4);            // 16-byte vectors in the tile

@@ -149,9 +149,6 @@ struct SearchLds {
   double red[kEvalBatch][3];
   float err[kEvalBatch];
   int num;
-#ifdef GZ_SEARCH_LDS_PAD
-  char pad[GZ_SEARCH_LDS_PAD];   // (experiment: fewer wavefronts per CU)
-#endif
 };
 // Round 4 took the struct from 12 672 to 10 064 bytes: the sRGB table is read from global memory (three
 // L1-resident loads per evaluation instead of three LDS reads at random banks), the pixel cache holds
@@ -159,9 +156,7 @@ struct SearchLds {
 // original's opsin image and the candidate's linear RGB live in registers; the blur's plane between its
 // passes carries four rows of zeros, the coefficients are kept transposed as well, and the column
 // stage's power terms replace its input in place (8 416 bytes: LDS no longer decides the occupancy).
-#ifndef GZ_SEARCH_LDS_PAD
 static_assert(sizeof(SearchLds) <= 160 * 1024 / 16, "k_block_search: four wavefronts per SIMD need <= 10 KB each");
-#endif
 
 // 4:2:0 chroma search only (MODE 2): the 10x10 subsampled samples around the 16x16 block
 // (UpdatePixelsForBlock's `subsampled`, output_image.cc:150-183) per chroma component.

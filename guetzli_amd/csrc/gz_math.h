@@ -246,9 +246,6 @@ GZ_DEVFN void div2_shared(float n0, float n1, float d, float* q0, float* q1) {
 //    x - (-y) == x + y == y + x -- and d -/+ impact is d + (-/+ impact); round 5: the two cases as
 //    one maximum (below), the FP64 form of absval behind a wavefront-uniform branch.
 GZ_DEVFN float malta_diff(float a, float b, const MaltaNorm nm) {
-#ifdef GZ_MALTA_DIFF_PLAIN
-  return malta_diff_plain(a, b, nm);
-#endif
   const float fa = fabsf(a), fb = fabsf(b);
   const float s = fa + fb;
   float absval = 0.5f * s;

@@ -256,7 +256,6 @@ struct HostKnobs {
   int code_threads = -1;              // GZ_CODE_THREADS: helper threads of the code refreshes (-1: by the cores)
   size_t parallel_count_min = (size_t)1 << 20;   // GZ_PARALLEL_COUNT_MIN: step counts on the worker pool from this many entries on
   long code_serial_steps = 30;        // GZ_CODE_SERIAL_STEPS: serial steps before the helpers are called in (0: at once)
-  bool step_prefetch = true;          // GZ_STEP_PREFETCH=0: no cache-line prefetches ahead of the serial steps
   bool check_mirror = false;          // GZ_CHECK_MIRROR: host mirror against the device image after every search
   int verify_level = 0;               // GZ_VERIFY_ENTROPY=1|2: every candidate also through the host writer
   long order_device_threshold = -1;   // GZ_ORDER_DEVICE_THRESHOLD: ranges above this are partitioned on the device
@@ -265,7 +264,6 @@ struct HostKnobs {
     if (const char* e = getenv("GZ_CODE_THREADS")) k.code_threads = std::max(0, std::min(4, atoi(e)));
     if (const char* e = getenv("GZ_PARALLEL_COUNT_MIN")) k.parallel_count_min = (size_t)atol(e);
     if (const char* e = getenv("GZ_CODE_SERIAL_STEPS")) k.code_serial_steps = atol(e) / 10 * 10;
-    if (const char* e = getenv("GZ_STEP_PREFETCH")) k.step_prefetch = atoi(e) != 0;
     k.check_mirror = getenv("GZ_CHECK_MIRROR") != nullptr;
     if (const char* e = getenv("GZ_VERIFY_ENTROPY")) k.verify_level = std::max(1, atoi(e));
     if (const char* e = getenv("GZ_ORDER_DEVICE_THRESHOLD")) k.order_device_threshold = std::max(16L, atol(e));
@@ -1327,7 +1325,6 @@ void Encoder::StepsWithHelpers(MaskSearch* msp, Iteration* itp, SortedOrder* sor
   // cache misses, which is what a step costs.  The steps to come are known (the sorted order),
   // so their lines are asked for ahead, one dependency per stage.  (A block that advances in
   // between makes a prefetch miss its mark by a candidate; nothing depends on these.)
-  const bool prefetch_ahead = knobs_.step_prefetch;
   auto prefetch_for = [&](size_t i) {
     if (i + 12 < n_order) {
       const int b1 = sorted[i + 12].first;
@@ -1351,7 +1348,7 @@ void Encoder::StepsWithHelpers(MaskSearch* msp, Iteration* itp, SortedOrder* sor
     }
   };
   auto take_step = [&](size_t i) {
-    if (prefetch_ahead) prefetch_for(i);
+    prefetch_for(i);
     const int b = sorted[i].first;
     SettleBlock(msp, b);
     const int idx = cand_idx[cand_off[b] + next_cand[b] + std::min(direction, 0)];

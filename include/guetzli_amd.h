@@ -49,7 +49,7 @@ extern "C" {
 typedef struct gz_ctx gz_ctx;
 
 /* Library / device ------------------------------------------------------------ */
-int gz_abi_version(void);                 /* currently 5 (4 + gz_config.patch_reconstruct, .opsin_ahead, gz_compare_counters) */
+int gz_abi_version(void);                 /* currently 6 (5 without the two experiment fields of gz_config) */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -74,8 +74,7 @@ int gz_device_pci_bus_id(int device, char* out, int cap);
  * named below), gz_get_config / gz_set_config read and replace it (between calls, never while work of the
  * context is in flight).  None of the fields changes a result bit: they choose kernel instantiations and
  * stream use, and exist for the tests (every instantiation on small images) and for A/B measurements.
- * Process-wide settings stay in the environment, read once: GZ_POOL_MB (cache of freed device memory),
- * GZ_CU_PARTITION / GZ_CU_MAIN / GZ_CU_SIDE (CU-masked stream sets, experiments). */
+ * Process-wide settings stay in the environment, read once: GZ_POOL_MB (cache of freed device memory). */
 typedef struct gz_config {
   int struct_size;      /* sizeof(gz_config) as the caller compiled it (checked by gz_set_config) */
   int blur_packed;      /* GZ_BLUR_PK      -1: by image size (row / column pairs from 1.5 MPix on); 0, 1: forced */
@@ -84,8 +83,6 @@ typedef struct gz_config {
                                             flight), three for a lone context; 0: always three; 1: always one */
   int store_distmap;    /* GZ_STORE_DISTMAP 1: every Compare stores the distance map (default: only gz_compare with
                                             distmap != NULL and the stage probes do) */
-  int side_small;       /* GZ_SIDE_SMALL    1: side-branch blurs in Malta-sized forms (experiment, round 6) */
-  int malta_pad_bytes;  /* GZ_MALTA_PAD     unused dynamic LDS per Malta workgroup (experiment, round 6) */
   int patch_reconstruct;/* GZ_PATCH_RECON   1 (default): gz_apply_candidate_steps / gz_apply_coeff_edits transform the block
                                             positions they change again (4:4:4 frames of half a megapixel and more, while
                                             fewer than half of the blocks change) and the Compare behind them skips its

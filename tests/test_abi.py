@@ -36,7 +36,7 @@ def test_every_declared_symbol_is_exported(lib_path):
 
 def test_argument_errors_and_no_silent_fallback(lib_path):
     L = capi.Library(lib_path)
-    assert L.lib.gz_abi_version() == 5
+    assert L.lib.gz_abi_version() == 6
     assert L.lib.gz_strerror(-2).decode() == "no usable HIP device"
     err = C.c_int(0)
     rgb = np.zeros((16, 16, 3), np.uint8)
@@ -60,17 +60,17 @@ def test_config_struct(lib_path, monkeypatch):
     """gz_config: filled from the environment once (gz_config_from_environment needs no device), bad arguments are
     codes."""
     L = capi.Library(lib_path)
-    for k in ("GZ_BLUR_PK", "GZ_TILE_ROWS", "GZ_SINGLE_STREAM", "GZ_STORE_DISTMAP", "GZ_SIDE_SMALL", "GZ_MALTA_PAD", "GZ_PATCH_RECON", "GZ_OPSIN_AHEAD"):
+    for k in ("GZ_BLUR_PK", "GZ_TILE_ROWS", "GZ_SINGLE_STREAM", "GZ_STORE_DISTMAP", "GZ_PATCH_RECON", "GZ_OPSIN_AHEAD"):
         monkeypatch.delenv(k, raising=False)
     d = L.config_from_environment().as_dict()
     assert d == {"struct_size": C.sizeof(capi.GzConfig), "blur_packed": -1, "tile_rows": 0, "single_stream": -1,
-                 "store_distmap": 0, "side_small": 0, "malta_pad_bytes": 0, "patch_reconstruct": 1, "opsin_ahead": 1}
+                 "store_distmap": 0, "patch_reconstruct": 1, "opsin_ahead": 1}
     monkeypatch.setenv("GZ_BLUR_PK", "0")
     monkeypatch.setenv("GZ_TILE_ROWS", "32")
     monkeypatch.setenv("GZ_SINGLE_STREAM", "1")
-    monkeypatch.setenv("GZ_MALTA_PAD", "7400")
+    monkeypatch.setenv("GZ_PATCH_RECON", "2")
     d = L.config_from_environment().as_dict()
-    assert (d["blur_packed"], d["tile_rows"], d["single_stream"], d["malta_pad_bytes"]) == (0, 32, 1, 7400)
+    assert (d["blur_packed"], d["tile_rows"], d["single_stream"], d["patch_reconstruct"]) == (0, 32, 1, 2)
     monkeypatch.setenv("GZ_TILE_ROWS", "24")     # not a tile height: ignored
     assert L.config_from_environment().tile_rows == 0
     cfg = capi.GzConfig()

@@ -174,8 +174,7 @@ def test_config_struct_chooses_instantiations_not_results(L):
             pc.assert_bits_equal(bm, bm0, "block maxima with a second context alive")
             other.compare()
         for kw in (dict(blur_packed=1, tile_rows=32), dict(blur_packed=0, tile_rows=16), dict(single_stream=1),
-                   dict(single_stream=0), dict(blur_packed=1, tile_rows=16, store_distmap=1),
-                   dict(side_small=1, malta_pad_bytes=7400)):
+                   dict(single_stream=0), dict(blur_packed=1, tile_rows=16, store_distmap=1)):
             ctx.set_config(**dict(base, **kw))
             d, dm, bm = ctx.compare()
             assert d == d0, kw

@@ -6,7 +6,7 @@
 //                           to the XCDs that have no CU: run under `timeout`, last
 //   ./cumask pair LO1 HI1 LO2 HI2   two streams on disjoint CU ranges running the same VALU-bound kernel
 //                           at once vs one after the other vs both unmasked (does partitioning isolate?)
-// Background: guetzli_amd/csrc/api/context.h (cu_plan): a batch's images on disjoint CUs.
+// Background: profiles/r06_chain_experiments.log (CU-partitioned stream sets: a batch's images on disjoint CUs).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
