@@ -299,10 +299,9 @@ struct gz_ctx {
   float* sup0[2];   // the original's half of DiffPrecompute (k_mask_sup of pi0: X, Y), per image
   float* sup_scratch[2] = {nullptr, nullptr};   // the same for Mask() on raw planes (block mask, probe)
   float *mask_out[3], *mask_dc_out[3];
-  bool have_mask_out = false;
 
   float* d_block_mask = nullptr;   // [3][nb] mask_xyz_ at block corners (StartBlockComparisons)
-  bool have_block_mask = false;
+  bool have_block_mask = false;   // (see "What the flags claim" below)
   int32_t* d_rank_cnt = nullptr; uint8_t* d_rank_idx = nullptr; float* d_rank_tables = nullptr;
   int32_t* d_out_cnt = nullptr; uint8_t* d_out_idx = nullptr; float* d_out_err = nullptr;
   int32_t* d_csr_off = nullptr;   // the search's CSR offsets (k_csr_offsets); the packed indices reuse d_rank_idx
@@ -353,10 +352,20 @@ struct gz_ctx {
   unsigned char* d_wflag = nullptr;                               // [nb]
   int* d_edit_pos = nullptr; short* d_edit_val = nullptr; size_t edit_cap = 0;
 
+  // ---- What the flags claim.
+  // The original: have_orig (d_orig holds its coefficients), have_block_mask (d_block_mask is StartBlockComparisons'
+  // mask of d_rgb); pi0 and sup0 have no flag: gz_set_rgb writes them, and a failed gz_set_rgb leaves them undefined.
+  // The candidate: have_cand (d_cand holds one), and what is derived from it: lin_is_cand, xyb_is_cand, have_distmap
+  // (the last Compare's distance map and block maxima are in place), h_block_max_valid (h_block_max is d_block_max).
+  // Pending two-phase calls: order_pending, desc_pending, results_in_desc, distance_in_desc, compare_pending,
+  // scan_pending, adv_pending, export_epoch (void_pending_order, set_frame).
+  // Rules:  DROP BEFORE WRITE -- a call that writes d_orig, d_cand, d_rgb / pi0, lin[] or xyb[] drops every claim that
+  // depends on that buffer before its first copy or launch.  RE-ARM ONLY ON SUCCESS -- a claim is set again only as the
+  // last state change before `return GZ_OK`.  Dropping is always safe: it costs one full reconstruction or opsin pass.
   bool have_orig = false, have_cand = false, have_distmap = false;
   // lin[] holds the reconstruction of d_cand as it is now (4:4:4 frames; cfg.patch_reconstruct): set by the Compare
   // chain's full reconstruction, kept by the mutators that transform the block positions they change
-  // (gz_apply_candidate_steps, gz_apply_coeff_edits), dropped by everything else that writes d_cand or lin[]
+  // (gz_apply_candidate_steps, gz_apply_coeff_edits: PatchClaims), dropped by everything else that writes d_cand or lin[]
   bool lin_is_cand = false;
   // ... and xyb[] the opsin image of those planes (cfg.opsin_ahead): the Compare chain's second kernel enqueued AHEAD,
   // behind the bulk steps' patches, while the host takes its serial steps; their edits then cost the opsin tiles around
@@ -422,6 +431,17 @@ namespace {
 
 const int kNumPlanes = 9 + 9 + 3 + 3 + 3 + 2 + 2 + 10 + 2;   // pi0, pi1, lin, tmp, xyb, lf_raw, hfp, 10 singles, sup0[2]
 
+// A pending order build is void (gz_order_build_auto_end fails); descent: a descent pending behind it too
+// (gz_order_descend_end returns nothing); distance: and the distance of a Compare that was to arrive with it.
+void void_pending_order(gz_ctx* c, bool descent = false, bool distance = false) {
+  c->order_pending = false;
+  c->results_in_desc = false;
+  if (descent) c->desc_pending = false;
+  if (distance) c->distance_in_desc = false;
+}
+
+// A new frame layout: the candidate, the search and whatever was pending or kept belonged to the old one (a stale
+// gz_order_build_auto_end / gz_order_descend_end / gz_compare_end / gz_jpeg_scan_end must fail, not return its data).
 void set_frame(gz_ctx* c, int factor) {
   c->cfac = factor;
   c->cbw = (c->w + 8 * factor - 1) / (8 * factor);
@@ -431,13 +451,10 @@ void set_frame(gz_ctx* c, int factor) {
   c->coff[1] = c->nb;
   c->coff[2] = c->nb + c->nbc;
   c->nblk = c->nb + 2 * c->nbc;
+  c->have_cand = false;
+  c->lin_is_cand = c->xyb_is_cand = false;
   c->have_search = false;
-  // whatever was pending or kept belonged to the old frame: a stale gz_order_build_auto_end /
-  // gz_order_descend_end / gz_compare_end / gz_jpeg_scan_end must fail, not return its data
-  c->order_pending = false;
-  c->results_in_desc = false;
-  c->desc_pending = false;
-  c->distance_in_desc = false;
+  void_pending_order(c, true, true);
   c->compare_pending = false;
   c->scan_pending = false;
   c->have_distmap = false;

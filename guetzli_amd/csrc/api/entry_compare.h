@@ -8,30 +8,24 @@ extern "C" {
 int gz_encode_rgb(gz_ctx* c, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
-  if (c->cfac != 1) {   // back to 4:4:4: the candidate and the search belonged to the other frame
-    set_frame(c, 1);
-    c->have_cand = false;
-    c->lin_is_cand = c->xyb_is_cand = false;
-  }
+  if (c->cfac != 1) set_frame(c, 1);   // back to 4:4:4
+  c->have_orig = false;
   GZ_LAUNCH(k_encode_rgb, dim3(gz_div_up(c->nb, kBlocksPerWG)), dim3(256), c->stream, c->d_rgb,
             c->w, c->h, c->bw, c->nb, c->d_orig);
   KCHK(c);
-  c->have_orig = true;
   if (coeffs_out) {
     HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_orig, (size_t)3 * c->nb * 128,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  c->have_orig = true;
   return GZ_OK;
 }
 
 static int set_orig(gz_ctx* c, const int16_t* coeffs, int factor) {
   if (!c || !coeffs) return GZ_E_ARG;
-  if (c->cfac != factor) {   // the candidate and the search belonged to the other frame
-    set_frame(c, factor);
-    c->have_cand = false;
-    c->lin_is_cand = c->xyb_is_cand = false;
-  }
+  if (c->cfac != factor) set_frame(c, factor);
+  c->have_orig = false;
   HIPCHK(c, hipMemcpyAsync(c->d_orig, coeffs, (size_t)c->nblk * 128, hipMemcpyHostToDevice,
                            c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -63,6 +57,7 @@ int gz_quantize(gz_ctx* c, const int* q, int16_t* coeffs_out) {
   int ones[192];
   if (!q) { for (int i = 0; i < 192; ++i) ones[i] = 1; q = ones; }
   for (int i = 0; i < 192; ++i) if (q[i] <= 0) return GZ_E_ARG;
+  c->lin_is_cand = c->xyb_is_cand = false;
   HIPCHK(c, hipMemcpyAsync(c->d_q, q, sizeof(int) * 192, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // q may live on the caller's stack
   const size_t total = (size_t)c->nblk * 64;
@@ -70,23 +65,22 @@ int gz_quantize(gz_ctx* c, const int* q, int16_t* coeffs_out) {
   GZ_LAUNCH(k_quantize, dim3(blocks), dim3(256), c->stream, c->d_orig, c->d_cand, c->coff[1],
             c->coff[2], c->nblk, c->d_q);
   KCHK(c);
-  c->have_cand = true;
-  c->lin_is_cand = c->xyb_is_cand = false;
   if (coeffs_out) {
     HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_cand, total * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  c->have_cand = true;
   return GZ_OK;
 }
 
 int gz_set_coeffs(gz_ctx* c, const int16_t* coeffs) {
   DeviceScope ds_(c);
   if (!c || !coeffs) return GZ_E_ARG;
+  c->lin_is_cand = c->xyb_is_cand = false;
   HIPCHK(c, hipMemcpyAsync(c->d_cand, coeffs, (size_t)c->nblk * 128, hipMemcpyHostToDevice,
                            c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->have_cand = true;
-  c->lin_is_cand = c->xyb_is_cand = false;
   return GZ_OK;
 }
 
@@ -141,6 +135,7 @@ int gz_compare(gz_ctx* c, float* distance, float* distmap, float* block_max) {
   DeviceScope ds_(c);
   if (!c || !distance) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
+  c->have_distmap = c->h_block_max_valid = false;
   TRY(enqueue_compare(c, true, distmap != nullptr));   // (the map is stored only for a caller that takes it)
   void* res = nullptr;
   TRY(result_buffer(c, 4, &res));
@@ -148,7 +143,6 @@ int gz_compare(gz_ctx* c, float* distance, float* distmap, float* block_max) {
   if (distmap) TRY(download_plane(c, c->distmap, distmap));
   // the per-block maxima stay on the device (phase B's weights are computed there); they
   // come to the host only when asked for, here or by gz_block_weights
-  c->h_block_max_valid = false;
   if (block_max) {
     c->h_block_max.resize(c->nb);
     HIPCHK(c, hipMemcpyAsync(c->h_block_max.data(), c->d_block_max, sizeof(float) * c->nb,
@@ -170,8 +164,8 @@ int gz_compare_begin(gz_ctx* c) {
   if (!c) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
   HIPCHK(c, hipEventRecord(c->ev_candidate, c->stream));   // gz_jpeg_scan waits for this only
-  TRY(enqueue_compare(c, true));
   c->h_block_max_valid = false;
+  TRY(enqueue_compare(c, true));
   c->compare_pending = true;
   c->distance_in_desc = false;
   return GZ_OK;

@@ -252,9 +252,10 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, floa
 int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   DeviceScope ds_(c);
   if (!c || !rgb) return GZ_E_ARG;
+  c->lin_is_cand = c->xyb_is_cand = false;   // (lin[] takes the original)
+  c->have_block_mask = c->have_distmap = false;   // (StartBlockComparisons' mask and the map belong to the old one)
   HIPCHK(c, hipMemcpyAsync(c->d_rgb, rgb, (size_t)3 * c->w * c->h, hipMemcpyHostToDevice, c->stream));
   // pi0_ = SeparateFrequencies(OpsinDynamicsImage(LinearRgb(rgb)))
-  c->lin_is_cand = c->xyb_is_cand = false;   // (lin[] takes the original)
   dim3 grid(gz_div_up(c->w, 256), c->h);
   GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), c->stream, c->d_rgb, c->w, c->h, c->pitch,
             c->plane, c->d_srgb_lut, c->lin[0]);
@@ -267,8 +268,6 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
     TRY(stage_mask_sup(c, in0, c->sup0));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->have_block_mask = false;   // StartBlockComparisons' mask belongs to the old original
-  c->have_distmap = false;
   return GZ_OK;
 }
 

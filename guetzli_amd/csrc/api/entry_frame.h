@@ -108,8 +108,6 @@ int gz_set_frame(gz_ctx* c, int chroma_factor) {
   if (c->cfac == chroma_factor) return GZ_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   set_frame(c, chroma_factor);
-  c->have_cand = false;
-  c->lin_is_cand = c->xyb_is_cand = false;
   c->have_orig = false;   // the original coefficients on the device belonged to the other frame
   return GZ_OK;
 }
@@ -135,10 +133,10 @@ int gz_downsample(gz_ctx* c, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
   if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
+  c->have_orig = false;     // (d_orig's chroma is rewritten)
+  c->xyb_is_cand = false;   // scratch: planes of the candidate's evaluation (nothing of it is in flight here)
   const int w = c->w, h = c->h;
   const size_t n = (size_t)w * h;
-  // scratch: planes of the candidate's evaluation (nothing of it is in flight here)
-  c->xyb_is_cand = false;
   float* yuv[3] = {c->xyb[0], c->xyb[1], c->xyb[2]};
   float* tmp_s = c->tmp[0];
   float* tmp_b = c->tmp[1];
@@ -200,12 +198,10 @@ int gz_downsample(gz_ctx* c, int16_t* coeffs_out) {
     KCHK(c);
   }
   set_frame(c, 2);
-  c->have_cand = false;
-  c->lin_is_cand = c->xyb_is_cand = false;
-  c->have_distmap = false;
   if (coeffs_out)
     HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_orig, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_orig = true;
   return GZ_OK;
 }
 
@@ -213,10 +209,11 @@ int gz_downsample_planes(gz_ctx* c, const float* y, const float* u, const float*
   DeviceScope ds_(c);
   if (!c || !y || !u || !v) return GZ_E_ARG;
   if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample_planes needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
+  c->have_orig = false;
+  c->xyb_is_cand = false;   // (xyb[] as scratch)
   const int w = c->w, h = c->h;
   const size_t n = (size_t)w * h;
   const float* src[3] = {y, u, v};
-  c->xyb_is_cand = false;   // (xyb[] as scratch)
   for (int i = 0; i < 3; ++i)
     HIPCHK(c, hipMemcpyAsync(c->xyb[i], src[i], n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   // output_image.cc:314-316: every component from its plane, luma included (factor 1), the
@@ -232,12 +229,10 @@ int gz_downsample_planes(gz_ctx* c, const float* y, const float* u, const float*
     KCHK(c);
   }
   set_frame(c, 2);
-  c->have_cand = false;
-  c->lin_is_cand = c->xyb_is_cand = false;
-  c->have_distmap = false;
   if (coeffs_out)
     HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_orig, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_orig = true;
   return GZ_OK;
 }
 

@@ -108,8 +108,7 @@ int gz_order_build(gz_ctx* c, int direction, const int32_t* next_cand,
       (direction != 1 && direction != -1) || (count_below && !below))
     return GZ_E_ARG;
   if (!c->have_search) { c->err = "gz_block_zeroing_orders must precede gz_order_build"; return GZ_E_STATE; }
-  c->order_pending = false;
-  c->results_in_desc = false;
+  void_pending_order(c);
   const int nb = c->sg_n;
   TRY(ensure_order_block_arrays(c));
   c->adv_pending = false;   // (the caller's own max_block_error and weights replace the device's)
@@ -195,9 +194,7 @@ int gz_order_build_auto(gz_ctx* c, int direction, int max_block_dist, double tar
   if (!c || !next_cand || !total || !blocks_to_change || (direction != 1 && direction != -1) ||
       max_block_dist < 0 || (count_below && !below))
     return GZ_E_ARG;
-  c->order_pending = false;
-  c->results_in_desc = false;
-  c->desc_pending = false;
+  void_pending_order(c, true);
   TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
   return order_build_device(c, direction, count_below, limit, total, blocks_to_change, below, true);
 }
@@ -206,9 +203,7 @@ int gz_order_build_auto_begin(gz_ctx* c, int direction, int max_block_dist, doub
                               int use_distmap, const int32_t* next_cand, int count_below, float limit) {
   DeviceScope ds_(c);
   if (!c || !next_cand || (direction != 1 && direction != -1) || max_block_dist < 0) return GZ_E_ARG;
-  c->order_pending = false;
-  c->results_in_desc = false;
-  c->desc_pending = false;
+  void_pending_order(c, true);
   TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
   TRY(order_build_enqueue(c, direction, count_below, limit, true));
   if (!c->h_order_pending) HIPCHK(c, pool_host_malloc((void**)&c->h_order_pending, sizeof(*c->h_order_pending)));
@@ -253,11 +248,7 @@ int gz_order_build_auto_descend_begin(gz_ctx* c, int direction, int max_block_di
   DeviceScope ds_(c);
   if (!c || !next_cand || (direction != 1 && direction != -1) || max_block_dist < 0 || max_levels < 0)
     return GZ_E_ARG;
-  c->order_pending = false;
-  c->results_in_desc = false;
-  c->desc_pending = false;
-  c->results_in_desc = false;
-  c->distance_in_desc = false;
+  void_pending_order(c, true, true);
   TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
   TRY(order_build_enqueue(c, direction, count_below, limit, true));
   TRY(descend_enqueue(c, 1, 0, 0, per_block, threshold, max_levels, std::max<size_t>(c->search_total, 1), true));
@@ -285,15 +276,20 @@ int gz_order_advance(gz_ctx* c, float val_threshold, int direction) {
 }
 
 // Does the call that changes n block positions of the candidate keep its linear planes current (transforming those
-// positions again), or leave them to the next Compare's full reconstruction?  (Decides, and drops the planes' claim.)
+// positions again), or leave them to the next Compare's full reconstruction?
 // (Below half a megapixel a full reconstruction costs what a patch launch costs, and an iteration is made of launches:
 // such images keep it, unless the tests' checking mode asks for patches at every size.)
-static bool patch_wanted(gz_ctx* c, int n) {
-  const bool patch = c->cfg.patch_reconstruct != 0 && c->lin_is_cand && c->cfac == 1 && (long)n * 2 <= (long)c->nb &&
-                     (c->nb >= 8192 || c->cfg.patch_reconstruct == 2);
-  if (!patch) c->lin_is_cand = c->xyb_is_cand = false;
-  return patch;
+static bool patch_wanted(const gz_ctx* c, int n) {
+  return c->cfg.patch_reconstruct != 0 && c->lin_is_cand && c->cfac == 1 && (long)n * 2 <= (long)c->nb &&
+         (c->nb >= 8192 || c->cfg.patch_reconstruct == 2);
 }
+// The claims lin_is_cand / xyb_is_cand through a call that may patch them: dropped on entry, re-armed by commit() as
+// the call's last state change before it returns GZ_OK -- every other return leaves them dropped.
+struct PatchClaims {
+  gz_ctx* c;
+  explicit PatchClaims(gz_ctx* c_) : c(c_) { c->lin_is_cand = c->xyb_is_cand = false; }
+  void commit(bool lin, bool xyb) { c->lin_is_cand = lin; c->xyb_is_cand = xyb; }
+};
 static PatchPlanes patch_planes(const gz_ctx* c, bool on) {
   PatchPlanes pp;
   pp.bw = c->bw; pp.w = c->w; pp.h = c->h; pp.pitch = c->pitch;
@@ -319,6 +315,10 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
     for (int i = 0; i < n; ++i) bad |= (unsigned)((unsigned)blocks[i] >= sg_n) | (unsigned)((unsigned)counts[i] > 192u);
     if (bad) return GZ_E_ARG;
   }
+  // the touched block positions of the candidate's linear planes are transformed again behind the statistics
+  // (chain.h, enqueue_compare), while they are a minority: beyond that the next Compare reconstructs the image
+  const bool patch = c->have_jq && patch_wanted(c, n);
+  PatchClaims claims(c);
   if ((size_t)2 * n > c->edit_cap) {   // the edit buffers double as (blocks, counts) staging
     HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
     (void)pool_free(c->d_edit_pos); (void)pool_free(c->d_edit_val);
@@ -349,9 +349,6 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
     // (persistent workgroups: four per CU's worth at most, each wavefront taking several blocks)
     // (the kernel reads the staging buffer itself -- page-locked and mapped: a copy command in front of
     // it costs more in hand-overs between commands than the 8 bytes per block cost over the bus)
-    // the touched block positions of the candidate's linear planes are transformed again behind the statistics
-    // (chain.h, enqueue_compare), while they are a minority: beyond that the next Compare reconstructs the image
-    const bool patch = patch_wanted(c, n);
     GZ_LAUNCH(k_apply_steps_hist, dim3(std::min(gz_div_up(n, 4), kStepHistGrid)), dim3(256), c->stream, (const int*)h,
               (const int*)h + n, n, direction, (const int*)c->d_next_cand,
               (const unsigned char*)c->d_out_idx, (const short*)c->d_orig, (short*)c->d_cand,
@@ -364,6 +361,7 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
     KCHK(c);
     c->have_step_delta = true;
     c->step_delta_event = false;
+    bool ahead = false;
     if (patch) {
       // gz_steps_histogram_delta waits for the sums, not for the stream: the patches run while the host reads them
       if (!c->ev_steps) HIPCHK(c, pool_event_create(&c->ev_steps));
@@ -375,15 +373,12 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
       // ... and, for a context that has the device to itself, the next Compare's opsin blur of the planes as they
       // are now: 100 us (4K) of the chain's critical path that run while the host takes its serial steps, whose
       // edits then cost the tiles around them (gz_apply_coeff_edits).  Not in a batch: the other images use the time.
-      c->xyb_is_cand = false;
-      if (c->cfg.opsin_ahead != 0 && !single_stream_wanted(c)) {
-        TRY(stage_opsin(c));
-        c->xyb_is_cand = true;
-      }
+      ahead = c->cfg.opsin_ahead != 0 && !single_stream_wanted(c);
+      if (ahead) TRY(stage_opsin(c));
     }
+    claims.commit(patch, ahead);
     return GZ_OK;
   }
-  c->lin_is_cand = c->xyb_is_cand = false;
   HIPCHK(c, hipMemcpyAsync(d_blocks, h, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream));
   TRY(stage_sent(c, &c->stage_main, c->stream));
   GZ_LAUNCH(k_apply_steps, dim3(gz_div_up(n, 4)), dim3(256), c->stream, (const int*)d_blocks,
@@ -416,6 +411,8 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
   const int limit = c->nblk * 64;
   for (int i = 0; i < n; ++i)
     if (pos[i] < 0 || pos[i] >= limit) return GZ_E_ARG;
+  const bool patch = patch_wanted(c, n), ahead = patch && c->xyb_is_cand;
+  PatchClaims claims(c);
   // A few hundred edits per iteration, between the host's last step and the chain's first kernel:
   // the kernel reads them straight from the page-locked staging buffer (two copies of a few KB on
   // the stream cost more than the bytes' trip over the bus).  Bulk edits go through device memory.
@@ -444,10 +441,10 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
   }
   GZ_LAUNCH(k_apply_coeff_edits, dim3(gz_div_up(n, 256)), dim3(256), c->stream, k_pos, k_val, n, c->d_cand);
   int rc_tiles = GZ_OK;   // (reported behind stage_sent: no path returns with a kernel still reading the staging buffer)
-  if (patch_wanted(c, n)) {   // the edited block positions' pixels, behind the edits (one wavefront per edit)
+  if (patch) {   // the edited block positions' pixels, behind the edits (one wavefront per edit)
     GZ_LAUNCH((k_reconstruct_listed<true>), dim3(gz_div_up(n, kBlocksPerWG)), dim3(256), c->stream, k_pos, n,
               (const int16_t*)c->d_cand, c->nb, patch_planes(c, true));
-    if (c->xyb_is_cand) {
+    if (ahead) {
       // the opsin image enqueued ahead (gz_apply_candidate_steps): a pixel's value depends on the linear planes
       // within 2 pixels of it (radius-2 blur), so the tiles that meet an edited block grown by 2 are computed again
       // -- or the image, when the edits are many (the last iterations of a search)
@@ -474,14 +471,14 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
   TRY(stage_sent(c, &c->stage_edits, c->stream));   // (the staging buffer is free again behind the kernels)
   KCHK(c);
   TRY(rc_tiles);
+  claims.commit(patch, ahead);
   return GZ_OK;   // the caller's buffers were copied to the staging buffer: no wait
 }
 
 int gz_order_upload(gz_ctx* c, const void* entries, uint64_t n) {
   DeviceScope ds_(c);
   if (!c || (n > 0 && !entries)) return GZ_E_ARG;
-  c->order_pending = false;
-  c->results_in_desc = false;
+  void_pending_order(c);
   TRY(ensure_order_capacity(c, (size_t)n));
   if (n > 0)
     HIPCHK(c, hipMemcpyAsync(c->d_order, entries, sizeof(OrderEntry) * n, hipMemcpyHostToDevice, c->stream));

@@ -118,7 +118,17 @@ inline void fiber_init(int t) {
   makecontext(&s.fibers[t], (void (*)())fiber_entry, 0);
 #endif
 }
+// Launch fault injection (tests/test_hip_failures.py), in the style of gz_emu_fail_alloc below: every launch is
+// counted; gz_emu_fail_launch(n) makes the (n + 1)-th launch from now on not run its body (once), and the next
+// hipGetLastError() then returns a launch failure (once).  (Launches run on one thread: no lock.)
+struct LaunchBook {
+  long calls = 0, fail_at = -1;
+  bool failed = false;
+};
+inline LaunchBook& launch_book() { static LaunchBook b; return b; }
 inline void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
+  LaunchBook& lb = launch_book();
+  if (lb.calls++ == lb.fail_at) { lb.fail_at = -1; lb.failed = true; return; }
   State& s = st();
   const int nt = (int)(block.x * block.y * block.z);
   if ((int)s.fibers.size() < nt) {
@@ -268,11 +278,16 @@ typedef int hipError_t;
 typedef void* hipStream_t;
 struct hipEmuEvent { std::chrono::steady_clock::time_point t; };
 typedef hipEmuEvent* hipEvent_t;
-enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorNoDevice = 100 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorNoDevice = 100, hipErrorLaunchFailure = 719 };
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice,
                      hipMemcpyHostToHost, hipMemcpyDefault };
 inline const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : e ? "emu error" : "success"; }
-inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipGetLastError() {
+  hipemu::LaunchBook& lb = hipemu::launch_book();
+  if (!lb.failed) return hipSuccess;
+  lb.failed = false;
+  return hipErrorLaunchFailure;
+}
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
@@ -304,6 +319,11 @@ extern "C" __attribute__((used, visibility("default"))) inline long gz_emu_alloc
   std::lock_guard<std::mutex> lk(b.mu);
   return b.calls;
 }
+extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_fail_launch(long n) {
+  hipemu::LaunchBook& b = hipemu::launch_book();
+  b.fail_at = n < 0 ? -1 : b.calls + n;
+}
+extern "C" __attribute__((used, visibility("default"))) inline long gz_emu_launch_calls(void) { return hipemu::launch_book().calls; }
 extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_live(long* device_bytes, long* host_bytes, long* blocks,
                                                                                 long* events) {
   hipemu::AllocBook& b = hipemu::alloc_book();

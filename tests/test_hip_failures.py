@@ -1,12 +1,18 @@
-"""Out-of-memory paths of the C ABI and of the host driver above it (VERDICT r5 "HIP-failure paths are untested").
+"""Out-of-memory and launch-failure paths of the C ABI and of the host driver above it (VERDICT r5 "HIP-failure paths
+are untested").
 
 The CPU emulation's hipMalloc / hipHostMalloc (tests/emu/hip_emu.h) count every allocation, can be told to fail the
-n-th one from now on with hipErrorOutOfMemory, and list what is still allocated.  Checked here:
+n-th one from now on with hipErrorOutOfMemory, and list what is still allocated.  Its kernel launches are counted the
+same way, and the n-th one from now on can be made to fail.  Checked here:
   * gz_create with EVERY one of its allocations failing in turn: NULL + GZ_E_NOMEM, nothing left allocated (device
     blocks, page-locked blocks, events), and the next gz_create succeeds;
   * a whole encode through the host driver with allocations failing at sampled points of its life (context creation,
     block search, phase B's order, the entropy coder's buffers, staging): the encode fails with an error -- no crash,
-    nothing left allocated -- and the encode after it produces the reference's bytes.
+    nothing left allocated -- and the encode after it produces the reference's bytes;
+  * the calls that write the candidate or the original with EVERY one of their launches failing in turn: the call
+    fails, and a caller that goes on gets a Compare that does not trust planes the failed call may have left stale
+    (the context's claims, context.h), with the distance of a fresh context given the same coefficients -- or, after a
+    failed downsample, a refusal to quantize a half-written original.
 (The emulation build allocates directly instead of through the product's pools, so "still allocated" is exact.)
 CPU only."""
 import ctypes as C
@@ -18,7 +24,8 @@ import numpy as np
 import pytest
 
 import images
-from checkers import ref
+from checkers import assert_bits_equal, ref
+from guetzli_amd.capi import GuetzliAmdError, Library
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
 import build_emu  # noqa: E402
@@ -35,6 +42,8 @@ def emu():
     lib.gz_emu_fail_alloc.argtypes = [C.c_long]
     lib.gz_emu_alloc_calls.restype = C.c_long
     lib.gz_emu_live.argtypes = [C.POINTER(C.c_long)] * 4
+    lib.gz_emu_fail_launch.argtypes = [C.c_long]
+    lib.gz_emu_launch_calls.restype = C.c_long
     return lib
 
 
@@ -101,3 +110,176 @@ def test_an_encode_survives_allocations_failing_anywhere(emu):
     assert failed >= len(points) // 2, (failed, len(points))
     jpg, _ = host.process(rgb, quality=90.0)
     assert hashlib.sha256(jpg).hexdigest() == exp
+
+
+# ---- launch failures: the context's claims on error paths (patch_reconstruct = 2: a Compare that trusts the linear
+# planes checks them against a full reconstruction itself, so a stale claim is GZ_E_STATE there, not a quiet error)
+TARGET = 0.971769
+Q = np.full((3, 64), 3, np.int32)
+
+
+@pytest.fixture(scope="module")
+def L(emu):
+    return Library(build_emu.build())
+
+
+def compare_patched(L, ctx):
+    """ctx.compare() and whether it relied on the patched planes / on the opsin image kept ahead."""
+    before = L.compare_counters(all=True)
+    got = ctx.compare()
+    d = [a - b for a, b in zip(L.compare_counters(all=True), before)]
+    return got, d[0] > 0, d[3] > 0
+
+
+def assert_as_fresh(L, ctx, got, rgb):
+    """got (ctx's Compare) bit for bit that of a fresh context given ctx's coefficients."""
+    with L.context(rgb, TARGET) as fresh:
+        fresh.set_coeffs(ctx.get_coeffs())
+        exp = fresh.compare()
+    for g, e, what in zip(got, exp, ("distance", "distance map", "block maxima")):
+        assert_bits_equal(np.asarray(g, np.float32), np.asarray(e, np.float32), what)
+
+
+def sweep_launches(emu, setup, call, after):
+    """setup() -> state; call(state) once cleanly to count its launches, then for every launch n of it on a fresh
+    state: launch n fails, the call fails with GZ_E_HIP, after(state, n) checks how the context goes on."""
+    st = setup()
+    before = emu.gz_emu_launch_calls()
+    call(st)
+    n_launches = emu.gz_emu_launch_calls() - before
+    assert n_launches >= 1
+    for n in range(n_launches):
+        st = setup()
+        emu.gz_emu_fail_launch(n)
+        try:
+            with pytest.raises(GuetzliAmdError, match="GZ_E_HIP"):
+                call(st)
+        finally:
+            emu.gz_emu_fail_launch(-1)
+        after(st, n)
+    return n_launches
+
+
+def patch_ready(L, rgb, search=True, **cfg):
+    """A context in the search loop's steady state: the Compare's full reconstruction made lin[] the candidate's."""
+    ctx = L.context(rgb, TARGET)
+    ctx.set_config(patch_reconstruct=2, **cfg)
+    ctx.encode_rgb(download=False)
+    ctx.quantize(Q, download=False)
+    cnt = None
+    if search:
+        cnt = np.diff(ctx.block_zeroing_orders()[0])
+        ctx.order_reset()
+    ctx.compare()
+    if search:
+        ctx.order_build_auto(1, 1, 1.0, True, np.zeros(ctx.nb, np.int32))
+        ctx.jpeg_histograms(Q)
+    return ctx, cnt
+
+
+def steps_of(ctx, cnt):
+    """Steps on fewer than half of the block positions (the patch path)."""
+    sel = np.flatnonzero(cnt > 0)[: ctx.nb // 2 - 1].astype(np.int32)
+    return sel, np.minimum(cnt[sel], 2).astype(np.int32)
+
+
+def edits_of(ctx, n, seed):
+    rng = np.random.default_rng(seed)
+    pos = rng.choice(3 * ctx.nb * 64, size=n, replace=False).astype(np.int32)
+    return pos, rng.integers(-40, 40, n).astype(np.int16)
+
+
+def goes_on_unpatched(L, rgb):
+    def after(ctx, n):
+        got, patched, ahead = compare_patched(L, ctx)
+        assert not patched and not ahead, f"launch {n} failed, and the next Compare trusted the patched planes"
+        assert_as_fresh(L, ctx, got, rgb)
+        ctx.close()
+    return after
+
+
+@pytest.mark.parametrize("ahead", [True, False])
+def test_candidate_steps_launch_failures_drop_the_claims(emu, L, ahead):
+    rgb = images.crop(40, 32, 100, 60)
+    cfg = dict(single_stream=0, opsin_ahead=1) if ahead else dict(opsin_ahead=0)
+
+    def call(st):
+        ctx, cnt = st
+        ctx.apply_candidate_steps(1, *steps_of(ctx, cnt))
+    ctx, cnt = patch_ready(L, rgb, **cfg)
+    call((ctx, cnt))
+    _, patched, kept = compare_patched(L, ctx)
+    assert patched and kept == ahead, "the clean call did not take the patch path"
+    ctx.close()
+    after = goes_on_unpatched(L, rgb)
+    n = sweep_launches(emu, lambda: patch_ready(L, rgb, **cfg), call, lambda st, n: after(st[0], n))
+    assert n >= (4 if ahead else 3), n
+
+
+@pytest.mark.parametrize("ahead", [True, False])
+def test_coeff_edits_launch_failures_drop_the_claims(emu, L, ahead):
+    """The direct path (4096 edits or fewer), behind bulk steps that kept the opsin image ahead, or not."""
+    rgb = images.crop(40, 32, 100, 60)
+    cfg = dict(single_stream=0, opsin_ahead=1) if ahead else dict(opsin_ahead=0)
+
+    def setup():
+        ctx, cnt = patch_ready(L, rgb, **cfg)
+        ctx.apply_candidate_steps(1, *steps_of(ctx, cnt))
+        return ctx
+
+    def call(ctx):
+        ctx.apply_coeff_edits(*edits_of(ctx, 6, 7))
+    ctx = setup()
+    call(ctx)
+    _, patched, kept = compare_patched(L, ctx)
+    assert patched and kept == ahead, "the clean call did not take the patch path"
+    ctx.close()
+    n = sweep_launches(emu, setup, call, goes_on_unpatched(L, rgb))
+    assert n >= (3 if ahead else 2), n
+
+
+def test_bulk_coeff_edits_launch_failures_drop_the_claims(emu, L):
+    """The bulk path (more than 4096 edits, through device memory) on an image with twice as many blocks."""
+    rgb = images.tiled(1024, 520)   # 8320 blocks
+
+    def setup():
+        return patch_ready(L, rgb, search=False)[0]
+
+    def call(ctx):
+        ctx.apply_coeff_edits(*edits_of(ctx, 4100, 11))
+    ctx = setup()
+    call(ctx)
+    assert compare_patched(L, ctx)[1], "the clean call did not take the patch path"
+    ctx.close()
+    assert sweep_launches(emu, setup, call, goes_on_unpatched(L, rgb)) >= 2
+
+
+def test_quantize_launch_failure_drops_the_claims(emu, L):
+    rgb = images.crop(40, 32, 100, 60)
+    sweep_launches(emu, lambda: patch_ready(L, rgb, search=False)[0], lambda ctx: ctx.quantize(Q + 2),
+                   goes_on_unpatched(L, rgb))
+
+
+@pytest.mark.parametrize("planes", [False, True])
+def test_downsample_launch_failures_leave_no_original(emu, L, planes):
+    """A failed gz_downsample* leaves the 4:4:4 frame with a half-rewritten original: quantizing it is refused (the
+    candidate and its planes are untouched: the next Compare may trust them -- and checks them itself)."""
+    rgb = images.crop(40, 32, 100, 60)
+    yuv = [np.ascontiguousarray(rgb[..., i], np.float32) for i in range(3)]
+
+    def call(ctx):
+        if planes:
+            ctx.downsample_planes(*yuv, download=False)
+        else:
+            ctx.downsample(download=False)
+
+    def after(ctx, n):
+        got, _, _ = compare_patched(L, ctx)
+        assert_as_fresh(L, ctx, got, rgb)
+        co = ctx.get_coeffs()
+        with pytest.raises(GuetzliAmdError, match="GZ_E_STATE"):
+            ctx.quantize(Q)
+        assert np.array_equal(ctx.get_coeffs(), co), f"launch {n} failed, and a half-written original was quantized"
+        assert ctx.frame_layout()[0] == 1
+        ctx.close()
+    sweep_launches(emu, lambda: patch_ready(L, rgb, search=False)[0], call, after)
