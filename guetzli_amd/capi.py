@@ -110,6 +110,8 @@ SIGNATURES = {
     "gz_probe_idct_blocks": (_I, [_I, _P, _I, _P]),
     "gz_probe_fdct_blocks": (_I, [_I, _P, _I]),
     "gz_probe_arith": (_I, [_I, _I, _P, _P, _P, _P, _I]),
+    "gz_probe_math": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "gz_probe_div2_sweep": (_I, [_I, _P, _I, C.c_uint, C.c_uint, _P, _P, C.c_size_t]),
     "gz_dct_double_blocks": (_I, [_I, _P, _I, _I]),
     "gz_component_to_float_pixels": (_I, [_I, _P, _I, _I, _P]),
     "gz_component_set_downsampled": (_I, [_I, _P, _I, _I, _I, _I, _P]),
@@ -222,6 +224,30 @@ class Library:
         self.check(self.lib.gz_probe_arith(device, op, _ptr(a), _ptr(b), _ptr(c), _ptr(out),
                                            a.size))
         return out
+
+    def probe_math(self, op, a, b=None, c=None, p=(), outs=1, device=0):
+        """gz_probe_math: op = GZ_MATH_* of include/guetzli_amd.h; float arrays (doubles for
+        GZ_MATH_INTERP_LUT512 = 15, int32 for GZ_MATH_QUANT_DIV = 16); returns [outs][n]."""
+        dt = np.float64 if op == 15 else np.int32 if op == 16 else np.float32
+        a = np.ascontiguousarray(a, dt)
+        b = None if b is None else np.ascontiguousarray(b, dt)
+        c = None if c is None else np.ascontiguousarray(c, dt)
+        n = a.size // 3 if op == 4 else a.size
+        pp = np.ascontiguousarray(p, np.float64)
+        out = np.zeros((outs, n), dt)
+        self.check(self.lib.gz_probe_math(device, op, n, _ptr(a), _ptr(b), _ptr(c),
+                                          _ptr(pp) if pp.size else None, pp.size, _ptr(out)))
+        return out
+
+    def div2_sweep(self, numerators, stride=1, sample_every=1 << 20, device=0):
+        """gz_probe_div2_sweep: (mismatches, sampled quotients [samples][len(numerators)])."""
+        num = np.ascontiguousarray(numerators, np.float32)
+        count = -(-(80 << 23) // stride)
+        sample = np.zeros((-(-count // sample_every), num.size), np.float32)
+        bad = C.c_uint64(0)
+        self.check(self.lib.gz_probe_div2_sweep(device, _ptr(num), num.size, stride, sample_every,
+                                                C.byref(bad), _ptr(sample), sample.size))
+        return bad.value, sample
 
     def context(self, rgb, target, device=0):
         return Context(self, rgb, target, device)
@@ -608,6 +634,10 @@ class Context:
         return out
 
     def probe_diffmap(self, rgb0, rgb1):
+        """The distance map and score of two linear images.  rgb0 MUST be the linear image of the
+        context's current original (gz_create's, or the last set_rgb's): the mask branch reads the
+        half precomputed from that original, and with another rgb0 the map is silently wrong.  Call
+        set_rgb(original) first to probe another pair."""
         a = np.ascontiguousarray(rgb0, np.float32)
         b = np.ascontiguousarray(rgb1, np.float32)
         d = np.zeros((self.h, self.w), np.float32)

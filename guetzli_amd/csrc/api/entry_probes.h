@@ -197,6 +197,103 @@ int gz_probe_arith(int device, int op, const void* a, const void* b, const void*
   return rc;
 }
 
+int gz_probe_math(int device, int op, int n, const void* a, const void* b, const void* c,
+                  const double* p, int np, void* out) {
+  if (!a || !out || n <= 0 || op < 0 || op >= GZ_MATH_OP_COUNT || np < 0 || (np > 0 && !p)) return GZ_E_ARG;
+  // per op: number of input arrays, elements per input (in units of n), constants, outputs per element
+  static const struct { int nin, per_in, np, outs; } kOps[GZ_MATH_OP_COUNT] = {
+      {3, 1, 0, 2},    // GZ_MATH_DIV2_SHARED
+      {2, 1, 4, 1},    // GZ_MATH_MALTA_DIFF
+      {2, 1, 4, 1},    // GZ_MATH_MALTA_DIFF_PLAIN
+      {1, 1, 0, 1},    // GZ_MATH_GAMMA_POLY
+      {2, 3, 0, 3},    // GZ_MATH_OPSIN_PIXEL
+      {1, 1, 1, 1},    // GZ_MATH_MAXIMUM_CLAMP
+      {1, 1, 1, 1},    // GZ_MATH_REMOVE_RANGE
+      {1, 1, 1, 1},    // GZ_MATH_AMPLIFY_RANGE
+      {2, 1, 0, 1},    // GZ_MATH_SUPPRESS_X_BY_Y
+      {2, 1, 2, 1},    // GZ_MATH_SUPPRESS_BRIGHT
+      {3, 1, 0, 3},    // GZ_MATH_LF_TO_VALS
+      {3, 1, 1, 1},    // GZ_MATH_L2DIFF
+      {3, 1, 2, 1},    // GZ_MATH_L2DIFF_ASYM
+      {2, 1, 0, 1},    // GZ_MATH_SAME_NOISE_PRE
+      {2, 1, 0, 1},    // GZ_MATH_DIFF_FROM_SUPS
+      {1, 1, 512, 1},  // GZ_MATH_INTERP_LUT512 (a, out: double)
+      {2, 1, 0, 1},    // GZ_MATH_QUANT_DIV (a, b, out: int32)
+  };
+  const auto& o = kOps[op];
+  if (np != o.np || (o.nin >= 2 && !b) || (o.nin >= 3 && !c)) return GZ_E_ARG;
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  const size_t es = op == GZ_MATH_INTERP_LUT512 ? 8 : 4;
+  const size_t in_bytes = es * (size_t)o.per_in * n, out_bytes = es * (size_t)o.outs * n;
+  DevBuf da, db, dc, dp, dout;
+  if (!da.alloc(in_bytes) || !db.alloc(in_bytes) || !dc.alloc(in_bytes) || !dp.alloc(sizeof(double) * 512) ||
+      !dout.alloc(out_bytes))
+    return GZ_E_NOMEM;
+  const void* src[3] = {a, b, c};
+  void* dst[3] = {da.p, db.p, dc.p};
+  for (int k = 0; k < o.nin; ++k)
+    if (hipMemcpy(dst[k], src[k], in_bytes, hipMemcpyHostToDevice) != hipSuccess) return GZ_E_HIP;
+  if (op == GZ_MATH_INTERP_LUT512 && hipMemcpy(dp.p, p, sizeof(double) * 512, hipMemcpyHostToDevice) != hipSuccess)
+    return GZ_E_HIP;
+  const dim3 grid(gz_div_up(n, 256));
+  if (op == GZ_MATH_QUANT_DIV) {
+    const int* pa = (const int*)da.p; const int* pq = (const int*)db.p; int* po = (int*)dout.p;
+    GZ_LAUNCH(k_probe_quant_div, grid, dim3(256), (hipStream_t)0, pa, pq, po, n);
+  } else {
+    ProbeMathArgs g;
+    memset(&g, 0, sizeof(g));
+    g.op = op; g.n = n;
+    g.a = da.p; g.b = db.p; g.c = dc.p;
+    g.table = (const double*)dp.p;
+    g.out = dout.p;
+    if (op == GZ_MATH_MALTA_DIFF || op == GZ_MATH_MALTA_DIFF_PLAIN) {
+      g.nm.norm2_0gt1 = (float)p[0]; g.nm.norm2_0lt1 = (float)p[1]; g.nm.norm1f = (float)p[2];
+      g.nm.fast_div = p[3] != 0.0 ? 1 : 0;
+    } else if (op != GZ_MATH_INTERP_LUT512) {
+      if (np > 0) g.p0 = p[0];
+      if (np > 1) g.p1 = p[1];
+    }
+    GZ_LAUNCH(k_probe_math, grid, dim3(256), (hipStream_t)0, g);
+  }
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return GZ_E_HIP;
+  if (hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return GZ_E_HIP;
+  return GZ_OK;
+}
+
+int gz_probe_div2_sweep(int device, const float* numerators, int nnum, unsigned stride, unsigned sample_every,
+                        uint64_t* mismatches, float* sample, size_t sample_cap) {
+  if (!numerators || !mismatches || nnum < 2 || nnum > 12 || (nnum & 1) || stride == 0 || sample_every == 0)
+    return GZ_E_ARG;
+  const unsigned long long total = 80ull << 23;                        // float denominators in [2^-40, 2^40)
+  const unsigned long long count = (total + stride - 1) / stride;     // checked ones
+  const unsigned long long nsample = (count + sample_every - 1) / sample_every;
+  if (sample && sample_cap < nsample * (size_t)nnum) return GZ_E_ARG;
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  DevBuf dbad, dsample;
+  if (!dbad.alloc(8) || (sample && !dsample.alloc(sizeof(float) * nsample * nnum))) return GZ_E_NOMEM;
+  if (hipMemset(dbad.p, 0, 8) != hipSuccess) return GZ_E_HIP;
+  Div2Numerators num;
+  memset(&num, 0, sizeof(num));
+  for (int k = 0; k < nnum; ++k) num.v[k] = numerators[k];
+  unsigned long long* pbad = (unsigned long long*)dbad.p;
+  float* psample = sample ? (float*)dsample.p : nullptr;
+  GZ_LAUNCH(k_probe_div2_sweep, dim3((unsigned)((count + 255) / 256)), dim3(256), (hipStream_t)0, num, nnum, stride,
+            count, sample_every, pbad, psample);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return GZ_E_HIP;
+  unsigned long long bad = 0;
+  if (hipMemcpy(&bad, dbad.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return GZ_E_HIP;
+  if (sample && hipMemcpy(sample, dsample.p, sizeof(float) * nsample * nnum, hipMemcpyDeviceToHost) != hipSuccess)
+    return GZ_E_HIP;
+  *mismatches = bad;
+  return GZ_OK;
+}
+
+#ifdef GZ_EMU
+// Emulation build only (test hook, in the style of gz_emu_fail_launch): the emulated reciprocal of
+// div2_shared off by u = -1, 0, +1 ulp -- v_rcp_f32 is accurate to 1 ulp, not correctly rounded.
+__attribute__((used, visibility("default"))) void gz_emu_set_rcp_ulps(int u) { gz::gz_emu_rcp_ulps() = u; }
+#endif
+
 #endif  // GZ_NO_PROBES
 
 }  // extern "C"

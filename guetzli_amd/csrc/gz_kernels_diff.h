@@ -401,4 +401,87 @@ __global__ void k_probe_arith(int op, const void* a, const void* b, const void* 
   }
 }
 
+// The per-pixel functions of gz_math.h evaluated element-wise (gz_probe_math): the forms that exist
+// only on the device -- the shared reciprocal of div2_shared on v_rcp_f32, malta_diff's
+// wavefront-uniform branch (256 consecutive elements are four wavefronts: the caller mixes rare-path
+// and ordinary elements inside them), the constant division of gamma_poly_f -- and every value branch,
+// on operands the image chain never produces.  op numbers: GZ_MATH_* of include/guetzli_amd.h.
+struct ProbeMathArgs {
+  int op, n;
+  const void *a, *b, *c;
+  const double* table;   // interp_lut512
+  MaltaNorm nm;          // malta_diff
+  double p0, p1;         // the op's constants
+  void* out;
+};
+__global__ __launch_bounds__(256) void k_probe_math(ProbeMathArgs g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = g.n;
+  // (whole wavefronts go through malta_diff: its ballot wants every lane present; lanes past the
+  // end evaluate element n - 1 again and store nothing)
+  const int j = i < n ? i : n - 1;
+  const float* a = (const float*)g.a;
+  const float* b = (const float*)g.b;
+  const float* c = (const float*)g.c;
+  float* out = (float*)g.out;
+  float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+  int outs = 1;
+  switch (g.op) {
+    case 0: div2_shared(a[j], b[j], c[j], &r0, &r1); outs = 2; break;
+    case 1: r0 = malta_diff(a[j], b[j], g.nm); break;
+    case 2: r0 = malta_diff_plain(a[j], b[j], g.nm); break;
+    case 3: r0 = gamma_poly_f((double)a[j]); break;
+    case 4:
+      opsin_pixel(a[j], a[n + j], a[2 * n + j], b[j], b[n + j], b[2 * n + j], &r0, &r1, &r2);
+      outs = 3;
+      break;
+    case 5: r0 = maximum_clamp(a[j], (float)g.p0); break;
+    case 6: r0 = remove_range((float)g.p0, a[j]); break;
+    case 7: r0 = amplify_range((float)g.p0, a[j]); break;
+    case 8: r0 = suppress_x_by_y(a[j], b[j]); break;
+    case 9: r0 = suppress_bright(a[j], b[j], (float)g.p0, (float)g.p1); break;
+    case 10: lf_to_vals(a[j], b[j], c[j], &r0, &r1, &r2); outs = 3; break;
+    case 11: r0 = l2diff_acc(a[j], b[j], c[j], g.p0); break;
+    case 12: r0 = l2diff_asym_acc(a[j], b[j], c[j], g.p0, g.p1); break;
+    case 13: r0 = same_noise_pre(a[j], b[j]); break;
+    case 14: r0 = diff_from_sups(a[j], b[j]); break;
+    case 15:
+      if (i < n) ((double*)g.out)[i] = interp_lut512(g.table, ((const double*)g.a)[i]);
+      return;
+    default: return;
+  }
+  if (i >= n) return;
+  out[i] = r0;
+  if (outs > 1) out[n + i] = r1;
+  if (outs > 2) out[2 * n + i] = r2;
+}
+
+// div2_shared against the device's own IEEE division for the `nnum` numerators (pairs: a pass's
+// norm2_0gt1, norm2_0lt1) and every `stride`-th float denominator of [2^-40, 2^40) (80 * 2^23 of
+// them; stride 1: all).  Counts the quotients that differ; of every `sample_every`-th checked
+// denominator the quotients go to `sample` ([checked index / sample_every][nnum]) for the host to
+// compare with ITS division.
+struct Div2Numerators { float v[12]; };
+__global__ __launch_bounds__(256) void k_probe_div2_sweep(Div2Numerators num, int nnum, unsigned stride,
+                                                         unsigned long long count, unsigned sample_every,
+                                                         unsigned long long* bad, float* sample) {
+  const unsigned long long k = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;   // checked index
+  if (k >= count) return;
+  const unsigned idx = (unsigned)(k * stride);
+  const unsigned e = idx >> 23, m = idx & 0x7fffffu;
+  const float d = __uint_as_float(((e + 127u - 40u) << 23) | m);
+  unsigned nb = 0;
+  for (int p = 0; p + 1 < nnum; p += 2) {
+    float q0, q1;
+    div2_shared(num.v[p], num.v[p + 1], d, &q0, &q1);
+    nb += __float_as_uint(q0) != __float_as_uint(num.v[p] / d);
+    nb += __float_as_uint(q1) != __float_as_uint(num.v[p + 1] / d);
+    if (sample && k % sample_every == 0) {
+      sample[(k / sample_every) * nnum + p] = q0;
+      sample[(k / sample_every) * nnum + p + 1] = q1;
+    }
+  }
+  if (nb) atomicAdd(bad, (unsigned long long)nb);
+}
+
 }  // namespace gz

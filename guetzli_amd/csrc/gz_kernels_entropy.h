@@ -211,6 +211,12 @@ GZ_DEVFN int quant_div(int a, int q, float rq) {
   k -= r < 0 ? 1 : 0;
   return a < 0 ? -k : k;
 }
+// gz_probe_math's op for it: out[i] = quant_div(a[i], q[i], 1.0f / (float)q[i]), rq as WaveTables gets it.
+__global__ __launch_bounds__(256) void k_probe_quant_div(const int* a, const int* q, int* out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = quant_div(a[i], q[i], 1.0f / (float)q[i]);
+}
 
 template <int UPM> struct McuShape {
   static constexpr int kComps = UPM == 1 ? 1 : 3;

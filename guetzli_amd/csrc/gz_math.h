@@ -162,8 +162,8 @@ struct MaltaNorm {
   int fast_div;   // 1: norm2_* are in [2^-40, 2^40] (malta_diff may share one reciprocal)
 };
 // The reference's statement sequence, kept as the definition the fast form below is checked
-// against (tests/cpp/verify_malta_diff.cc on the host; tools/ubench/divcheck.hip for the
-// division on the device).
+// against (tests/cpp/verify_malta_diff.cc on the host; tests/cpp/test_device_math.cc through
+// gz_probe_math / gz_probe_div2_sweep on the device).
 GZ_DEVFN float malta_diff_plain(float a, float b, const MaltaNorm nm) {
   const float absval = (float)(0.5 * (double)fabsf(a) + 0.5 * (double)fabsf(b));
   const float diff = a - b;

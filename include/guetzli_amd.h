@@ -482,6 +482,12 @@ int gz_probe_blur(gz_ctx* ctx, const float* in, float sigma, float border_ratio,
 int gz_probe_opsin(gz_ctx* ctx, const float* rgb3, float* xyb3); /* :324-366 */
 int gz_probe_separate_frequencies(gz_ctx* ctx, const float* xyb3,
                                   float* out10);                /* :489-622; lf3,mf3,hf2,uhf2 */
+/* PRECONDITION of gz_probe_diffmap: rgb0_3 must be the linear image (sRGB table of the 8-bit
+ * samples) of the context's CURRENT original -- the one given to gz_create or to the last
+ * gz_set_rgb.  The probe computes rgb0's band planes itself, but its mask branch is the production
+ * one, which reads the original's half of DiffPrecompute that gz_set_rgb computed once per image.
+ * With any other rgb0 the call succeeds and the map is wrong (by factors, on every pixel).  To
+ * probe another pair, gz_set_rgb its original first. */
 int gz_probe_diffmap(gz_ctx* ctx, const float* rgb0_3, const float* rgb1_3,
                      float* diffmap, float* score);             /* :784-908 both sides */
 int gz_probe_mask(gz_ctx* ctx, const float* xyb0_3, const float* xyb1_3, float* mask3,
@@ -496,6 +502,52 @@ int gz_probe_fdct_blocks(int device, int16_t* blocks, int n);
  * (out of (float)a is float). */
 int gz_probe_arith(int device, int op, const void* a, const void* b, const void* c,
                    void* out, int n);
+
+/* The per-pixel functions of the butteraugli chain (csrc/gz_math.h, quant_div of the entropy
+ * kernels) evaluated element-wise on the device, on host-supplied operands: the device-only forms
+ * (two quotients from one hardware reciprocal, Malta's branch-free "diffs" value with its
+ * wavefront-uniform rare path, the division by a constant through two fused multiply-adds) and
+ * every value branch can be compared with the plain C++ statement sequences at values no image
+ * produces.  a, b, c: n floats each unless stated; p: the op's np constants; out: n floats per
+ * output, output-major (out[k * n + i]).  256 consecutive elements share a workgroup, 64 a
+ * wavefront.
+ *   op                         inputs                          p                             outputs
+ *   GZ_MATH_DIV2_SHARED        a = n0, b = n1, c = d           -                             n0/d, n1/d
+ *   GZ_MATH_MALTA_DIFF         a, b                            norm2_0gt1, norm2_0lt1,       1
+ *   GZ_MATH_MALTA_DIFF_PLAIN   a, b                              norm1f, fast_div            1
+ *   GZ_MATH_GAMMA_POLY         a                               -                             1
+ *   GZ_MATH_OPSIN_PIXEL        a = blurred rgb [3][n],         -                             x, y, b
+ *                              b = sharp rgb [3][n]
+ *   GZ_MATH_MAXIMUM_CLAMP      a                               maxval                        1
+ *   GZ_MATH_REMOVE_RANGE       a                               w                             1
+ *   GZ_MATH_AMPLIFY_RANGE      a                               w                             1
+ *   GZ_MATH_SUPPRESS_X_BY_Y    a = x, b = y                    -                             1
+ *   GZ_MATH_SUPPRESS_BRIGHT    a = hf, b = brightness          mul, reg                      1
+ *   GZ_MATH_LF_TO_VALS         a = x, b = y, c = b             -                             3
+ *   GZ_MATH_L2DIFF             a = acc, b, c                   w                             1
+ *   GZ_MATH_L2DIFF_ASYM        a = acc, b, c                   w_0gt1, w_0lt1 (times 0.8)    1
+ *   GZ_MATH_SAME_NOISE_PRE     a, b                            -                             1
+ *   GZ_MATH_DIFF_FROM_SUPS     a = sup0, b = sup1              -                             1
+ *   GZ_MATH_INTERP_LUT512      a = ix (n DOUBLES)              the table, 512 doubles        1 (double)
+ *   GZ_MATH_QUANT_DIV          a, b = q >= 1 (n int32 each)    -                             1 (int32)  */
+enum {
+  GZ_MATH_DIV2_SHARED = 0, GZ_MATH_MALTA_DIFF, GZ_MATH_MALTA_DIFF_PLAIN, GZ_MATH_GAMMA_POLY,
+  GZ_MATH_OPSIN_PIXEL, GZ_MATH_MAXIMUM_CLAMP, GZ_MATH_REMOVE_RANGE, GZ_MATH_AMPLIFY_RANGE,
+  GZ_MATH_SUPPRESS_X_BY_Y, GZ_MATH_SUPPRESS_BRIGHT, GZ_MATH_LF_TO_VALS, GZ_MATH_L2DIFF,
+  GZ_MATH_L2DIFF_ASYM, GZ_MATH_SAME_NOISE_PRE, GZ_MATH_DIFF_FROM_SUPS, GZ_MATH_INTERP_LUT512,
+  GZ_MATH_QUANT_DIV, GZ_MATH_OP_COUNT
+};
+int gz_probe_math(int device, int op, int n, const void* a, const void* b, const void* c,
+                  const double* p, int np, void* out);
+/* div2_shared against the device's own IEEE division, on the device: for the nnum numerators (an
+ * even number, at most 12: each pair shares its reciprocal) and every stride-th float denominator
+ * of [2^-40, 2^40) -- 80 * 2^23 of them, stride 1: all -- the number of quotients that differ.
+ * sample (may be null): the quotients of every sample_every-th CHECKED denominator,
+ * sample[(k / sample_every) * nnum + j] for the k-th checked one, for the host to compare with its
+ * own division; sample_cap: floats available there. */
+int gz_probe_div2_sweep(int device, const float* numerators, int nnum, unsigned stride,
+                        unsigned sample_every, uint64_t* mismatches, float* sample,
+                        size_t sample_cap);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,41 @@ namespace {
 
 typedef std::vector<float> Plane;
 
+// ================================================================== branch census ==
+// How many samples took each arm of each value branch of the butteraugli chain since the
+// last orc_branch_census_reset().  Counting only: no arm's arithmetic depends on it.  The
+// tests use it to show that their inputs reach every arm (tests/test_value_domain.py).
+#define GZ_CENSUS_ARMS(X)                                                                  \
+  X(gamma_yq_zero) X(gamma_yq_nonzero) X(gamma_nonfinite)                                  \
+  X(mf_x_remove_range_above) X(mf_x_remove_range_below) X(mf_x_remove_range_inside)        \
+  X(mf_y_amplify_range_above) X(mf_y_amplify_range_below) X(mf_y_amplify_range_inside)     \
+  X(hf_x_remove_range_above) X(hf_x_remove_range_below) X(hf_x_remove_range_inside)        \
+  X(hf_y_maximum_clamp_above) X(hf_y_maximum_clamp_below) X(hf_y_maximum_clamp_inside)     \
+  X(uhf_y_maximum_clamp_above) X(uhf_y_maximum_clamp_below) X(uhf_y_maximum_clamp_inside)  \
+  X(malta_neg_too_small) X(malta_neg_too_big) X(malta_neg_no_hit)                          \
+  X(malta_pos_too_small) X(malta_pos_too_big) X(malta_pos_no_hit)                          \
+  X(malta_hit_diff_negative) X(malta_hit_diff_nonnegative)                                 \
+  X(malta_sum_zero) X(malta_sum_outside_2p100) X(malta_den_above_2p40)                     \
+  X(l2asym_neg_too_small) X(l2asym_neg_too_big) X(l2asym_neg_no_hit)                       \
+  X(l2asym_pos_too_small) X(l2asym_pos_too_big) X(l2asym_pos_no_hit)                       \
+  X(same_noise_clamp0) X(same_noise_clamp1) X(same_noise_no_clamp)                         \
+  X(diff_precompute_cutoff) X(diff_precompute_below_cutoff)                                \
+  X(lut_index_negative) X(lut_index_top) X(lut_index_inside)                               \
+  X(combine_linear) X(combine_sqrt)
+enum CensusArm {
+#define X(n) kArm_##n,
+  GZ_CENSUS_ARMS(X)
+#undef X
+  kArmCount
+};
+const char* const kCensusNames[kArmCount] = {
+#define X(n) #n,
+  GZ_CENSUS_ARMS(X)
+#undef X
+};
+unsigned long long g_census[kArmCount];
+inline void tick(int arm) { ++g_census[arm]; }
+
 // ===================================================================== block path ==
 
 // ref: guetzli/idct.cc:29-38.  Only rows 0..3 are used (as in Compute1dIDCT); rows
@@ -247,6 +282,8 @@ inline double gamma_poly(double v) {
   const double xc = 2.0 * x01 - 1.0;
   const double yp = clenshaw6(xc, p);
   const double yq = clenshaw6(xc, q);
+  if (!(xc * 0.0 == 0.0)) tick(kArm_gamma_nonfinite);
+  tick(yq == 0.0 ? kArm_gamma_yq_zero : kArm_gamma_yq_nonzero);
   if (yq == 0.0) return 0.0;
   return static_cast<float>(yp / yq);
 }
@@ -271,22 +308,29 @@ void opsin(const float* rgb, int w, int h, float* xyb) {
 
 // =================================================== butteraugli: frequency bands ==
 
-inline float remove_range(float w, float x) {   // butteraugli.cc:369
+// (`arm`: the census entry of the call site's first arm -- above, below, inside follow each other)
+inline float remove_range(float w, float x, int arm) {   // butteraugli.cc:369
+  tick(arm + (x > w ? 0 : x < -w ? 1 : 2));
   return x > w ? x - w : x < -w ? x + w : 0.0f;
 }
-inline float amplify_range(float w, float x) {  // :374
+inline float amplify_range(float w, float x, int arm) {  // :374
+  tick(arm + (x > w ? 0 : x < -w ? 1 : 2));
   return x > w ? x + w : x < -w ? x - w : 2.0f * x;
 }
-inline float maximum_clamp(float v, float maxval) {  // :432-444
+inline float maximum_clamp(float v, float maxval, int arm) {  // :432-444
   static const double kMul = 0.688059627878;
   if (v >= maxval) {
+    tick(arm);
     v -= maxval;
     v *= kMul;
     v += maxval;
   } else if (v < -maxval) {
+    tick(arm + 1);
     v += maxval;
     v *= kMul;
     v -= maxval;
+  } else {
+    tick(arm + 2);
   }
   return v;
 }
@@ -319,8 +363,8 @@ void separate_frequencies(const float* xyb, int w, int h, Psycho* ps) {
     static const double w0 = 0.120079806822, w1 = 0.03430529365;
     for (size_t p = 0; p < n; ++p) {
       ps->hf[i][p] -= ps->mf[i][p];
-      ps->mf[i][p] = i == 0 ? remove_range(w0, ps->mf[i][p])
-                            : amplify_range(w1, ps->mf[i][p]);
+      ps->mf[i][p] = i == 0 ? remove_range(w0, ps->mf[i][p], kArm_mf_x_remove_range_above)
+                            : amplify_range(w1, ps->mf[i][p], kArm_mf_y_amplify_range_above);
     }
   }
   // SuppressXByY (:470-487), all double per pixel.
@@ -352,11 +396,11 @@ void separate_frequencies(const float* xyb, int w, int h, Psycho* ps) {
       float& hf = ps->hf[i][p];
       uhf -= hf;
       if (i == 0) {
-        hf = remove_range(kRemoveHfRange, hf);
+        hf = remove_range(kRemoveHfRange, hf, kArm_hf_x_remove_range_above);
       } else {
         const float br = ps->lf[1][p];   // raw LF-Y, before the vals conversion
-        hf = maximum_clamp(hf, kMaxclampHf);
-        uhf = maximum_clamp(uhf, kMaxclampUhf);
+        hf = maximum_clamp(hf, kMaxclampHf, kArm_hf_y_maximum_clamp_above);
+        uhf = maximum_clamp(uhf, kMaxclampUhf, kArm_uhf_y_maximum_clamp_above);
         uhf = suppress_bright(uhf, br, kMulSuppressUhf, kRegUhf);
         hf = suppress_bright(hf, br, kMulSuppressHf, kRegHf);
       }
@@ -404,16 +448,24 @@ void malta(const float* lum0, const float* lum1, int w, int h, bool lf, double w
     const double too_big = 1.05 * fabs0;
     double impact = 0.0;
     bool hit = true;
+    {   // census: the cases gz_math.h's malta_diff singles out (sum of magnitudes 0 or outside
+        // [2^-100, 2^100]: its FP64 form of absval; denominator above 2^40: its plain divisions)
+      const float s = std::abs(a) + std::abs(b);
+      if (s == 0.0f) tick(kArm_malta_sum_zero);
+      else if (!(s >= 0x1p-100f && s <= 0x1p100f)) tick(kArm_malta_sum_outside_2p100);
+      if (!(static_cast<float>(norm1) + absval <= 0x1p40f)) tick(kArm_malta_den_above_2p40);
+    }
     if (a < 0) {
-      if (b > -too_small) impact = scaler2 * (b + too_small);
-      else if (b < -too_big) impact = scaler2 * (-b - too_big);
-      else hit = false;
+      if (b > -too_small) { tick(kArm_malta_neg_too_small); impact = scaler2 * (b + too_small); }
+      else if (b < -too_big) { tick(kArm_malta_neg_too_big); impact = scaler2 * (-b - too_big); }
+      else { tick(kArm_malta_neg_no_hit); hit = false; }
     } else {
-      if (b < too_small) impact = scaler2 * (too_small - b);
-      else if (b > too_big) impact = scaler2 * (b - too_big);
-      else hit = false;
+      if (b < too_small) { tick(kArm_malta_pos_too_small); impact = scaler2 * (too_small - b); }
+      else if (b > too_big) { tick(kArm_malta_pos_too_big); impact = scaler2 * (b - too_big); }
+      else { tick(kArm_malta_pos_no_hit); hit = false; }
     }
     if (hit) {
+      tick(diff < 0 ? kArm_malta_hit_diff_negative : kArm_malta_hit_diff_nonnegative);
       if (diff < 0) d -= impact; else d += impact;
     }
     diffs[i] = d;
@@ -475,8 +527,9 @@ const MaskLuts& mask_luts() {
 }
 // ref: butteraugli.cc:236-251
 inline double interp_clamp_neg(const double* a, int size, double ix) {
-  if (ix < 0) ix = 0;
+  if (ix < 0) { tick(kArm_lut_index_negative); ix = 0; }
   const int base = static_cast<int>(ix);
+  tick(base >= size - 1 ? kArm_lut_index_top : kArm_lut_index_inside);
   if (base >= size - 1) return a[size - 1];
   const double mix = ix - base;
   return a[base] + mix * (a[base + 1] - a[base]);
@@ -494,6 +547,7 @@ void diff_precompute(const float* p0, const float* p1, int w, int h, float* out)
       static const double mul0 = 0.918416534734;
       float v = mul0 * std::min(sup0, sup1);
       static const double cutoff = 55.0184555849;
+      tick(v >= cutoff ? kArm_diff_precompute_cutoff : kArm_diff_precompute_below_cutoff);
       if (v >= cutoff) v = cutoff;
       out[i] = v;
     }
@@ -584,19 +638,27 @@ void l2diff_asym(const Plane& i0, const Plane& i1, double w_0gt1, double w_0lt1,
     const double too_big = 1.0 * fabs0;
     if (a < 0) {
       if (b > -too_small) {
+        tick(kArm_l2asym_neg_too_small);
         double v = b + too_small;
         out += w_0lt1 * v * v;
       } else if (b < -too_big) {
+        tick(kArm_l2asym_neg_too_big);
         double v = -b - too_big;
         out += w_0lt1 * v * v;
+      } else {
+        tick(kArm_l2asym_neg_no_hit);
       }
     } else {
       if (b < too_small) {
+        tick(kArm_l2asym_pos_too_small);
         double v = too_small - b;
         out += w_0lt1 * v * v;
       } else if (b > too_big) {
+        tick(kArm_l2asym_pos_too_big);
         double v = b - too_big;
         out += w_0lt1 * v * v;
+      } else {
+        tick(kArm_l2asym_pos_no_hit);
       }
     }
   }
@@ -609,6 +671,9 @@ void same_noise_levels(const Plane& i0, const Plane& i1, int w, int h, double kS
   for (size_t p = 0; p < n; ++p) {
     double v0 = std::fabs(i0[p]);
     double v1 = std::fabs(i1[p]);
+    if (v0 > maxclamp) tick(kArm_same_noise_clamp0);
+    if (v1 > maxclamp) tick(kArm_same_noise_clamp1);
+    if (!(v0 > maxclamp) && !(v1 > maxclamp)) tick(kArm_same_noise_no_clamp);
     if (v0 > maxclamp) v0 = maxclamp;
     if (v1 > maxclamp) v1 = maxclamp;
     t[p] = v0 - v1;
@@ -668,6 +733,7 @@ void diffmap_psycho(const Psycho& pi0, const Psycho& pi1, int w, int h, float* r
     const float a = dc[0][p] * mdc[p] + dc[1][p] * mdc[n + p] + dc[2][p] * mdc[2 * n + p];
     const float b = ac[0][p] * m[p] + ac[1][p] * m[n + p] + ac[2][p] * m[2 * n + p];
     const float v = a + b;
+    tick(v < (1.0f / (kInitialSlope * kInitialSlope)) ? kArm_combine_linear : kArm_combine_sqrt);
     d[p] = v < (1.0f / (kInitialSlope * kInitialSlope)) ? kInitialSlope * v : std::sqrt(v);
   }
   static const double kSigma = 1.72547472444, mul1 = 0.458794906198;
@@ -1093,6 +1159,14 @@ void orc_blur(const float* in, int w, int h, float sigma, float border_ratio,
 }
 
 void orc_opsin(const float* rgb, int w, int h, float* xyb) { opsin(rgb, w, h, xyb); }
+
+// The branch census: counts since the last reset, in the order of orc_branch_census_name(i).
+int orc_branch_census(unsigned long long* out, int n) {
+  for (int i = 0; i < n && i < kArmCount; ++i) out[i] = g_census[i];
+  return kArmCount;
+}
+const char* orc_branch_census_name(int i) { return i >= 0 && i < kArmCount ? kCensusNames[i] : nullptr; }
+void orc_branch_census_reset(void) { memset(g_census, 0, sizeof(g_census)); }
 
 void orc_separate_frequencies(const float* xyb, int w, int h, float* out10) {
   Psycho ps;

@@ -46,6 +46,14 @@ void orc_malta(const float* lum0, const float* lum1, int w, int h, int lf,
                double w_0gt1, double w_0lt1, double norm1, float* acc);
 double orc_diffmap(const float* rgb0, const float* rgb1, int w, int h, float* diffmap);
 
+/* ---- branch census: samples per arm of every value branch of the stages above since the last
+ * reset (remove_range, amplify_range, maximum_clamp, the Malta and L2DiffAsymmetric ladders,
+ * the SameNoiseLevels clamps, DiffPrecompute's cutoff, the mask LUT's ends, the sqrt stage).
+ * orc_branch_census fills out[0..n) and returns the number of arms. ---- */
+int  orc_branch_census(unsigned long long* out, int n);
+const char* orc_branch_census_name(int i);
+void orc_branch_census_reset(void);
+
 /* ---- guetzli comparator (a17-a21) ---- */
 void* orc_comparator_create(const uint8_t* rgb, int w, int h, float target);
 void  orc_comparator_destroy(void* c);

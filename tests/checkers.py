@@ -64,6 +64,9 @@ _REF_ONLY = {
 _ORC_ONLY = {
     "dct_double": (None, [_P, C.c_int]),
     "set_downsampled": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "branch_census": (C.c_int, [_P, C.c_int]),
+    "branch_census_name": (C.c_char_p, [C.c_int]),
+    "branch_census_reset": (None, []),
 }
 
 
@@ -222,6 +225,18 @@ class Checker:
         d = np.zeros((h, w), np.float32)
         score = self._diffmap(_ptr(a), _ptr(b), w, h, _ptr(d))
         return d, score
+
+    # ---- branch census (oracle only) ----------------------------------------------
+    def census_reset(self):
+        self._branch_census_reset()
+
+    def census(self):
+        """{arm: samples that took it since census_reset()} for every value branch of the
+        butteraugli stages (oracle/gz_oracle.h)."""
+        n = self._branch_census(None, 0)
+        a = np.zeros(n, np.uint64)
+        self._branch_census(_ptr(a), n)
+        return {self._branch_census_name(i).decode(): int(a[i]) for i in range(n)}
 
     # ---- guetzli comparator -----------------------------------------------------
     def comparator(self, rgb, target):

@@ -666,3 +666,221 @@ def case_compare_blocks(L, w, h, x0=0, y0=0, qs=3, n=24):
         got_px = ctx.compare_block_pixels(np.array(xy), px.reshape(-1, 3, 64))
         assert_bits_equal(got_px, np.array(exp, np.float64), "CompareBlock (pixels)")
     oc.close()
+
+
+# ------------------------------------------------ value-domain fields (tests/fields.py) --
+BAND_NAMES = ["lf0", "lf1", "lf2", "mf0", "mf1", "mf2", "hf0", "hf1", "uhf0", "uhf1"]
+XYB_SCALES = (40.0, -40.0)   # both arms of maximum_clamp on HF-Y, the top of the mask tables
+
+
+ALL_INSTANTIATIONS = tuple(dict(blur_packed=pk, tile_rows=tr) for pk in (0, 1) for tr in (16, 32))
+
+
+def _configs(ctx, configs):
+    """Walks the context through the given gz_config settings (None: as it is)."""
+    base = ctx.get_config().as_dict()
+    for cfg in configs:
+        if cfg is not None:
+            ctx.set_config(**dict(base, **cfg))
+        yield "" if cfg is None else f" under {cfg}"
+    ctx.set_config(**base)
+
+
+def case_value_domain_stages(L, w, h, only=None, scaled_xyb=True, configs=(None,)):
+    """opsin -> separate_frequencies -> mask -> diffmap against the oracle on every (original,
+    candidate) pair of the synthetic fields: the value branches and the device-only arithmetic at
+    values a photograph against its mildly quantised copy never produces.  gz_probe_diffmap gets a
+    context whose original is the pair's (its mask branch reads the context's precomputed half).
+    configs: gz_config settings (blur tile height, packed passes) each pair is probed under; the
+    oracle's side is computed once per pair."""
+    import fields
+    rgb_of_ctx = None
+    ctx = None
+    try:
+        for name, rgb, lin0, lin1 in fields.pairs(w, h, only):
+            if ctx is None:
+                ctx = L.context(rgb, 1.0)
+            elif rgb is not rgb_of_ctx:
+                ctx.set_rgb(rgb)
+            rgb_of_ctx = rgb
+            x0_, x1_ = oracle.opsin(lin0), oracle.opsin(lin1)
+            band_in = [(x0_ if name.endswith("/self") else x1_, name)]
+            mask_in = [(x0_, x1_, name)]
+            if scaled_xyb and name.endswith(("/self", "/inverse")):
+                for s in XYB_SCALES:
+                    a, b = x0_ * np.float32(s), x1_ * np.float32(s)
+                    band_in.append((b, f"{name} x {s}"))
+                    mask_in.append((a, b, f"{name} x {s}"))
+            band_exp = [oracle.separate_frequencies(x) for x, _ in band_in]
+            mask_exp = [oracle.mask(a, b) for a, b, _ in mask_in]
+            ed, es = oracle.diffmap(lin0, lin1)
+            for under in _configs(ctx, configs):
+                assert_bits_equal(ctx.probe_opsin(lin0), x0_, f"opsin(original) of {name}{under}")
+                assert_bits_equal(ctx.probe_opsin(lin1), x1_, f"opsin(candidate) of {name}{under}")
+                for (x, what), exp in zip(band_in, band_exp):
+                    got = ctx.probe_separate_frequencies(x)
+                    for i, nm in enumerate(BAND_NAMES):
+                        if nm != "mf2":   # dead plane in the reference (wmul[5] == 0), never computed
+                            assert_bits_equal(got[i], exp[i], f"separate_frequencies {nm} of {what}{under}")
+                for (a, b, what), (em, edc) in zip(mask_in, mask_exp):
+                    gm, gdc = ctx.probe_mask(a, b)
+                    assert_bits_equal(gm, em, f"mask of {what}{under}")
+                    assert_bits_equal(gdc, edc, f"mask_dc of {what}{under}")
+                gd, gs = ctx.probe_diffmap(lin0, lin1)
+                assert_bits_equal(gd, ed, f"diffmap of {name}{under}")
+                assert gs == np.float32(es), name
+    finally:
+        if ctx is not None:
+            ctx.close()
+
+
+VALUE_DOMAIN_QSCALES = (1, 3, 12, 40)
+
+
+def case_value_domain_compare(L, w, h, only=None, qscales=VALUE_DOMAIN_QSCALES, target=0.971769, blocks_on=(),
+                              configs=(None,)):
+    """The production path on every synthetic original: encode_rgb -> quantize(q) -> compare; the
+    distance map, the distance, the block maxima and the block weights against the oracle's
+    comparator, under each of the gz_config settings.  On the originals named in `blocks_on` also
+    phase A's candidate orders and the per-block seam (gz_block_zeroing_orders, gz_compare_blocks)."""
+    import fields
+    rng = np.random.default_rng(RNG_SEED + 23 * w + h)
+    for oname, rgb in fields.originals(w, h).items():
+        if only is not None and oname not in only:
+            continue
+        oc = oracle.comparator(rgb, target)
+        with L.context(rgb, target) as ctx:
+            co = ctx.encode_rgb()
+            assert_bits_equal(co, oracle.encode_rgb(rgb), f"encode_rgb of {oname}")
+            for qs in qscales:
+                cq = ctx.quantize(np.full((3, 64), qs, np.int32))
+                edist, edm = oc.compare(cq)
+                pad = np.zeros((ctx.bh * 8, ctx.bw * 8), np.float32)
+                pad[:h, :w] = edm
+                ebm = pad.reshape(ctx.bh, 8, ctx.bw, 8).max(axis=(1, 3)).reshape(-1)
+                ewgt = {d: oc.block_weights(d, 2, 1.0, edm) for d in (1, -1)}
+                for under in _configs(ctx, configs):
+                    dist, dm, bm = ctx.compare()
+                    assert_bits_equal(dm, edm, f"distmap of {oname} q={qs}{under}")
+                    assert dist == edist, (oname, qs, under)
+                    assert_bits_equal(bm, ebm, f"block max of {oname} q={qs}{under}")
+                    for direction in (1, -1):
+                        assert_bits_equal(ctx.block_weights(direction, 2, 1.0), ewgt[direction],
+                                          f"block weights of {oname} q={qs}{under}")
+            if oname in blocks_on:
+                cq = ctx.quantize(np.full((3, 64), 3, np.int32))
+                off, idx, err = ctx.block_zeroing_orders()
+                eoff, eidx, eerr = oc.block_zeroing_orders(cq, co)
+                assert_bits_equal(off, eoff, f"candidate offsets of {oname}")
+                assert_bits_equal(idx, eidx, f"candidate coefficient indices of {oname}")
+                assert_bits_equal(err, eerr, f"candidate errors of {oname}")
+                xy, blocks, exp = [], [], []
+                for _ in range(12):
+                    b = int(rng.integers(0, ctx.nb))
+                    cand = cq.copy()
+                    for _ in range(int(rng.integers(0, 4))):
+                        cand[int(rng.integers(0, 3)), b, int(rng.integers(1, 64))] = 0
+                    xy.append((b % ctx.bw, b // ctx.bw))
+                    blocks.append(cand[:, b, :])
+                    exp.append(oc.compare_block(cand, b % ctx.bw, b // ctx.bw))
+                got = ctx.compare_blocks(np.array(xy), np.stack(blocks))
+                assert_bits_equal(got, np.array(exp, np.float64), f"CompareBlock of {oname}")
+        oc.close()
+
+
+def case_probe_diffmap_needs_the_contexts_original(L, w=72, h=48):
+    """gz_probe_diffmap's documented precondition: rgb0 is the linear image of the context's current
+    original (the mask branch reads the half gz_set_rgb precomputed from it).  After gz_set_rgb(other),
+    a probe with the matching rgb0 equals the oracle."""
+    import fields
+    first = images.crop(w, h, 40, 60)
+    other = fields.photo_with_zero_rectangle(w, h)
+    lin0 = fields.linear(other)
+    lin1 = fields.candidates(other)["jpeg_error_x3"]
+    ed, es = oracle.diffmap(lin0, lin1)
+    with L.context(first, 1.0) as ctx:
+        ctx.set_rgb(other)
+        gd, gs = ctx.probe_diffmap(lin0, lin1)
+        assert_bits_equal(gd, ed, "diffmap after set_rgb(other)")
+        assert gs == np.float32(es)
+        # and back: the context follows its current original, not the one it was created with
+        ctx.set_rgb(first)
+        lf = fields.linear(first)
+        lc = fields.coded(first)
+        gd, gs = ctx.probe_diffmap(lf, lc)
+        ed, es = oracle.diffmap(lf, lc)
+        assert_bits_equal(gd, ed, "diffmap after set_rgb(first)")
+        assert gs == np.float32(es)
+
+
+def case_stream_choice_same_bits(L, w, h):
+    """gz_config.single_stream flipped once on one synthetic field: the same bits."""
+    import fields
+    rgb = fields.photo_with_zero_rectangle(w, h)
+    with L.context(rgb, 0.971769) as ctx:
+        ctx.encode_rgb(download=False)
+        ctx.quantize(np.full((3, 64), 12, np.int32), download=False)
+        base = ctx.get_config().as_dict()
+        ctx.set_config(**dict(base, single_stream=1))
+        d0, dm0, bm0 = ctx.compare()
+        ctx.set_config(**dict(base, single_stream=0))
+        d1, dm1, bm1 = ctx.compare()
+        assert d0 == d1
+        assert_bits_equal(dm1, dm0, "distance map, three streams against one")
+        assert_bits_equal(bm1, bm0, "block maxima, three streams against one")
+
+
+def case_device_math(lib_path, tmp_path, stride, timeout):
+    """tests/cpp/test_device_math.cc: the per-pixel functions evaluated by the library at lib_path
+    (gz_probe_math) against the plain statement sequences on the host, and div2_shared against the
+    device's IEEE division on every stride-th denominator (gz_probe_div2_sweep).  One run under a
+    time limit; a non-zero exit fails."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "test_device_math")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DGZ_EMU",
+                    "-I" + os.path.join(root, "guetzli_amd", "csrc"), "-I" + os.path.join(root, "tests", "emu"),
+                    os.path.join(root, "tests", "cpp", "test_device_math.cc"), "-o", exe, "-ldl"], check=True)
+    out = subprocess.run([exe, lib_path, str(stride)], capture_output=True, text=True, timeout=timeout)
+    print(out.stdout)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "device_math: ok" in out.stdout
+    assert f"div2_shared sweep (stride {stride}):" in out.stdout and " 0 mismatches with the device's division" in out.stdout
+    return out.stdout
+
+
+def case_probe_math_binding(L):
+    """Library.probe_math / Library.div2_sweep (capi.py) on a few hundred elements: absent operands,
+    the parameter block, two outputs, the int32 form, and the sweep's count and sample layout.  The
+    expected values are numpy's IEEE float32 division and C's truncating integer division."""
+    rng = np.random.default_rng(RNG_SEED + 77)
+    n = 320
+    # the production numerators of the first Malta normalisation (butteraugli.cc: 5.1409625726 times and over 0.8)
+    n0 = np.full(n, np.float32(5.1409625726 * np.float32(0.8)), np.float32)
+    n1 = np.full(n, np.float32(5.1409625726 / np.float32(0.8)), np.float32)
+    d = np.exp2(rng.uniform(-40, 40, n)).astype(np.float32)
+    got = L.probe_math(0, n0, n1, d, outs=2)                         # GZ_MATH_DIV2_SHARED
+    assert got.shape == (2, n)
+    assert_bits_equal(got[0], n0 / d, "div2_shared, first quotient")
+    assert_bits_equal(got[1], n1 / d, "div2_shared, second quotient")
+    # GZ_MATH_MAXIMUM_CLAMP: one operand, one parameter; below the bound the value passes through
+    v = rng.uniform(-70.0, 70.0, n).astype(np.float32)
+    assert_bits_equal(L.probe_math(5, v, p=(78.8223237675,))[0], v, "maximum_clamp inside its bounds")
+    above = L.probe_math(5, np.full(n, 100.0, np.float32), p=(78.8223237675,))[0]
+    assert ((above > 78.8223237675) & (above < 100.0)).all()
+    # GZ_MATH_QUANT_DIV: int32 operands
+    a = rng.integers(-32768, 32768, n).astype(np.int32)
+    q = rng.integers(1, 256, n).astype(np.int32)
+    want = (np.sign(a) * (np.abs(a) // q)).astype(np.int32)          # C's a / q
+    assert_bits_equal(L.probe_math(16, a, q)[0], want, "quant_div")
+    # the sweep on every 2^20 + 1-th denominator of [2^-40, 2^40), every sample kept
+    num = np.array([n0[0], n1[0]], np.float32)
+    stride = (1 << 20) + 1
+    bad, sample = L.div2_sweep(num, stride=stride, sample_every=1)
+    assert bad == 0
+    idx = np.arange(sample.shape[0], dtype=np.uint64) * np.uint64(stride)
+    den = ((((idx >> np.uint64(23)) + np.uint64(127 - 40)) << np.uint64(23)) | (idx & np.uint64(0x7fffff)))
+    den = den.astype(np.uint32).view(np.float32)
+    assert sample.shape == (-(-(80 << 23) // stride), 2)
+    assert_bits_equal(sample, num[None, :] / den[:, None], "div2_shared sweep samples")

@@ -85,6 +85,57 @@ def test_device_ranking_is_std_sort(L, tmp_path):
     assert "device == std::sort" in out.stdout
 
 
+def test_probe_math_python_binding(L):
+    pc.case_probe_math_binding(L)
+
+
+def test_device_math_equals_the_plain_forms(L, tmp_path):
+    """gz_math.h's device-only forms with the device's own v_rcp_f32, fused multiply-adds and
+    wavefront-uniform branch: every per-pixel function element-wise against the reference's plain
+    statement sequences evaluated on the host (random, threshold-hugging and special operands, mixed
+    wavefronts), and div2_shared against the device's IEEE division for EVERY float denominator of
+    [2^-40, 2^40) and the twelve production numerators: 0 mismatches."""
+    out = pc.case_device_math(L.path, tmp_path, stride=1, timeout=600)
+    assert f"{12 * (80 << 23)} quotients, 0 mismatches with the device's division" in out
+
+
+# The value-domain fields (tests/fields.py) under both blur tile heights and both settings of the
+# packed passes (gz_config, what GZ_TILE_ROWS / GZ_BLUR_PK fill at gz_create: each pair is probed
+# under the four settings against ONE evaluation of the oracle, which is where the time goes);
+# 444x258: interior Malta tiles on the vector path (pitch a multiple of 4), interior blur tiles, the
+# radius >= 16 interior path from x0 >= 256; 333x141: ragged, the generic paths.
+@pytest.mark.parametrize("wh", [(444, 258), (333, 141)])
+def test_value_domain_stages(L, wh):
+    pc.case_value_domain_stages(L, *wh, configs=pc.ALL_INSTANTIATIONS)
+
+
+@pytest.mark.parametrize("wh", [(444, 258), (333, 141)])
+def test_value_domain_compare(L, wh):
+    pc.case_value_domain_compare(L, *wh, configs=pc.ALL_INSTANTIATIONS,
+                                 blocks_on=("checker8", "primaries", "noise", "photo_zero_rect",
+                                            "impulses_black", "step_v", "ramp"))
+
+
+def test_value_domain_under_the_environment_switches(L, monkeypatch):
+    """The same switches as the environment sets them at gz_create (as test_paired_row_column_passes does)."""
+    monkeypatch.setenv("GZ_BLUR_PK", "1")
+    monkeypatch.setenv("GZ_TILE_ROWS", "32")
+    only = ("photo_zero_rect", "checker1", "primaries")
+    pc.case_value_domain_stages(L, 444, 258, only=only)
+    pc.case_value_domain_compare(L, 444, 258, only=only, qscales=(3, 40))
+    monkeypatch.setenv("GZ_BLUR_PK", "0")
+    monkeypatch.setenv("GZ_TILE_ROWS", "16")
+    pc.case_value_domain_stages(L, 333, 141, only=only)
+
+
+def test_probe_diffmap_follows_the_contexts_current_original(L):
+    pc.case_probe_diffmap_needs_the_contexts_original(L, 200, 110)
+
+
+def test_value_domain_stream_choice(L):
+    pc.case_stream_choice_same_bits(L, 444, 258)
+
+
 def test_malta_interior_and_border_tiles(L):
     """k_malta_rolled on an image with interior and border Malta tiles, against the oracle."""
     pc.case_compare(L, 200, 110, x0=100, y0=60, qscales=(5,))
@@ -399,6 +450,10 @@ GOLDEN_JPEG_SHA = {
 }
 GOLDEN_TRACE_SHA = {
     (444, 258, 95): "954ec7623366bc3c345fc5b0748017f9a5e0128aba0917a249cca390a615f787",
+    # (derived from the unmodified reference's trace, equal to the digests of BASELINE.md section 2:
+    # 114 and 231 lines)
+    (444, 258, 84): "4614a5283cbf84be626cfbb987b84808ca01835e18d72dae136babcdd1c9e38f",
+    (1920, 1080, 95): "39b9ff411272c3dc6522fb952e49febfed28ab9edca255d3ec83ddb8ebd85c20",
 }
 
 
@@ -442,13 +497,15 @@ def test_png_file_in_jpeg_out_matches_the_reference_golden():
 
 
 def test_whole_encode_1080p_bit_identical_jpeg():
-    """BASELINE config 2 (1920x1080, quality 95): byte-identical to the reference output."""
+    """BASELINE config 2 (1920x1080, quality 95): byte-identical to the reference output, and so is
+    the --verbose trace (the ordered record of every evaluation of the search)."""
     import hashlib
     import guetzli_amd
     rgb = images.tiled(1920, 1080)
-    jpg, info = guetzli_amd.process(rgb, quality=95)
+    jpg, info = guetzli_amd.process(rgb, quality=95, want_trace=True)
     assert len(jpg) == 721187
     assert hashlib.sha256(jpg).hexdigest() == GOLDEN_JPEG_SHA[(1920, 1080, 95)]
+    assert hashlib.sha256(info["trace"].encode()).hexdigest() == GOLDEN_TRACE_SHA[(1920, 1080, 95)]
 
 
 @pytest.mark.parametrize("q,size", [(95, 2895866), (84, 1430837)])

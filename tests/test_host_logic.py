@@ -122,7 +122,9 @@ def test_malta_diff_fast_form_equals_the_reference_sequence(tmp_path):
     the reference's statement sequence on 10^8 random / threshold-hugging / denormal / huge
     pairs for the six normalisations in use, and the shared-reciprocal division against the IEEE
     quotient for every mantissa of the denominator with the reciprocal estimate off by -1, 0
-    and +1 ulp (the device's own v_rcp_f32 is covered by tools/ubench/divcheck.hip)."""
+    and +1 ulp.  The device's own v_rcp_f32 is covered by tests/cpp/test_device_math.cc: the
+    emulation suite runs it on a strided subset of the denominators (test_kernels_emu.py), the GPU
+    suite on every one (test_gpu_parity.py::test_device_math_equals_the_plain_forms)."""
     exe = str(tmp_path / "verify_md")
     subprocess.run(["g++", "-O2", "-mfma", "-ffp-contract=off", "-pthread", "-DGZ_EMU",
                     "-I" + os.path.join(ROOT, "guetzli_amd", "csrc"), "-I" + os.path.join(ROOT, "tests", "emu"),

@@ -195,3 +195,54 @@ def test_patched_candidate_planes(L, wh):
 
 def test_global_order420(L):
     pc.case_global_order420(L, 48, 40, oracle, x0=100, y0=60)
+
+
+# ------------------------------------------------ value-domain fields (tests/fields.py) --
+def test_value_domain_stages(L):
+    """Every stage probe on every (original, candidate) pair of the synthetic fields."""
+    pc.case_value_domain_stages(L, 96, 72)
+
+
+def test_value_domain_stages_ragged(L):
+    pc.case_value_domain_stages(L, 45, 35, scaled_xyb=False)
+
+
+def test_value_domain_under_every_instantiation(L):
+    """The form the GPU suite runs: each pair probed under the four gz_config settings (16- / 32-row
+    tiles, packed passes or not) against one evaluation of the oracle."""
+    only = ("photo_zero_rect", "primaries")
+    pc.case_value_domain_stages(L, 72, 48, only=only, configs=pc.ALL_INSTANTIATIONS)
+    pc.case_value_domain_compare(L, 72, 48, only=only, qscales=(3,), configs=pc.ALL_INSTANTIATIONS)
+
+
+def test_value_domain_compare(L):
+    pc.case_value_domain_compare(L, 45, 35, blocks_on=("checker8", "primaries", "noise", "photo_zero_rect",
+                                                       "impulses_black", "step_v", "ramp"))
+
+
+def test_value_domain_interior_tiles_32_rows_packed(L, monkeypatch):
+    """Wide and tall enough for interior blur and Malta tiles, through the 32-row tiles and the packed
+    passes; the pasted rectangle gives Malta tiles that mix all-zero sample pairs with others."""
+    monkeypatch.setenv("GZ_TILE_ROWS", "32")
+    monkeypatch.setenv("GZ_BLUR_PK", "1")
+    only = ("photo_zero_rect", "checker1", "primaries")
+    pc.case_value_domain_stages(L, 200, 110, only=only)
+    pc.case_value_domain_compare(L, 200, 110, only=only, qscales=(3, 40))
+
+
+def test_probe_diffmap_follows_the_contexts_current_original(L):
+    pc.case_probe_diffmap_needs_the_contexts_original(L)
+
+
+def test_value_domain_stream_choice(L):
+    pc.case_stream_choice_same_bits(L, 136, 88)
+
+
+def test_probe_math_python_binding(L):
+    pc.case_probe_math_binding(L)
+
+
+def test_device_math_driver_on_a_strided_sweep(L, tmp_path):
+    """The driver of the device-side math check against the emulation build: validates the harness
+    (inputs, plain forms, the probe's plumbing) where no GPU is; the reciprocal here is the emulated one."""
+    pc.case_device_math(L.path, tmp_path, stride=4099, timeout=300)

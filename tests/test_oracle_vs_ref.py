@@ -301,3 +301,67 @@ def test_comparator_420_compare_weights_and_orders():
                     assert_bits_equal(x, y, f"{what} frame420={frame420} mask={mask} la={lookahead}")
     oc.close()
     rc.close()
+
+
+# ------------------------------------------------ value-domain fields (tests/fields.py) --
+# The six Malta passes of DiffmapPsychoImage: (band plane of separate_frequencies' ten, LF taps,
+# w_0gt1, w_0lt1, norm1), with hf_asymmetry = 0.8f and its FLOAT square root as the reference has them.
+_ASYM = np.float32(0.8)
+_SQ = np.sqrt(_ASYM)          # float32
+MALTA_PASSES = [(9, False, 5.1409625726 * float(_ASYM), 5.1409625726 / float(_ASYM), 58.5001247061),
+                (8, False, 4.91743441556 * float(_ASYM), 4.91743441556 / float(_ASYM), 687196.39002),
+                (7, True, 153.671655716 * float(_SQ), 153.671655716 / float(_SQ), 83150785.9592),
+                (6, True, 668.358918152 * float(_SQ), 668.358918152 / float(_SQ), 0.882954368025),
+                (4, True, 6841.81248144, 6841.81248144, 0.0135134962487),
+                (3, True, 813.901703816, 813.901703816, 16792.9322251)]
+
+
+def test_value_domain_fields_oracle_equals_reference():
+    """The synthetic fields the kernels are checked on (tests/fields.py) through the oracle and the
+    unmodified reference: opsin, separate_frequencies (the scaled XYB planes of the stage probes
+    included), mask, the six production Malta normalisations on the fields' band planes, and the
+    distance map -- the oracle is pinned on this data as it is on photographs."""
+    import fields
+    import parity_cases as pc
+    w, h = 96, 72
+    for name, rgb, lin0, lin1 in fields.pairs(w, h):
+        x0, x1 = ref.opsin(lin0), ref.opsin(lin1)
+        assert_bits_equal(oracle.opsin(lin0), x0, f"opsin(original) of {name}")
+        assert_bits_equal(oracle.opsin(lin1), x1, f"opsin(candidate) of {name}")
+        p0, p1 = ref.separate_frequencies(x0), ref.separate_frequencies(x1)
+        assert_bits_equal(oracle.separate_frequencies(x1), p1, f"separate_frequencies of {name}")
+        for a, b, what in [(x0, x1, name)] + ([(x0 * np.float32(s), x1 * np.float32(s), f"{name} x {s}")
+                                                for s in pc.XYB_SCALES] if name.endswith(("/self", "/inverse")) else []):
+            if a is not x0:
+                assert_bits_equal(oracle.separate_frequencies(b), ref.separate_frequencies(b),
+                                  f"separate_frequencies of {what}")
+            om, omdc = oracle.mask(a, b)
+            rm, rmdc = ref.mask(a, b)
+            assert_bits_equal(om, rm, f"mask of {what}")
+            assert_bits_equal(omdc, rmdc, f"mask_dc of {what}")
+        for plane, lf, wa, wb, n1 in MALTA_PASSES:
+            assert_bits_equal(oracle.malta(p0[plane], p1[plane], lf, wa, wb, n1),
+                              ref.malta(p0[plane], p1[plane], lf, wa, wb, n1), f"malta plane {plane} of {name}")
+        od, os_ = oracle.diffmap(lin0, lin1)
+        rd, rs = ref.diffmap(lin0, lin1)
+        assert_bits_equal(od, rd, f"diffmap of {name}")
+        assert os_ == rs, name
+
+
+def test_value_domain_fields_comparator_oracle_equals_reference():
+    """... and the production comparator on every synthetic original at the cases' quantisers."""
+    import fields
+    import parity_cases as pc
+    w, h = 45, 35
+    for oname, rgb in fields.originals(w, h).items():
+        co = ref.encode_rgb(rgb)
+        assert_bits_equal(oracle.encode_rgb(rgb), co, f"encode_rgb of {oname}")
+        oc, rc = oracle.comparator(rgb, 0.971769), ref.comparator(rgb, 0.971769)
+        for qs in pc.VALUE_DOMAIN_QSCALES:
+            cq, _, _ = ref.reconstruct(co, w, h, np.full((3, 64), qs, np.int32))
+            od, odm = oc.compare(cq)
+            rd, rdm = rc.compare(cq)
+            assert_bits_equal(odm, rdm, f"distmap of {oname} q={qs}")
+            assert od == rd
+        oc.close()
+        rc.close()

@@ -1,7 +1,7 @@
-// Device check of gz::div2_shared (gz_math.h): for the twelve numerators of the six Malta
-// normalisations and EVERY float denominator in [2^-40, 2^40] (80 x 2^23 values), the two
-// quotients from one v_rcp_f32 equal the compiler's IEEE divisions bit for bit.  Also times
-// malta_diff against malta_diff_plain on band-like data.
+// Times gz::malta_diff (gz_math.h: no if-ladder, two quotients from one v_rcp_f32) against
+// malta_diff_plain on band-like data.  Timing only: that the two give the same bits on the device
+// -- for every float denominator of [2^-40, 2^40] -- is checked by the suite (gz_probe_div2_sweep,
+// gz_probe_math: tests/cpp/test_device_math.cc, run by tests/test_gpu_parity.py).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I../../guetzli_amd/csrc divcheck.hip -o divcheck
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -27,27 +27,6 @@ static MaltaNorm norm_of(bool lf, double w_0gt1, double w_0lt1, double norm1) {
 }
 struct Norms { MaltaNorm n[6]; };
 
-__global__ void k_check(Norms nn, unsigned long long* bad) {
-  const unsigned idx = blockIdx.x * 256u + threadIdx.x;   // 80 * 2^23 denominators
-  const unsigned e = idx >> 23, m = idx & 0x7fffffu;
-  const float d = __uint_as_float(((e + 127u - 40u) << 23) | m);
-  unsigned b = 0;
-  for (int k = 0; k < 6; ++k) {
-    float q0, q1;
-    gz::div2_shared(nn.n[k].norm2_0gt1, nn.n[k].norm2_0lt1, d, &q0, &q1);
-    b += __float_as_uint(q0) != __float_as_uint(nn.n[k].norm2_0gt1 / d);
-    b += __float_as_uint(q1) != __float_as_uint(nn.n[k].norm2_0lt1 / d);
-  }
-  if (b) atomicAdd(bad, (unsigned long long)b);
-}
-template <bool FAST>
-__global__ void k_time(const float* a, const float* b, float* o, MaltaNorm nm, int n, unsigned long long* bad) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float r = FAST ? gz::malta_diff(a[i], b[i], nm) : gz::malta_diff_plain(a[i], b[i], nm);
-  if (FAST && __float_as_uint(r) != __float_as_uint(gz::malta_diff_plain(a[i], b[i], nm))) atomicAdd(bad, 1ull);
-  o[i] = r;
-}
 template <bool FAST>
 __global__ void k_time_only(const float* a, const float* b, float* o, MaltaNorm nm, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -76,11 +55,6 @@ int main() {
   nn.n[3] = norm_of(false, 4.91743441556 * asym, 4.91743441556 / asym, 687196.39002);
   nn.n[4] = norm_of(true, 668.358918152 * sq, 668.358918152 / sq, 0.882954368025);
   nn.n[5] = norm_of(true, 813.901703816, 813.901703816, 16792.9322251);
-  unsigned long long* bad; hipMalloc(&bad, 16); hipMemset(bad, 0, 16);
-  hipLaunchKernelGGL(k_check, dim3(80u * (1u << 23) / 256u), dim3(256), 0, 0, nn, bad);
-  unsigned long long hb[2] = {0, 0};
-  hipMemcpy(hb, bad, 8, hipMemcpyDeviceToHost);
-  printf("div2_shared on the device: %llu quotients, %llu mismatches\n", 12ull * 80 * (1u << 23), hb[0]);
   const int n = 1 << 24;
   float *a, *b, *o; hipMalloc(&a, n * 4); hipMalloc(&b, n * 4); hipMalloc(&o, n * 4);
   float* h = (float*)malloc(n * 4);
@@ -90,9 +64,6 @@ int main() {
   hipMemcpy(a, h, n * 4, hipMemcpyHostToDevice);
   for (int i = 0; i < n; ++i) h[i] = h[i] * (0.3f + 1.2f * rnd()) * (rnd() < 0.05f ? -1.0f : 1.0f);
   hipMemcpy(b, h, n * 4, hipMemcpyHostToDevice);
-  for (int k = 0; k < 6; ++k) hipLaunchKernelGGL(k_time<true>, dim3(n / 256), dim3(256), 0, 0, a, b, o, nn.n[k], n, bad + 1);
-  hipMemcpy(hb, bad, 16, hipMemcpyDeviceToHost);
-  printf("malta_diff vs malta_diff_plain on the device: %d x 6 pairs, %llu mismatches\n", n, hb[1]);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int fast = 0; fast < 2; ++fast) {
     hipEventRecord(e0);
@@ -115,5 +86,5 @@ int main() {
     printf("%s, 48 evaluations per loaded pair: %.1f us per 16.8 M pairs = %.3f ns per evaluation chip-wide\n",
            fast ? "malta_diff      " : "malta_diff_plain", ms / 5 * 1000, ms / 5 * 1e6 / (48.0 * n));
   }
-  return hb[0] || hb[1] ? 1 : 0;
+  return 0;
 }
