@@ -28,6 +28,10 @@ typedef std::vector<float> Plane;
 // How many samples took each arm of each value branch of the butteraugli chain since the
 // last orc_branch_census_reset().  Counting only: no arm's arithmetic depends on it.  The
 // tests use it to show that their inputs reach every arm (tests/test_value_domain.py).
+// The search_* / search420_* arms are phase A's (orc_block_zeroing_orders[_masked]): the
+// greedy selection, the monotone minimum, the cut at the block error limit, the clamps of the
+// IDCT and the colour transform as the search's candidates meet them, and the plain counter
+// search_evaluations = CompareBlock calls made by the search loops (tests/test_search_domain.py).
 #define GZ_CENSUS_ARMS(X)                                                                  \
   X(gamma_yq_zero) X(gamma_yq_nonzero) X(gamma_nonfinite)                                  \
   X(mf_x_remove_range_above) X(mf_x_remove_range_below) X(mf_x_remove_range_inside)        \
@@ -44,7 +48,23 @@ typedef std::vector<float> Plane;
   X(same_noise_clamp0) X(same_noise_clamp1) X(same_noise_no_clamp)                         \
   X(diff_precompute_cutoff) X(diff_precompute_below_cutoff)                                \
   X(lut_index_negative) X(lut_index_top) X(lut_index_inside)                               \
-  X(combine_linear) X(combine_sqrt)
+  X(combine_linear) X(combine_sqrt)                                                        \
+  X(search_lookahead_first_wins) X(search_lookahead_later_wins)                            \
+  X(search_lookahead_tie_kept_first)                                                       \
+  X(search_err_zero) X(search_err_positive)                                                \
+  X(search_tries_below_lookahead)                                                          \
+  X(search_min_from_end_lowers) X(search_min_from_end_keeps)                               \
+  X(search_list_empty) X(search_list_cut) X(search_list_cut_to_nothing)                    \
+  X(search_list_kept_whole) X(search_list_has_189)                                         \
+  X(search_err_equals_limit)                                                               \
+  X(search_idct_pixel_clamped_low) X(search_idct_pixel_clamped_high)                       \
+  X(search_idct_pixel_inside)                                                              \
+  X(search_rgb_clamped_low) X(search_rgb_clamped_high) X(search_rgb_inside)                \
+  X(search_rank_equal_scores)                                                              \
+  X(search420_subblock_outside_image)                                                      \
+  X(search420_subblock_outside_right) X(search420_subblock_outside_below)                  \
+  X(search420_max_from_later_subblock)                                                     \
+  X(search_evaluations)
 enum CensusArm {
 #define X(n) kArm_##n,
   GZ_CENSUS_ARMS(X)
@@ -58,6 +78,17 @@ const char* const kCensusNames[kArmCount] = {
 };
 unsigned long long g_census[kArmCount];
 inline void tick(int arm) { ++g_census[arm]; }
+// The search_* clamp arms count only what phase A's loops run (the IDCT and the colour
+// transform serve every other path too).
+int g_in_search = 0;
+struct InSearch {
+  InSearch() { ++g_in_search; }
+  ~InSearch() { --g_in_search; }
+};
+// (`first`: the census entry of the low arm -- high, inside follow)
+inline void tick_clamp(int first, int v) {
+  if (g_in_search) tick(first + (v < 0 ? 0 : v > 255 ? 1 : 2));
+}
 
 // ===================================================================== block path ==
 
@@ -154,9 +185,15 @@ inline void fdct_row(int16_t* in, const int16_t* t) {
 inline uint8_t clamp255(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 inline void ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {
   const int half = 1 << 15;
-  rgb[0] = clamp255(y + ((91881 * (cr - 128) + half) >> 16));
-  rgb[1] = clamp255(y + ((-46802 * (cr - 128) + (-22554 * (cb - 128) + half)) >> 16));
-  rgb[2] = clamp255(y + ((116130 * (cb - 128) + half) >> 16));
+  const int r = y + ((91881 * (cr - 128) + half) >> 16);
+  const int g = y + ((-46802 * (cr - 128) + (-22554 * (cb - 128) + half)) >> 16);
+  const int b = y + ((116130 * (cb - 128) + half) >> 16);
+  tick_clamp(kArm_search_rgb_clamped_low, r);
+  tick_clamp(kArm_search_rgb_clamped_low, g);
+  tick_clamp(kArm_search_rgb_clamped_low, b);
+  rgb[0] = clamp255(r);
+  rgb[1] = clamp255(g);
+  rgb[2] = clamp255(b);
 }
 
 // ref: gamma_correct.cc:23-38
@@ -981,6 +1018,27 @@ double compare_block(const BlockSearch* bs, const int16_t* block192) {
   return sqrt(diff);
 }
 
+// ---- phase A's census (counting only) ----
+typedef std::vector<std::pair<int, float> > ScoredList;
+inline void census_ranked(const ScoredList& v) {
+  for (size_t i = 1; i < v.size(); ++i)
+    if (v[i].second == v[i - 1].second) tick(kArm_search_rank_equal_scores);
+}
+inline void census_evaluation(float e) {
+  tick(kArm_search_evaluations);
+  tick(e == 0.0f ? kArm_search_err_zero : kArm_search_err_positive);
+}
+inline void census_step(size_t left, int lookahead, int best_i) {
+  tick(best_i == 0 ? kArm_search_lookahead_first_wins : kArm_search_lookahead_later_wins);
+  if (left < (size_t)lookahead) tick(kArm_search_tries_below_lookahead);
+}
+// (empty: the block has no candidate at all; cut: the error limit keeps fewer than there are, down to none)
+inline void census_list(size_t size, size_t num) {
+  tick(size == 0 ? kArm_search_list_empty : num < size ? kArm_search_list_cut : kArm_search_list_kept_whole);
+  if (size > 0 && num == 0) tick(kArm_search_list_cut_to_nothing);
+  if (size == 189) tick(kArm_search_list_has_189);
+}
+
 void init_block_search(BlockSearch* bs, const Comparator* c) {
   bs->cmp = c;
   bs->mask.resize((size_t)3 * c->w * c->h);
@@ -1008,8 +1066,11 @@ void orc_idct_block(const int16_t* block, uint8_t* out) {
   for (int y = 0; y < 8; ++y) {
     int t[8];
     idct_1d(cols + 8 * y, 1, t);
-    for (int x = 0; x < 8; ++x)
-      out[8 * y + x] = clamp255((t[x] + (257 << 17)) >> 18);
+    for (int x = 0; x < 8; ++x) {
+      const int v = (t[x] + (257 << 17)) >> 18;
+      tick_clamp(kArm_search_idct_pixel_clamped_low, v);
+      out[8 * y + x] = clamp255(v);
+    }
   }
 }
 
@@ -1311,6 +1372,7 @@ int orc_block_zeroing_orders(void* p, const int16_t* coeffs, const int16_t* orig
   const int bw = (c->w + 7) / 8, bh = (c->h + 7) / 8, nb = bw * bh;
   BlockSearch bs;
   init_block_search(&bs, c);
+  InSearch in_search;
   static const uint8_t oldCsf[64] = {
       10, 10, 20, 40, 60, 70, 80, 90, 10, 20, 30, 60, 70, 80, 90, 90,
       20, 30, 60, 70, 80, 90, 90, 90, 40, 60, 70, 80, 90, 90, 90, 90,
@@ -1347,6 +1409,7 @@ int orc_block_zeroing_orders(void* p, const int16_t* coeffs, const int16_t* orig
       std::sort(input_order.begin(), input_order.end(),
                 [](const std::pair<int, float>& a, const std::pair<int, float>& b) {
                   return a.second < b.second; });
+      census_ranked(input_order);
       int16_t processed[192];
       memcpy(processed, block, sizeof(processed));
       switch_block(&bs, bx, by);
@@ -1361,13 +1424,17 @@ int orc_block_zeroing_orders(void* p, const int16_t* coeffs, const int16_t* orig
           float max_err = 0;
           if (8 * bx < c->w && 8 * by < c->h) {
             const float e = static_cast<float>(compare_block(&bs, cand));
+            census_evaluation(e);
             max_err = std::max(max_err, e);
           }
           if (max_err < best_err) {
             best_err = max_err;
             best_i = (int)i;
+          } else if (max_err == best_err) {
+            tick(kArm_search_lookahead_tie_kept_first);
           }
         }
+        census_step(input_order.size(), lookahead, best_i);
         const int ci = input_order[best_i].first;
         processed[ci] = 0;
         input_order.erase(input_order.begin() + best_i);
@@ -1376,10 +1443,15 @@ int orc_block_zeroing_orders(void* p, const int16_t* coeffs, const int16_t* orig
       float min_err = 1e10;
       for (int i = (int)out.size() - 1; i >= 0; --i) {
         min_err = std::min(min_err, out[i].second);
+        tick(out[i].second > min_err ? kArm_search_min_from_end_lowers : kArm_search_min_from_end_keeps);
         out[i].second = min_err;
       }
       size_t num = 0;
-      while (num < out.size() && out[num].second <= c->target) ++num;
+      while (num < out.size() && out[num].second <= c->target) {
+        if (out[num].second == c->target) tick(kArm_search_err_equals_limit);
+        ++num;
+      }
+      census_list(out.size(), num);
       offsets[bix] = total;
       for (size_t i = 0; i < num; ++i) {
         if (total < cap) {
@@ -1775,6 +1847,7 @@ int orc_block_zeroing_orders_masked(void* p, const int16_t* coeffs, const int16_
   const int gw = (c->w + 8 * factor - 1) / (8 * factor), gh = (c->h + 8 * factor - 1) / (8 * factor);
   BlockSearch bs;
   init_block_search(&bs, c);
+  InSearch in_search;
   static const uint8_t oldCsf[64] = {
       10, 10, 20, 40, 60, 70, 80, 90, 10, 20, 30, 60, 70, 80, 90, 90,
       20, 30, 60, 70, 80, 90, 90, 90, 40, 60, 70, 80, 90, 90, 90, 90,
@@ -1815,6 +1888,7 @@ int orc_block_zeroing_orders_masked(void* p, const int16_t* coeffs, const int16_
       std::sort(input_order.begin(), input_order.end(),
                 [](const std::pair<int, float>& a, const std::pair<int, float>& b) {
                   return a.second < b.second; });
+      census_ranked(input_order);
       int16_t processed[192];
       memcpy(processed, block, sizeof(processed));
       // SwitchBlock: the original's opsin image of every sub-block
@@ -1837,20 +1911,31 @@ int orc_block_zeroing_orders_masked(void* p, const int16_t* coeffs, const int16_
           cand[input_order[i].first] = 0;
           set_blocks(cand);
           float max_err = 0;
+          bool first_sub = true;
           for (int oy = 0, s = 0; oy < factor; ++oy)
             for (int ox = 0; ox < factor; ++ox, ++s) {
               const int bxx = bx * factor + ox, byy = by * factor + oy;
               if (8 * bxx < c->w && 8 * byy < c->h) {
                 memcpy(bs.orig_xyb, sub_xyb[s].data(), sizeof(bs.orig_xyb));
                 const float e = static_cast<float>(compare_block_image(&bs, img, bxx, byy));
+                census_evaluation(e);
+                if (!first_sub && e > max_err) tick(kArm_search420_max_from_later_subblock);
+                first_sub = false;
                 max_err = std::max(max_err, e);
+              } else {
+                tick(kArm_search420_subblock_outside_image);
+                if (8 * bxx >= c->w) tick(kArm_search420_subblock_outside_right);
+                if (8 * byy >= c->h) tick(kArm_search420_subblock_outside_below);
               }
             }
           if (max_err < best_err) {
             best_err = max_err;
             best_i = (int)i;
+          } else if (max_err == best_err) {
+            tick(kArm_search_lookahead_tie_kept_first);
           }
         }
+        census_step(input_order.size(), lookahead, best_i);
         const int ci = input_order[best_i].first;
         processed[ci] = 0;
         input_order.erase(input_order.begin() + best_i);
@@ -1860,10 +1945,15 @@ int orc_block_zeroing_orders_masked(void* p, const int16_t* coeffs, const int16_
       float min_err = 1e10;
       for (int i = (int)out.size() - 1; i >= 0; --i) {
         min_err = std::min(min_err, out[i].second);
+        tick(out[i].second > min_err ? kArm_search_min_from_end_lowers : kArm_search_min_from_end_keeps);
         out[i].second = min_err;
       }
       size_t num = 0;
-      while (num < out.size() && out[num].second <= c->target) ++num;
+      while (num < out.size() && out[num].second <= c->target) {
+        if (out[num].second == c->target) tick(kArm_search_err_equals_limit);
+        ++num;
+      }
+      census_list(out.size(), num);
       offsets[bix] = total;
       for (size_t i = 0; i < num; ++i) {
         if (total < cap) {

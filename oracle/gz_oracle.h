@@ -49,6 +49,10 @@ double orc_diffmap(const float* rgb0, const float* rgb1, int w, int h, float* di
 /* ---- branch census: samples per arm of every value branch of the stages above since the last
  * reset (remove_range, amplify_range, maximum_clamp, the Malta and L2DiffAsymmetric ladders,
  * the SameNoiseLevels clamps, DiffPrecompute's cutoff, the mask LUT's ends, the sqrt stage).
+ * The search_* / search420_* arms are phase A's, counted by orc_block_zeroing_orders[_masked]: which look-ahead
+ * candidate wins and ties kept, errors of exactly 0, the monotone minimum, the cut at the error limit, the clamps
+ * of the IDCT and the colour transform inside the search, equal ranking scores, 4:2:0 sub-blocks outside the image;
+ * search_evaluations is a plain counter of the CompareBlock calls the search loops make.
  * orc_branch_census fills out[0..n) and returns the number of arms. ---- */
 int  orc_branch_census(unsigned long long* out, int n);
 const char* orc_branch_census_name(int i);

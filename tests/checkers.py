@@ -233,6 +233,14 @@ class Checker:
     def census(self):
         """{arm: samples that took it since census_reset()} for every value branch of the
         butteraugli stages (oracle/gz_oracle.h)."""
+        return {k: v for k, v in self._census_all().items() if not k.startswith("search")}
+
+    def search_census(self):
+        """The same for phase A's arms (search_*, search420_*; search_evaluations is a plain counter
+        of the CompareBlock calls the search loops made): orc_block_zeroing_orders[_masked]."""
+        return {k: v for k, v in self._census_all().items() if k.startswith("search")}
+
+    def _census_all(self):
         n = self._branch_census(None, 0)
         a = np.zeros(n, np.uint64)
         self._branch_census(_ptr(a), n)

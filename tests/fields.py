@@ -6,7 +6,12 @@ of samples (the oracle's branch census checks that: tests/test_value_domain.py).
 
 `originals(w, h)` gives uint8 [h][w][3] images; `candidates(rgb)` gives, for one original, float32
 [3][h][w] LINEAR planes in [0, 255] (what gz_probe_opsin / gz_probe_diffmap take); `pairs(w, h)`
-walks every (original, candidate) pair as linear planes."""
+walks every (original, candidate) pair as linear planes.
+
+`search_cases(w, h)` / `search_cases_420(w, h)` are the inputs of phase A, the block search: an original image, the
+coefficients the ranking reads, the candidate's coefficients, a target and the search's parameters."""
+import typing
+
 import numpy as np
 
 import images
@@ -147,3 +152,160 @@ def pairs(w, h, only=None):
         lin0 = linear(rgb)
         for cname, lin1 in candidates(rgb).items():
             yield f"{oname}/{cname}", rgb, lin0, lin1
+
+
+# ------------------------------------------------------------ phase A: the block search --
+# Inputs of gz_block_zeroing_orders[_masked] beyond a photograph against its mildly quantised copy
+# (tests/test_search_domain.py counts, with the oracle's search census, which arms of the search each
+# family takes).  Coefficient arrays come from the oracle's encode_rgb / reconstruct.
+class SearchCase(typing.NamedTuple):
+    name: str
+    rgb: np.ndarray        # uint8 [h][w][3]: the context's original image
+    orig: np.ndarray       # int16: what the ranking scores read (gz_set_orig_coeffs where it is not rgb's own)
+    cand: np.ndarray       # int16: the candidate the search starts from (gz_set_coeffs)
+    target: float
+    lookahead: int = 3
+    new_model: bool = True
+    comp_mask: int = 7
+    foreign: bool = False  # orig is not what the library derives from rgb (gz_encode_rgb, gz_downsample)
+
+
+TARGET = 0.971769
+# The largest coefficient magnitude the search cases use: the whole int16 range, 32767 and -32768.  The reference's
+# integer IDCT sums eight products of a coefficient with a constant of up to 11363 in an int, so from eight
+# coefficients of about 2^15 on the sum passes 2^31, which C++ leaves undefined.  As compiled here the oracle and
+# the unmodified reference both wrap, and they agree bit for bit on every case below at this magnitude (checked at
+# 2^15, 2^14 and 2^13; tests/test_oracle_vs_ref.py::test_search_domain_oracle_equals_reference keeps checking it
+# where oracle/_ref is built), so nothing was shrunk.  Should a compiler make the two disagree, this is the bound to
+# lower, to the largest power of two at which they agree again.
+EXTREME = 1 << 15
+
+
+def _quantised(co, w, h, q):
+    return oracle.reconstruct(co, w, h, np.broadcast_to(np.asarray(q, np.int32), (3, 64)).copy())[0]
+
+
+def extremes(co, mag=EXTREME):
+    """mag - 1 or -mag in every AC position of every third block, the signs by position; the other blocks are co's.
+    mag = EXTREME = 2^15 is the bound up to which the oracle and the unmodified reference agree (the note above)."""
+    out = co.copy()
+    k = np.arange(64)
+    val = np.where(((k & 7) + (k >> 3)) & 1, -(mag - 1), mag - 1)
+    val[k % 5 == 0] = -mag
+    val = val.astype(np.int16)
+    out[:, ::3, 1:] = val[1:]
+    return out
+
+
+def sparse_wide(co, rng, mag=EXTREME):
+    """Uniform over [-mag, mag) with 60 % zeros (DC included: a DC far outside [0, 255] saturates whole blocks)."""
+    out = rng.integers(-mag, mag, size=co.shape).astype(np.int16)
+    out[rng.random(co.shape) < 0.6] = 0
+    return out
+
+
+def matrix_quantiser():
+    """A per-coefficient quantiser as parity_cases.case_jpeg_entropy draws one: luma 1..8, chroma 1..29."""
+    rng = np.random.default_rng(SEED + 31)
+    return np.stack([rng.integers(1, 9, 64), rng.integers(1, 30, 64), rng.integers(1, 30, 64)]).astype(np.int32)
+
+
+def search_originals(w, h):
+    import parity_cases
+    o = originals(w, h)
+    o["colourful"] = parity_cases.colourful(w, h)
+    return o
+
+
+def search_cases(w, h, only=None):
+    """SearchCase tuples for a 4:4:4 frame of w x h; `only`: the families to walk (the part of the name before the
+    first slash)."""
+    def want(family):
+        return only is None or family in only
+    imgs = search_originals(w, h)
+    co = {}
+
+    def coeffs(name):
+        if name not in co:
+            co[name] = oracle.encode_rgb(imgs[name])
+        return co[name]
+
+    if want("field"):
+        for name, rgb in imgs.items():
+            yield SearchCase(f"field/{name}", rgb, coeffs(name), _quantised(coeffs(name), w, h, 2), TARGET)
+    if want("target"):
+        for t in (0.3, 3.0):
+            yield SearchCase(f"target/noise/{t}", imgs["noise"], coeffs("noise"), coeffs("noise").copy(), t)
+    if want("zero_error"):
+        rng = np.random.default_rng(5)
+        for name in ("white", "black", "grey"):
+            cand = coeffs(name).copy()
+            hit = rng.random(cand.shape) < 0.05
+            hit[:, :, 0] = False
+            tiny = (rng.integers(1, 4, cand.shape) * rng.choice([-1, 1], cand.shape)).astype(np.int16)
+            cand[hit] = tiny[hit]
+            yield SearchCase(f"zero_error/{name}", imgs[name], coeffs(name), cand, TARGET)
+    photo, pco = imgs["photo_zero_rect"], None
+    if want("saturating") or want("foreign_orig") or want("matrix"):
+        pco = coeffs("photo_zero_rect")
+    if want("saturating"):
+        x4 = np.clip(pco.astype(np.int32) * 4, -32768, 32767).astype(np.int16)
+        yield SearchCase("saturating/x4", photo, pco, x4, TARGET)
+        rng = np.random.default_rng(SEED + 2040)
+        wild = rng.integers(-2040, 2041, size=pco.shape).astype(np.int16)
+        for t in (50.0, 500.0):
+            yield SearchCase(f"saturating/uniform2040/{t}", photo, pco, wild, t)
+        yield SearchCase("saturating/extremes/500.0", photo, pco, extremes(pco), 500.0)
+        sw = sparse_wide(pco, np.random.default_rng(SEED + 16384))
+        for t in (50.0, 500.0):
+            yield SearchCase(f"saturating/sparse_wide/{t}", photo, pco, sw, t)
+    if want("foreign_orig"):
+        cand = _quantised(pco, w, h, 2)
+        yield SearchCase("foreign_orig/noise", photo, coeffs("noise"), cand, TARGET, foreign=True)
+        ext = extremes(pco)   # (as orig it is only scored, abs(-32768) included, never transformed)
+        yield SearchCase("foreign_orig/extremes", photo, ext, cand, TARGET, foreign=True)
+        yield SearchCase("foreign_orig/extremes/old_model", photo, ext, cand, TARGET, new_model=False, foreign=True)
+    if want("matrix"):
+        yield SearchCase("matrix/photo_zero_rect", photo, pco, _quantised(pco, w, h, matrix_quantiser()), TARGET)
+    if want("params"):
+        for name in ("noise", "discs", "primaries", "checker1"):
+            cand = _quantised(coeffs(name), w, h, 2)
+            for mask in (1, 6):
+                yield SearchCase(f"params/{name}/mask{mask}", imgs[name], coeffs(name), cand, TARGET, comp_mask=mask)
+            yield SearchCase(f"params/{name}/lookahead5/old_model", imgs[name], coeffs(name), cand, TARGET,
+                             lookahead=5, new_model=False)
+        cand = _quantised(coeffs("noise"), w, h, 2)
+        for la in (1, 7):   # (7 is no multiple of the kernel's batch of three: the last batch is partial)
+            yield SearchCase(f"params/noise/lookahead{la}", imgs["noise"], coeffs("noise"), cand, TARGET, lookahead=la)
+
+
+SEARCH_FIELDS_420 = ("ramp", "primaries", "noise", "colourful", "photo_zero_rect")
+
+
+def search_cases_420(w, h, only=None):
+    """SearchCase tuples on the 4:2:0 frame of w x h (orig = the oracle's downsample of the original, cand = its
+    quantised coefficients; frame layout: luma blocks, Cb, Cr), component masks 1 and 6.  Grey fields have no
+    chroma candidates and appear under mask 1 only."""
+    imgs = search_originals(w, h)
+    nb = ((w + 7) // 8) * ((h + 7) // 8)
+    for name in SEARCH_FIELDS_420:
+        if only is not None and name not in only:
+            continue
+        orig = oracle.downsample(oracle.encode_rgb(imgs[name]), w, h)
+        cand = oracle.reconstruct420(orig, w, h, np.full((3, 64), 2, np.int32))[0]
+        for t in (TARGET, 3.0):
+            for mask in (1, 6):
+                yield SearchCase(f"420/{name}/{t}/mask{mask}", imgs[name], orig, cand, t, comp_mask=mask)
+    if only is None or "white" in only:
+        # (the reference leaves a grey image's frame 4:4:4: its 4:2:0 frame is put together here, chroma all zero,
+        #  and goes in through gz_set_orig_coeffs_420)
+        nbc = ((w + 15) // 16) * ((h + 15) // 16)
+        orig = np.concatenate([oracle.encode_rgb(imgs["white"])[0], np.zeros((2 * nbc, 64), np.int16)])
+        rng = np.random.default_rng(5)
+        cand = orig.copy()
+        hit = rng.random(cand.shape) < 0.05
+        hit[:, 0] = False
+        hit[nb:] = False
+        tiny = (rng.integers(1, 4, cand.shape) * rng.choice([-1, 1], cand.shape)).astype(np.int16)
+        cand[hit] = tiny[hit]
+        yield SearchCase("420/white/tiny_ac/mask1", imgs["white"], orig, cand, TARGET, comp_mask=1, foreign=True)

@@ -636,14 +636,21 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
     oc.close()
 
 
-def case_compare_blocks(L, w, h, x0=0, y0=0, qs=3, n=24):
-    """gz_compare_blocks == Comparator::SwitchBlock + CompareBlock (the per-block seam)."""
+def case_compare_blocks(L, w, h, x0=0, y0=0, qs=3, n=24, case=None, expect_zero=False):
+    """gz_compare_blocks == Comparator::SwitchBlock + CompareBlock (the per-block seam).  With `case` (a
+    fields.SearchCase) the image, the target and the candidate coefficients are the case's, not the photograph's and
+    its quantised copy, and every block of the bottom row and of the right column is evaluated as well."""
     rng = np.random.default_rng(RNG_SEED + 17 * w + h)
-    rgb = images.crop(w, h, x0, y0)
-    oc = oracle.comparator(rgb, 0.971769)
-    with L.context(rgb, 0.971769) as ctx:
+    rgb = images.crop(w, h, x0, y0) if case is None else case.rgb
+    target = 0.971769 if case is None else case.target
+    oc = oracle.comparator(rgb, target)
+    with L.context(rgb, target) as ctx:
         ctx.encode_rgb()
-        cq = ctx.quantize(np.full((3, 64), qs, np.int32))
+        if case is None:
+            cq = ctx.quantize(np.full((3, 64), qs, np.int32))
+        else:
+            cq = np.ascontiguousarray(case.cand, np.int16)
+            ctx.set_coeffs(cq)
         bw = ctx.bw
         xy, blocks, exp = [], [], []
         for _ in range(n):
@@ -651,11 +658,24 @@ def case_compare_blocks(L, w, h, x0=0, y0=0, qs=3, n=24):
             cand = cq.copy()
             for _ in range(int(rng.integers(0, 4))):   # zero a few coefficients of the block
                 cand[int(rng.integers(0, 3)), b, int(rng.integers(1, 64))] = 0
+            if case is not None and len(xy) % 3:       # ... or, as the search does on its way, about half or all
+                gone = rng.random((3, 64)) < (0.5, 1.0)[len(xy) % 3 - 1]
+                gone[:, 0] = False
+                cand[:, b, :][gone] = 0
             xy.append((b % bw, b // bw))
             blocks.append(cand[:, b, :])
             exp.append(oc.compare_block(cand, b % bw, b // bw))
+        if case is not None:   # the ragged edges: the bottom row and the right column, as they stand
+            edge = [(bx, ctx.bh - 1) for bx in range(bw)] + [(bw - 1, by) for by in range(ctx.bh - 1)]
+            for bx, by in edge:
+                xy.append((bx, by))
+                blocks.append(cq[:, by * bw + bx, :])
+                exp.append(oc.compare_block(cq, bx, by))
+        what = "" if case is None else f" of {case.name}"
         got = ctx.compare_blocks(np.array(xy), np.stack(blocks))
-        assert_bits_equal(got, np.array(exp, np.float64), "CompareBlock")
+        assert_bits_equal(got, np.array(exp, np.float64), "CompareBlock" + what)
+        if expect_zero:
+            assert (np.array(exp) == 0.0).any(), f"no block error{what} is exactly 0.0"
         # the pixel form of the seam (gz_compare_block_pixels): the windows' YCbCr pixels are the
         # integer IDCT of their blocks, edge-replicated as OutputImageComponent::ToPixels does
         px = L.idct_blocks(np.stack(blocks).reshape(-1, 64)).reshape(-1, 3, 8, 8)
@@ -664,8 +684,97 @@ def case_compare_blocks(L, w, h, x0=0, y0=0, qs=3, n=24):
             px[i, :, :, vw:] = px[i, :, :, vw - 1:vw]
             px[i, :, vh:, :] = px[i, :, vh - 1:vh, :]
         got_px = ctx.compare_block_pixels(np.array(xy), px.reshape(-1, 3, 64))
-        assert_bits_equal(got_px, np.array(exp, np.float64), "CompareBlock (pixels)")
+        assert_bits_equal(got_px, np.array(exp, np.float64), "CompareBlock (pixels)" + what)
     oc.close()
+
+
+# --------------------------------------------- phase A on the search cases (tests/fields.py) --
+_search_expected = {}
+
+
+def search_expected(case, w, h, frame420=False):
+    """The oracle's (offsets, indices, errors, census) of one fields.SearchCase: computed once per process and
+    shared by the tests that need it (callers leave the arrays unchanged)."""
+    key = (case.name, w, h, frame420)
+    if key not in _search_expected:
+        oc = oracle.comparator(case.rgb, case.target)
+        oracle.census_reset()
+        if frame420 or case.comp_mask != 7:
+            r = oc.block_zeroing_orders_masked(case.cand, case.orig, frame420, case.comp_mask, case.lookahead,
+                                               case.new_model)
+        else:
+            r = oc.block_zeroing_orders(case.cand, case.orig, case.lookahead, case.new_model)
+        census = oracle.search_census()
+        oc.close()
+        for a in r:
+            a.setflags(write=False)
+        _search_expected[key] = r + (census,)
+    return _search_expected[key]
+
+
+def _check_search(ctx, case, w, h, frame420):
+    off, idx, err = ctx.block_zeroing_orders(case.lookahead, case.new_model, comp_mask=case.comp_mask)
+    eoff, eidx, eerr, census = search_expected(case, w, h, frame420)
+    assert_bits_equal(off, eoff, f"candidate offsets of {case.name}")
+    assert_bits_equal(idx, eidx, f"candidate coefficient indices of {case.name}")
+    assert_bits_equal(err, eerr, f"candidate errors of {case.name}")
+    assert ctx.search_evaluations() == census["search_evaluations"], case.name
+
+
+def case_search_domain(L, w, h, only=None):
+    """gz_block_zeroing_orders[_masked] on every search case of a 4:4:4 frame (tests/fields.py: search_cases)
+    against the oracle, bit for bit: offsets, candidate indices, errors; and gz_search_evaluations against the number
+    of CompareBlock calls the oracle's search loops made.  The original coefficients are the image's own
+    (gz_encode_rgb) or, where the case says so, foreign ones (gz_set_orig_coeffs: the JPEG-input path)."""
+    import fields
+    n = 0
+    for case in fields.search_cases(w, h, only):
+        with L.context(case.rgb, case.target) as ctx:
+            co = ctx.encode_rgb()
+            if case.foreign:
+                ctx.set_orig_coeffs(case.orig)
+            else:
+                assert_bits_equal(co, case.orig, f"encode_rgb of {case.name}")
+            ctx.set_coeffs(case.cand)
+            _check_search(ctx, case, w, h, False)
+        n += 1
+    assert n > 0, only
+
+
+def case_search_domain_420(L, w, h, only=None):
+    """The same on the 4:2:0 frame (search_cases_420), component masks 1 and 6: the original's coefficients come
+    from gz_downsample (and must be the oracle's) or go in through gz_set_orig_coeffs_420, case by case in turn."""
+    import fields
+    n = 0
+    for case in fields.search_cases_420(w, h, only):
+        with L.context(case.rgb, case.target) as ctx:
+            ctx.encode_rgb(download=False)
+            if case.foreign or n & 1:
+                ctx.set_orig_coeffs_420(case.orig)
+            else:
+                assert_bits_equal(ctx.downsample(), case.orig, f"downsample of {case.name}")
+            ctx.set_coeffs(case.cand)
+            _check_search(ctx, case, w, h, True)
+        n += 1
+    assert n > 0, only
+
+
+# The candidates the seam is run on: one case per distinct candidate array of the zero_error, saturating (x4 and
+# uniform) and foreign_orig families (the seam reads neither the target's cut nor the original coefficients).
+SEAM_CASES = ("zero_error/white", "zero_error/black", "zero_error/grey", "saturating/x4",
+              "saturating/uniform2040/500.0", "foreign_orig/noise")
+
+
+def case_compare_blocks_on_search_domain(L, w, h):
+    """The per-block seam, coefficient form and pixel form, on candidates of the search cases: 24 random blocks and
+    the bottom row and right column of each; on flat white with tiny AC values some errors are exactly 0.0."""
+    import fields
+    ran = []
+    for case in fields.search_cases(w, h, ("zero_error", "saturating", "foreign_orig")):
+        if case.name in SEAM_CASES:
+            case_compare_blocks(L, w, h, case=case, expect_zero=case.name == "zero_error/white")
+            ran.append(case.name)
+    assert sorted(ran) == sorted(SEAM_CASES), ran
 
 
 # ------------------------------------------------ value-domain fields (tests/fields.py) --

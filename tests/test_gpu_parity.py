@@ -418,6 +418,34 @@ def test_compare_blocks(L):
     pc.case_compare_blocks(L, 200, 120, x0=100, y0=60, n=200)
 
 
+SEARCH_FAMILIES = ("field", "target", "zero_error", "saturating", "foreign_orig", "matrix", "params")
+
+
+@pytest.mark.parametrize("family", SEARCH_FAMILIES)
+def test_search_domain(L, family):
+    """Phase A on the search cases of tests/fields.py (synthetic fields, targets that cut every list and none,
+    errors that are exactly 0.0, coefficients up to the int16 extremes, original coefficients foreign to the
+    candidate, a quantiser matrix, component masks and look-aheads) against the oracle, bit for bit, and
+    gz_search_evaluations against the oracle's count.  93x59: 12x8 blocks, 5 ragged columns, 3 ragged rows, two
+    ranking workgroups."""
+    pc.case_search_domain(L, 93, 59, only=(family,))
+
+
+def test_search_domain_covers_every_family():
+    import fields
+    assert {c.name.split("/")[0] for c in fields.search_cases(93, 59)} == set(SEARCH_FAMILIES)
+
+
+def test_search_domain_420(L):
+    """The same on a 4:2:0 frame, masks 1 and 6.  85x53: luma grid 11x7, odd on both axes, so the corner chroma cell
+    (grid 6x4) has three of its four sub-blocks outside the image."""
+    pc.case_search_domain_420(L, 85, 53)
+
+
+def test_compare_blocks_on_search_domain(L):
+    pc.case_compare_blocks_on_search_domain(L, 93, 59)
+
+
 def test_block_search_bees(L):
     """Phase A on the whole BASELINE config-1 image (1848 blocks, ~300k CompareBlock
     evaluations) against the oracle, bit for bit."""

@@ -246,3 +246,21 @@ def test_device_math_driver_on_a_strided_sweep(L, tmp_path):
     """The driver of the device-side math check against the emulation build: validates the harness
     (inputs, plain forms, the probe's plumbing) where no GPU is; the reciprocal here is the emulated one."""
     pc.case_device_math(L.path, tmp_path, stride=4099, timeout=300)
+
+
+# ------------------------------------------------ phase A on the search cases (tests/fields.py) --
+# The `params` family (component masks 1 and 6 and look-aheads 1, 5 and 7 on four fields: 45 s here, most of it
+# the look-aheads on noise) is left to the GPU suite; test_block_search_masks_and_params above runs masks and
+# look-aheads through the emulation on the photograph.  Every other family runs here, one test each.
+@pytest.mark.parametrize("family", ["field", "target", "zero_error", "saturating", "foreign_orig", "matrix"])
+def test_search_domain(L, family):
+    """gz_block_zeroing_orders[_masked] on the search cases at the GPU suite's size."""
+    pc.case_search_domain(L, 93, 59, only=(family,))
+
+
+def test_search_domain_420(L):
+    pc.case_search_domain_420(L, 85, 53)
+
+
+def test_compare_blocks_on_search_domain(L):
+    pc.case_compare_blocks_on_search_domain(L, 93, 59)

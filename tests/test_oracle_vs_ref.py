@@ -365,3 +365,24 @@ def test_value_domain_fields_comparator_oracle_equals_reference():
             assert od == rd
         oc.close()
         rc.close()
+
+
+def test_search_domain_oracle_equals_reference():
+    """Every search case of tests/fields.py at the GPU suite's sizes (93x59, 4:4:4; 85x53, 4:2:0) through the
+    unmodified reference's ComputeBlockZeroingOrder loop against the oracle's: offsets, indices and errors bit for
+    bit -- coefficients at the int16 extremes included, where the reference's integer IDCT overflows its int sums
+    (fields.EXTREME says what to do should the two ever disagree there)."""
+    import fields
+    import parity_cases as pc
+    for (w, h), gen, f420 in (((93, 59), fields.search_cases, False), ((85, 53), fields.search_cases_420, True)):
+        for case in gen(w, h):
+            rc = ref.comparator(case.rgb, case.target)
+            if f420 or case.comp_mask != 7:
+                got = rc.block_zeroing_orders_masked(case.cand, case.orig, f420, case.comp_mask, case.lookahead,
+                                                     case.new_model)
+            else:
+                got = rc.block_zeroing_orders(case.cand, case.orig, case.lookahead, case.new_model)
+            rc.close()
+            exp = pc.search_expected(case, w, h, f420)
+            for g, e, what in zip(got, exp, ("offsets", "indices", "errors")):
+                assert_bits_equal(g, e, f"{what} of {case.name}")
