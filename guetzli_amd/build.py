@@ -134,7 +134,8 @@ def _run(cmd, verbose):
 
 HOST_DIR = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
-HOST_SOURCES = ["jpeg_reader.cc", "jpeg_writer.cc", "png_reader.cc", "processor.cc", "silver_screen.cc"]
+HOST_SOURCES = ["jpeg_reader.cc", "jpeg_writer.cc", "png_reader.cc", "processor.cc", "candidate.cc", "phase_b.cc",
+                "gzh_wrapper.cc", "silver_screen.cc"]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", "-Wextra",
               "-Wno-unused-parameter"]
 

@@ -1,0 +1,208 @@
+// The C wrapper of the host driver (ctypes: guetzli_amd/encoder.py) and the test hooks of its pieces.
+#include <string.h>
+
+#include <algorithm>
+#include <exception>
+
+#include "jpeg_reader.h"
+#include "jpeg_writer.h"
+#include "parallel.h"
+#include "png_reader.h"
+#include "processor.h"
+#include "reader_dump.h"
+
+extern "C" {
+
+// Every entry point below catches what the C++ underneath may throw (std::bad_alloc on a huge
+// declared image, ...): nothing propagates through the C boundary.  Return values: >= 0 the
+// size of the result (copied only if it fits the caller's buffer: a larger size asks for a
+// retry with that much room), -1 failure (message on stderr), -2 exception.
+#define GZH_GUARD_BEGIN try {
+#define GZH_GUARD_END                                                        \
+  } catch (const std::exception& e) {                                        \
+    fprintf(stderr, "guetzli_amd: %s\n", e.what());                          \
+    return -2;                                                               \
+  } catch (...) {                                                            \
+    fprintf(stderr, "guetzli_amd: unknown exception\n");                     \
+    return -2;                                                               \
+  }
+
+static void CopyText(const std::string& s, char* dst, long cap) {
+  if (!dst || cap <= 0) return;
+  const size_t n = std::min<size_t>(s.size(), (size_t)cap - 1);
+  memcpy(dst, s.data(), n);
+  dst[n] = 0;
+}
+
+// guetzli::Process with every field of Params.  jpeg_len < 0: `data` is packed RGB of w x h,
+// otherwise JPEG bytes.  quality < 0: `target` is the butteraugli target directly.
+// iparams: device, clear_metadata, try_420, force_420, use_silver_screen,
+// zeroing_greedy_lookahead, new_zeroing_model.
+long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double quality,
+                        float target, const int* iparams, uint8_t* out, long cap, char* trace,
+                        long trace_cap, char* timers, long timers_cap) {
+  GZH_GUARD_BEGIN
+  guetzli_amd::Params params;
+  params.butteraugli_target =
+      quality >= 0 ? (float)guetzli_amd::ButteraugliScoreForQuality(quality) : target;
+  params.device = iparams[0];
+  params.clear_metadata = iparams[1] != 0;
+  params.try_420 = iparams[2] != 0;
+  params.force_420 = iparams[3] != 0;
+  params.use_silver_screen = iparams[4] != 0;
+  params.zeroing_greedy_lookahead = iparams[5];
+  params.new_zeroing_model = iparams[6] != 0;
+  guetzli_amd::ProcessStats stats;
+  std::string dbg;
+  if (trace) stats.debug_output = &dbg;
+  std::string jpg;
+  bool ok;
+  if (jpeg_len < 0) {
+    static thread_local std::vector<uint8_t> v;   // Process takes a vector, as the reference's does
+    v.assign(data, data + (size_t)3 * w * h);
+    ok = guetzli_amd::Process(params, &stats, v, w, h, &jpg);
+  } else {
+    std::string in((const char*)data, (size_t)jpeg_len);
+    ok = guetzli_amd::Process(params, &stats, in, &jpg);
+  }
+  if (!ok) return -1;
+  if ((long)jpg.size() <= cap) memcpy(out, jpg.data(), jpg.size());
+  CopyText(dbg, trace, trace_cap);
+  if (timers && timers_cap > 0) {
+    std::string t;
+    for (const auto& kv : stats.timers) {
+      char buf[128];
+      snprintf(buf, sizeof(buf), "%s=%.6f;", kv.first.c_str(), kv.second);
+      t += buf;
+    }
+    for (const auto& kv : stats.counters) {
+      char buf[128];
+      snprintf(buf, sizeof(buf), "#%s=%d;", kv.first.c_str(), kv.second);
+      t += buf;
+    }
+    CopyText(t, timers, timers_cap);
+  }
+  return (long)jpg.size();
+  GZH_GUARD_END
+}
+
+long gzh_process(const uint8_t* rgb, int w, int h, double quality, float target, int device,
+                 uint8_t* out, long cap, char* trace, long trace_cap, char* timers,
+                 long timers_cap) {
+  const int ip[7] = {device, 1, 0, 0, 0, 3, 1};
+  return gzh_process_params(rgb, -1, w, h, quality, target, ip, out, cap, trace, trace_cap, timers,
+                            timers_cap);
+}
+
+// Process(params, stats, jpeg_data, &out); clear_metadata as Params::clear_metadata.
+long gzh_process_jpeg(const uint8_t* data, long len, double quality, float target, int device,
+                      int clear_metadata, uint8_t* out, long cap, char* trace, long trace_cap) {
+  const int ip[7] = {device, clear_metadata, 0, 0, 0, 3, 1};
+  return gzh_process_params(data, len, 0, 0, quality, target, ip, out, cap, trace, trace_cap, nullptr, 0);
+}
+
+double gzh_butteraugli_score_for_quality(double q) {
+  return guetzli_amd::ButteraugliScoreForQuality(q);
+}
+
+// Length-limited Huffman depths of a 257-entry histogram (CreateHuffmanTree, entropy_encode.cc:
+// 73-145), the way phase B's size model calls it (stream: see jpeg_writer.h).  Test hook.
+void gzh_huffman_depths(const uint32_t* counts, int tree_limit, uint8_t* depth, int stream) {
+  guetzli_amd::HuffmanDepths(counts, (size_t)guetzli_amd::kHistoSize, tree_limit, depth, stream);
+}
+
+// Threads of the driver's worker pool (the calling thread included): min(16, cores the process may
+// run on), GZ_HOST_THREADS overrides.  Test hook for the per-rank core share of a multi-GPU run.
+int gzh_worker_pool_size() { return guetzli_amd::WorkerPool::Get().size(); }
+
+// ReadJpeg as a canonical dump (test hook; the format: reader_dump.h).  Returns the dump size (copied if it
+// fits), or -1 if the stream is rejected.
+long gzh_read_jpeg(const uint8_t* data, long len, uint8_t* out, long cap) {
+  GZH_GUARD_BEGIN
+  guetzli_amd::JpegInput jpg;
+  std::string err;
+  if (!guetzli_amd::ReadJpeg(data, (size_t)len, &jpg, &err)) return -1;
+  const std::string d = guetzli_amd::DumpJpegInput(jpg);
+  if ((long)d.size() <= cap) memcpy(out, d.data(), d.size());
+  return (long)d.size();
+  GZH_GUARD_END
+}
+
+// ReadPNG (guetzli.cc:47-152): PNG bytes -> packed RGB with alpha blended on black.  Returns
+// 3*w*h (copied to out if it fits) and the dimensions in wh[0..1], or -1 if the stream is
+// rejected (message on stderr).
+long gzh_read_png(const uint8_t* data, long len, int* wh, uint8_t* out, long cap) {
+  GZH_GUARD_BEGIN
+  std::vector<uint8_t> rgb;
+  std::string err;
+  int w = 0, h = 0;
+  if (!guetzli_amd::ReadPng(data, (size_t)len, &w, &h, &rgb, &err)) {
+    fprintf(stderr, "Error reading PNG data from input file: %s\n", err.c_str());
+    return -1;
+  }
+  wh[0] = w;
+  wh[1] = h;
+  if ((long)rgb.size() <= cap) memcpy(out, rgb.data(), rgb.size());
+  return (long)rgb.size();
+  GZH_GUARD_END
+}
+
+// WriteJpeg of an image given by dequantised coefficients + quant matrices, for a frame with chroma subsampling
+// factor 1 or 2 (coefficients in the frame layout of include/guetzli_amd.h).  Test hook.
+long gzh_write_jpeg_factor(const int16_t* coeffs, int w, int h, const int* q, int original,
+                           int factor, uint8_t* out, long cap) {
+  GZH_GUARD_BEGIN
+  guetzli_amd::Frame f;
+  if (original) {
+    guetzli_amd::FrameFromOriginal(coeffs, w, h, &f);
+  } else {
+    int qq[3][64];
+    memcpy(qq, q, sizeof(qq));
+    guetzli_amd::FrameFromImageFactor(coeffs, qq, w, h, factor, &f);
+  }
+  std::string s;
+  if (!guetzli_amd::WriteJpeg(f, &s)) return -1;
+  if ((long)s.size() <= cap) memcpy(out, s.data(), s.size());
+  return (long)s.size();
+  GZH_GUARD_END
+}
+
+// The same for a 4:4:4 frame.
+long gzh_write_jpeg(const int16_t* coeffs, int w, int h, const int* q, int original,
+                    uint8_t* out, long cap) {
+  return gzh_write_jpeg_factor(coeffs, w, h, q, original, 1, out, cap);
+}
+
+// Marker segments + Huffman codes from symbol counts (test hook of BuildJpegHead):
+// counts uint32 [2][3][256] as gz_jpeg_histograms returns them; q null = the q=1 original.
+// Returns the head length (bytes copied to head_out if they fit) or -1.
+long gzh_jpeg_head_factor(const uint32_t* counts, const int* q, int w, int h, int ncomp, int factor,
+                          uint8_t* head_out, long cap, uint8_t* depth /*[2][3][256]*/,
+                          uint16_t* code /*[2][3][256]*/) {
+  GZH_GUARD_BEGIN
+  guetzli_amd::SymbolHistogram dc[3], ac[3];
+  for (int c = 0; c < 3; ++c)
+    for (int i = 0; i < 256; ++i) {
+      dc[c].Add(i, (int)counts[(0 * 3 + c) * 256 + i]);
+      ac[c].Add(i, (int)counts[(1 * 3 + c) * 256 + i]);
+    }
+  guetzli_amd::Frame f;
+  int qq[3][64];
+  if (q) memcpy(qq, q, sizeof(qq));
+  guetzli_amd::FrameTablesFactor(q ? qq : nullptr, w, h, ncomp, factor, &f);
+  guetzli_amd::JpegHead head;
+  if (!guetzli_amd::BuildJpegHead(f, dc, ac, &head)) return -1;
+  if ((long)head.bytes.size() <= cap) memcpy(head_out, head.bytes.data(), head.bytes.size());
+  memcpy(depth, head.depth, sizeof(head.depth));
+  memcpy(code, head.code, sizeof(head.code));
+  return (long)head.bytes.size();
+  GZH_GUARD_END
+}
+
+long gzh_jpeg_head(const uint32_t* counts, const int* q, int w, int h, int ncomp,
+                   uint8_t* head_out, long cap, uint8_t* depth /*[2][3][256]*/,
+                   uint16_t* code /*[2][3][256]*/) {
+  return gzh_jpeg_head_factor(counts, q, w, h, ncomp, 1, head_out, cap, depth, code);
+}
+
+}  // extern "C"

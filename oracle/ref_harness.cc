@@ -422,7 +422,7 @@ long ref_write_jpeg(const int16_t* coeffs, int w, int h, const int* q, uint8_t* 
 }
 
 // ReadJpeg(data, JPEG_READ_ALL) as the canonical dump gzh_read_jpeg also produces (see
-// guetzli_amd/host/processor.cc); -1 if the reference rejects the stream.
+// guetzli_amd/host/gzh_wrapper.cc); -1 if the reference rejects the stream.
 long ref_read_jpeg(const uint8_t* data, long len, uint8_t* out, long cap) {
   guetzli::JPEGData jpg;
   if (!guetzli::ReadJpeg(data, (size_t)len, guetzli::JPEG_READ_ALL, &jpg)) return -1;

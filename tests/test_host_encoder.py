@@ -475,3 +475,32 @@ def test_lazy_host_mirror_equals_the_device_image_after_the_search(host_emu, mon
         exp_jpg, _ = ref.process_params(rgb, ref._butteraugli_score_for_quality(95.0), **kw)
         got, _ = host_emu.process(rgb, quality=95, **kw)
         assert got == exp_jpg
+
+
+# What one 4:4:4 search publishes in ProcessStats (bench.py, the profiles and the tools read these names):
+# recorded from the driver before its split into files, not generated from the driver's own table.
+# ("downsample" appears only when a 4:2:0 round downsampled the image: not in this encode.)
+PUBLISHED_TIMERS = [
+    "block_search", "block_upload", "compare", "compare_begin", "compare_end", "create+encode", "jpeg_head",
+    "jpeg_scan_begin", "jpeg_scan_end", "jpeg_write", "pb_device_descents", "pb_device_fetches",
+    "pb_device_partitions", "pb_fast_apply", "pb_fast_count", "pb_fast_delta", "pb_fast_mirror", "pb_loop",
+    "pb_loop_codes", "pb_loop_ensure_sorted", "pb_loop_fast_steps", "pb_order", "pb_order_ahead_begin", "pb_sort",
+    "phase_b_host", "quantize", "select_frequency_masking", "select_quant_matrix", "total"]
+PUBLISHED_COUNTERS = [
+    "block search evaluations", "candidates entropy-coded", "candidates rejected on their size bound",
+    "number of iterations", "number of iterations down", "number of iterations up", "phase B code refresh threads",
+    "phase B coefficient steps", "phase B device partitions", "phase B entries fetched", "phase B fast steps",
+    "phase B order entries", "phase B partitions made ahead", "phase B prefixes exported by the device",
+    "phase B steps taken ahead and undone"]
+
+
+def test_published_timer_and_counter_names(host_emu):
+    """The names of the timers and counters of an encode with iterations in both directions are exactly the
+    published ones: none lost, renamed or added."""
+    _, info = host_emu.process(images.crop(40, 32, 100, 60), quality=95)
+    assert info["counters"]["number of iterations up"] > 0 and info["counters"]["number of iterations down"] > 0
+    assert sorted(info["timers"]) == sorted(PUBLISHED_TIMERS)
+    assert sorted(info["counters"]) == sorted(PUBLISHED_COUNTERS)
+    fast = sum(info["timers"]["pb_fast_" + part] for part in ("count", "apply", "mirror", "delta"))
+    # the four parts and an unpublished rest (five figures that arrive rounded to 1e-6 s each)
+    assert info["timers"]["pb_loop_fast_steps"] >= fast - 5e-6
