@@ -1,4 +1,4 @@
-// The Compare chain: blur dispatch (which instantiation for which size), the pipeline stages (opsin, SeparateFrequencies, mask branch, Malta, combine, final blur) on three streams, reconstruction, the block mask, candidate ranking on the host.
+// The Compare chain: blur dispatch (which instantiation for which size), the stream graph (ChainStreams, fork), the pipeline stages (opsin, SeparateFrequencies, mask branch, Malta, combine, final blur) on three streams, reconstruction, the chain's self-checks, the block mask.
 // (part of the one translation unit gz_api.hip, which includes these files in order; split by
 // concern in round 5 -- no declaration here is visible outside libguetzli_amd.so but the C ABI)
 #pragma once
@@ -18,6 +18,7 @@ namespace {
 // What round 4 removed after it had lost every A/B of rounds 2 and 3: the unrolled (non-compact)
 // column pass and fused kernels, 64-row tiles, the epilogue without 16-byte accesses and the row
 // pass with LDS bank conflicts (GZ_BLUR_OPT), the three-plane LF passes, the unpaired mask blurs.
+// Every dispatcher and stage below launches on the stream it is given.
 static bool packed_blur(const gz_ctx* c) {
   if (c->cfg.blur_packed >= 0) return c->cfg.blur_packed != 0;
   // (round 5, with 16-row tiles: 1080p 0.3356 -> 0.3290 ms, 2560 x 1440 0.487 -> 0.466, 3200 x 1800 0.719 -> 0.684;
@@ -34,77 +35,45 @@ static bool small_tiles(const gz_ctx* c) {
   return (size_t)c->w * c->h < 7000000;
 }
 
-template <int R, class Src, int NC>
-int blur_h(gz_ctx* c, const SrcPack<Src, NC>& src, const PlanePack<NC>& dst,
-           const BlurCfg& cfg) {
-  if (cfg.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
-  const Taps<R> tp = taps_of<R>(cfg);
-  const BorderScale bs = cfg.bx;
+// PAIR (with `second`): two blurs of equal radius and different sigma on two independent planes as ONE launch per
+// pass (grid z = plane; plane 1 takes the second tap set): the mask's radius-20 pair (butteraugli.cc:1780-1790).
+template <int R, class Src, int NC, bool PAIR = false>
+int blur_h(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const PlanePack<NC>& dst,
+           const BlurCfg& cfg, const BlurCfg* second = nullptr) {
+  if (PAIR != (second != nullptr)) { c->err = "blur pair mismatch"; return GZ_E_STATE; }
+  const BlurCfg& cfg1 = PAIR ? *second : cfg;
+  if (cfg.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
+  const Taps<R> t0 = taps_of<R>(cfg), t1 = taps_of<R>(cfg1);
+  const BorderScale b0 = cfg.bx, b1 = cfg1.bx;
   const int w = c->w, h = c->h, pitch = c->pitch;
   if (packed_blur(c)) {
     dim3 grid(gz_div_up(c->w, HW), gz_div_up(c->h, HP), NC);
-    GZ_LAUNCH((k_blur_h_pk<R, Src, NC>), grid, dim3(256), c->stream, src, dst, w, h, pitch, tp, bs, tp, bs);
+    GZ_LAUNCH((k_blur_h_pk<R, Src, NC, PAIR>), grid, dim3(256), stream, src, dst, w, h, pitch, t0, b0, t1, b1);
   } else {
     dim3 grid(gz_div_up(c->w, HW), gz_div_up(c->h, HH), NC);
-    GZ_LAUNCH((k_blur_h<R, Src, NC>), grid, dim3(256), c->stream, src, dst, w, h, pitch, tp, bs, tp, bs);
+    GZ_LAUNCH((k_blur_h<R, Src, NC, PAIR>), grid, dim3(256), stream, src, dst, w, h, pitch, t0, b0, t1, b1);
   }
   KCHK(c);
   return GZ_OK;
 }
 
-template <int R, int NC, class Post>
-int blur_v(gz_ctx* c, const CPlanePack<NC>& src, const Post& post, const BlurCfg& cfg) {
-  if (cfg.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
-  const Taps<R> tp = taps_of<R>(cfg);
-  const BorderScale bs = cfg.by;
+template <int R, int NC, class Post, bool PAIR = false>
+int blur_v(gz_ctx* c, hipStream_t stream, const CPlanePack<NC>& src, const Post& post, const BlurCfg& cfg,
+           const BlurCfg* second = nullptr) {
+  if (PAIR != (second != nullptr)) { c->err = "blur pair mismatch"; return GZ_E_STATE; }
+  const BlurCfg& cfg1 = PAIR ? *second : cfg;
+  if (cfg.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
+  const Taps<R> t0 = taps_of<R>(cfg), t1 = taps_of<R>(cfg1);
+  const BorderScale b0 = cfg.by, b1 = cfg1.by;
   const int w = c->w, h = c->h, pitch = c->pitch;
   const bool small = small_tiles(c);
-  dim3 grid(gz_div_up(c->w, VW), gz_div_up(c->h, small ? kSmallTileRows : kTileRows));
+  dim3 grid(gz_div_up(c->w, VW), gz_div_up(c->h, small ? kSmallTileRows : kTileRows), PAIR ? 2 : 1);
   if (packed_blur(c)) {
-    if (small) GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kSmallTileRows>), grid, dim3(256), c->stream, src, post, w, h, pitch, tp, bs, tp, bs);
-    else GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kTileRows>), grid, dim3(256), c->stream, src, post, w, h, pitch, tp, bs, tp, bs);
+    if (small) GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kSmallTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
+    else GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
   } else {
-    if (small) GZ_LAUNCH((k_blur_v_compact<R, NC, Post, kSmallTileRows>), grid, dim3(256), c->stream, src, post, w, h, pitch, tp, bs, tp, bs);
-    else GZ_LAUNCH((k_blur_v_compact<R, NC, Post, kTileRows>), grid, dim3(256), c->stream, src, post, w, h, pitch, tp, bs, tp, bs);
-  }
-  KCHK(c);
-  return GZ_OK;
-}
-
-// Two blurs of equal radius and different sigma on two independent planes as ONE launch per
-// pass (grid z = plane): the mask's radius-20 pair (butteraugli.cc:1780-1790).
-template <int R, class Src>
-int blur_h_pair(gz_ctx* c, const SrcPack<Src, 2>& src, const PlanePack<2>& dst, const BlurCfg& cfg0,
-                const BlurCfg& cfg1) {
-  if (cfg0.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
-  const Taps<R> t0 = taps_of<R>(cfg0), t1 = taps_of<R>(cfg1);
-  const BorderScale b0 = cfg0.bx, b1 = cfg1.bx;
-  const int w = c->w, h = c->h, pitch = c->pitch;
-  if (packed_blur(c)) {
-    dim3 grid(gz_div_up(c->w, HW), gz_div_up(c->h, HP), 2);
-    GZ_LAUNCH((k_blur_h_pk<R, Src, 2, true>), grid, dim3(256), c->stream, src, dst, w, h, pitch, t0, b0, t1, b1);
-  } else {
-    dim3 grid(gz_div_up(c->w, HW), gz_div_up(c->h, HH), 2);
-    GZ_LAUNCH((k_blur_h<R, Src, 2, true>), grid, dim3(256), c->stream, src, dst, w, h, pitch, t0, b0, t1, b1);
-  }
-  KCHK(c);
-  return GZ_OK;
-}
-template <int R>
-int blur_v_pair(gz_ctx* c, const CPlanePack<2>& src, const PostStore<2>& post, const BlurCfg& cfg0,
-                const BlurCfg& cfg1) {
-  if (cfg0.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
-  const Taps<R> t0 = taps_of<R>(cfg0), t1 = taps_of<R>(cfg1);
-  const BorderScale b0 = cfg0.by, b1 = cfg1.by;
-  const int w = c->w, h = c->h, pitch = c->pitch;
-  const bool small = small_tiles(c);
-  dim3 grid(gz_div_up(c->w, VW), gz_div_up(c->h, small ? kSmallTileRows : kTileRows), 2);
-  if (packed_blur(c)) {
-    if (small) GZ_LAUNCH((k_blur_v_pk<R, 2, PostStore<2>, kSmallTileRows, true>), grid, dim3(256), c->stream, src, post, w, h, pitch, t0, b0, t1, b1);
-    else GZ_LAUNCH((k_blur_v_pk<R, 2, PostStore<2>, kTileRows, true>), grid, dim3(256), c->stream, src, post, w, h, pitch, t0, b0, t1, b1);
-  } else {
-    if (small) GZ_LAUNCH((k_blur_v_compact<R, 2, PostStore<2>, kSmallTileRows, true>), grid, dim3(256), c->stream, src, post, w, h, pitch, t0, b0, t1, b1);
-    else GZ_LAUNCH((k_blur_v_compact<R, 2, PostStore<2>, kTileRows, true>), grid, dim3(256), c->stream, src, post, w, h, pitch, t0, b0, t1, b1);
+    if (small) GZ_LAUNCH((k_blur_v_compact<R, NC, Post, kSmallTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
+    else GZ_LAUNCH((k_blur_v_compact<R, NC, Post, kTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
   }
   KCHK(c);
   return GZ_OK;
@@ -114,7 +83,7 @@ int blur_v_pair(gz_ctx* c, const CPlanePack<2>& src, const PostStore<2>& post, c
 // maxima and the image maximum; that kernel keeps its results in registers (always 32-row tiles).
 // bm.tiles + n_tiles: the listed tiles only (tile ids of the grid this function would launch).
 template <int R, int NC, class Src, class Post, bool BM = false>
-int blur2d(gz_ctx* c, const SrcPack<Src, NC>& src, const Post& post, const BlurCfg& cfg,
+int blur2d(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const Post& post, const BlurCfg& cfg,
            BlockMaxOut bm = BlockMaxOut{nullptr, nullptr, 0, nullptr}, int n_tiles = 0) {
   if (cfg.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
   const Taps<R> tp = taps_of<R>(cfg);
@@ -123,63 +92,44 @@ int blur2d(gz_ctx* c, const SrcPack<Src, NC>& src, const Post& post, const BlurC
   // (the chain's last blur, with block maxima: 16-row tiles below 1.5 MPix only -- 720p chain 0.224 -> 0.213 ms,
   // nothing at 1080p, +3 % at 2560 x 1440: profiles/r05_chain_experiments.log, section 8)
   // (a tile list: always the 16-row tiles -- a handful of workgroups, whose time is one workgroup's latency)
-  if (bm.tiles || (BM ? small_tiles(c) && (size_t)c->w * c->h < 1500000 : small_tiles(c))) {
-    dim3 grid(gz_div_up(c->w, T2), gz_div_up(c->h, kSmallTileRows));
-    if (bm.tiles) grid = dim3(n_tiles);
-    GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kSmallTileRows>), grid, dim3(256), c->stream, src, post, w,
-              h, pitch, tp, bx, by, bm);
-  } else {
-    dim3 grid(gz_div_up(c->w, T2), gz_div_up(c->h, kTileRows));
-    if (bm.tiles) grid = dim3(n_tiles);
-    GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kTileRows>), grid, dim3(256), c->stream, src, post, w,
-              h, pitch, tp, bx, by, bm);
-  }
+  const bool small = bm.tiles || (BM ? small_tiles(c) && (size_t)c->w * c->h < 1500000 : small_tiles(c));
+  const dim3 grid = bm.tiles ? dim3(n_tiles) : dim3(gz_div_up(c->w, T2), gz_div_up(c->h, small ? kSmallTileRows : kTileRows));
+  if (small) GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kSmallTileRows>), grid, dim3(256), stream, src, post, w, h, pitch, tp, bx, by, bm);
+  else GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kTileRows>), grid, dim3(256), stream, src, post, w, h, pitch, tp, bx, by, bm);
   KCHK(c);
   return GZ_OK;
 }
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != GZ_OK) return rc_; } while (0)
 
-// Reserves `bytes` of the staging buffer (waiting for its previous upload if that is still
-// running) and returns it; stage_sent() marks the upload that was just enqueued on `stream`.
-static int stage_reserve(gz_ctx* c, HostStage* st, size_t bytes, void** out) {
-  if (!st->ev) HIPCHK(c, pool_event_create(&st->ev));
-  if (st->busy) {
-    HIPCHK(c, hipEventSynchronize(st->ev));
-    st->busy = false;
+// One plane blurred with any of the chain's radii, by the kernels gz_compare uses for that radius: fused below 16,
+// two passes (through `tmp`) from 16 up.  A template on the Post functor, instantiated where it is used (gz_probe_blur):
+// a build without the probes (GZ_NO_PROBES) does not carry the instantiations that only they launch.
+template <int R, class Post>
+int blur_plane_r(gz_ctx* c, hipStream_t stream, const SrcPack<SrcPlain, 1>& src, float* tmp, const Post& post, const BlurCfg& cfg) {
+  if constexpr (R < 16) {
+    return blur2d<R, 1, SrcPlain, Post>(c, stream, src, post, cfg);
+  } else {
+    PlanePack<1> t; CPlanePack<1> ct;
+    t.p[0] = tmp; ct.p[0] = tmp;
+    TRY((blur_h<R, SrcPlain, 1>(c, stream, src, t, cfg)));
+    return blur_v<R, 1, Post>(c, stream, ct, post, cfg);
   }
-  if (bytes > st->cap) {
-    if (st->h) (void)pool_host_free(st->h);
-    st->h = nullptr;
-    st->cap = 0;
-    const size_t cap = bytes + bytes / 2 + 4096;
-    HIPCHK(c, pool_host_malloc(&st->h, cap));
-    st->cap = cap;
+}
+template <class Post>
+int blur_plane(gz_ctx* c, hipStream_t stream, const SrcPack<SrcPlain, 1>& src, float* tmp, const Post& post, const BlurCfg& cfg) {
+  switch (cfg.r) {
+    case 2: return blur_plane_r<2>(c, stream, src, tmp, post, cfg);
+    case 3: return blur_plane_r<3>(c, stream, src, tmp, post, cfg);
+    case 4: return blur_plane_r<4>(c, stream, src, tmp, post, cfg);
+    case 5: return blur_plane_r<5>(c, stream, src, tmp, post, cfg);
+    case 8: return blur_plane_r<8>(c, stream, src, tmp, post, cfg);
+    case 16: return blur_plane_r<16>(c, stream, src, tmp, post, cfg);
+    case 20: return blur_plane_r<20>(c, stream, src, tmp, post, cfg);
+    case 23: return blur_plane_r<23>(c, stream, src, tmp, post, cfg);
   }
-  *out = st->h;
-  return GZ_OK;
-}
-static int stage_sent(gz_ctx* c, HostStage* st, hipStream_t stream) {
-  HIPCHK(c, hipEventRecord(st->ev, stream));
-  st->busy = true;
-  return GZ_OK;
-}
-static int result_buffer(gz_ctx* c, size_t bytes, void** out) {
-  if (bytes > c->h_res_cap) {
-    if (c->h_res) (void)pool_host_free(c->h_res);
-    c->h_res = nullptr;
-    c->h_res_cap = 0;
-    const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    HIPCHK(c, pool_host_malloc(&c->h_res, cap));
-    c->h_res_cap = cap;
-  }
-  *out = c->h_res;
-  return GZ_OK;
-}
-static void stage_free(HostStage* st) {
-  if (st->ev) { (void)hipEventSynchronize(st->ev); pool_event_destroy(st->ev); }
-  if (st->h) (void)pool_host_free(st->h);
-  st->h = nullptr; st->ev = nullptr; st->cap = 0; st->busy = false;
+  c->err = "unsupported blur radius";
+  return GZ_E_ARG;
 }
 
 int setup_blur_cfg(gz_ctx* c, BlurCfg* cfg, float sigma, float border_ratio) {
@@ -203,61 +153,85 @@ int setup_blur_cfg(gz_ctx* c, BlurCfg* cfg, float sigma, float border_ratio) {
   return GZ_OK;
 }
 
+// ------------------------------------------------------------------ the stream graph --
+// The SameNoise blur and the mask branch (DiffPrecompute + three blurs; scratch planes
+// tmp[0..2], snb, diffx, diffy, mxb, myb1, myb2) read only the two PsychoImages, so they run
+// on the side stream while the main stream does Malta; k_combine needs both.  At 1080p a launch is
+// ~1000 workgroups for 256 CUs and the kernels are latency-bound: the overlap is worth ~10 %.
+// cfg.single_stream: 1 = the whole Compare on the main stream (per-kernel profiling; no fork / join events),
+// 0 = the three-stream chain, -1 (default) = by company: three streams for a context that has the device to itself,
+// ONE when other contexts are alive on it (a batch's images in flight).  The side streams buy a lone chain its
+// overlap (1080p 0.326 against 0.371 ms); several images in flight overlap each other instead, and every fork /
+// join costs host time in a runtime four threads are calling into: one stream per image is +65 % at 512 x 512,
+// +12-25 % at 1 MPix, +10 % at 1080p, +4 % at 4K (profiles/r06_chain_experiments.log, section 6).  The choice is
+// made per Compare and changes no result: every Compare joins its side streams before it ends.
+static bool single_stream_wanted(const gz_ctx* c) {
+  if (c->cfg.single_stream >= 0) return c->cfg.single_stream != 0;
+  return slots_taken(c->device) > 1;
+}
+// ... decided ONCE per Compare (enqueue_compare) and handed to its stages as this value: contexts come and go on other
+// threads while a Compare is being enqueued, and a fork made for three streams must not meet a join that thinks there
+// was one.  Not forked: all three are the main stream, and the same code enqueues the same kernels in the same order.
+struct ChainStreams {
+  hipStream_t main, side, side2;
+};
+static ChainStreams chain_streams(const gz_ctx* c, bool forked) {
+  return forked ? ChainStreams{c->stream, c->side_stream, c->side_stream2} : ChainStreams{c->stream, c->stream, c->stream};
+}
+// An edge of the graph: what `to` gets from here on runs behind what `from` holds now.  Recorded and waited for only
+// when the two differ (a stream keeps its own order); fork() is both halves, a join records where its branch ends and
+// waits where its results are needed.
+static int record_for(gz_ctx* c, hipStream_t from, hipStream_t to, hipEvent_t ev) {
+  if (from != to) HIPCHK(c, hipEventRecord(ev, from));
+  return GZ_OK;
+}
+static int wait_for(gz_ctx* c, hipStream_t from, hipStream_t to, hipEvent_t ev) {
+  if (from != to) HIPCHK(c, hipStreamWaitEvent(to, ev, 0));
+  return GZ_OK;
+}
+static int fork(gz_ctx* c, hipStream_t from, hipStream_t to, hipEvent_t ev) {
+  TRY(record_for(c, from, to, ev));
+  return wait_for(c, from, to, ev);
+}
+
 // --------------------------------------------------------------- pipeline stages ------
 // OpsinDynamicsImage: lin[3] -> xyb[3]
 // tiles (optional): only the listed tiles of the launch's grid (opsin_tile_rows() high), n_tiles of them.
-int stage_opsin(gz_ctx* c, const int* tiles = nullptr, int n_tiles = 0) {
+int stage_opsin(gz_ctx* c, hipStream_t stream, const int* tiles = nullptr, int n_tiles = 0) {
   SrcPack<SrcPlain, 3> s;
   for (int i = 0; i < 3; ++i) s.s[i].p = c->lin[i];
   PostOpsin post;
   for (int i = 0; i < 3; ++i) { post.lin[i] = c->lin[i]; post.xyb[i] = c->xyb[i]; }
-  TRY((blur2d<2, 3, SrcPlain, PostOpsin>(c, s, post, c->blur[B_OPSIN], BlockMaxOut{nullptr, nullptr, 0, tiles}, n_tiles)));
-  return GZ_OK;
+  return blur2d<2, 3, SrcPlain, PostOpsin>(c, stream, s, post, c->blur[B_OPSIN], BlockMaxOut{nullptr, nullptr, 0, tiles}, n_tiles);
 }
 static int opsin_tile_rows(const gz_ctx*) { return kSmallTileRows; }   // (of a tile LIST: blur2d)
 
 // SeparateFrequencies: xyb[3] -> Psycho planes
 // The LF blur (radius 16) runs as X / Y (two planes, PostLFxy) and B (one plane, PostLFb: its
-// XybLowFreqToVals mixes in the raw LF of Y the first wrote, butteraugli.cc:386-389).  side_b (the
-// candidate's chain, unless single-stream): B -- which only k_combine reads -- goes to side stream
-// 2, beside the MF / HF bands instead of in front of them; the caller joins that stream before
-// k_combine (join_mask_branch).  Its row-pass result goes through the distance-map plane, which
-// nothing else touches before the chain's last kernel.
-int stage_separate(gz_ctx* c, Psycho* ps, bool side_b = false) {
-  hipStream_t main_stream = c->stream;
-  hipStream_t b_stream = side_b ? c->side_stream2 : c->stream;
-  int rc = GZ_OK;
-  if (side_b) {
-    HIPCHK(c, hipEventRecord(c->ev_xyb, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(b_stream, c->ev_xyb, 0));
-  }
+// XybLowFreqToVals mixes in the raw LF of Y the first wrote, butteraugli.cc:386-389).  B -- which only k_combine
+// reads -- goes to cs.side2 (the candidate's chain, when forked), beside the MF / HF bands instead of in front of
+// them; the caller joins that stream before k_combine (stage_diffmap).  Its row-pass result goes through the
+// distance-map plane, which nothing else touches before the chain's last kernel.
+int stage_separate(gz_ctx* c, const ChainStreams& cs, Psycho* ps) {
+  TRY(fork(c, cs.main, cs.side2, c->ev_xyb));
   {
-    c->stream = b_stream;
     SrcPack<SrcPlain, 1> s; PlanePack<1> t;
     s.s[0].p = c->xyb[2]; t.p[0] = c->distmap;
-    rc = blur_h<16, SrcPlain, 1>(c, s, t, c->blur[B_LF]);
-    c->stream = main_stream;
-    TRY(rc);
+    TRY((blur_h<16, SrcPlain, 1>(c, cs.side2, s, t, c->blur[B_LF])));
   }
   {
     SrcPack<SrcPlain, 2> s; PlanePack<2> t; CPlanePack<2> ct;
     for (int i = 0; i < 2; ++i) { s.s[i].p = c->xyb[i]; t.p[i] = c->tmp[i]; ct.p[i] = c->tmp[i]; }
-    TRY((blur_h<16, SrcPlain, 2>(c, s, t, c->blur[B_LF])));
+    TRY((blur_h<16, SrcPlain, 2>(c, cs.main, s, t, c->blur[B_LF])));
     PostLFxy post;
     for (int i = 0; i < 2; ++i) { post.lf_raw[i] = c->lf_raw[i]; post.lf_vals[i] = ps->lfv[i]; }
-    TRY((blur_v<16, 2, PostLFxy>(c, ct, post, c->blur[B_LF])));
+    TRY((blur_v<16, 2, PostLFxy>(c, cs.main, ct, post, c->blur[B_LF])));
   }
-  if (side_b) {
-    HIPCHK(c, hipEventRecord(c->ev_lfy, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(b_stream, c->ev_lfy, 0));
-  }
+  TRY(fork(c, cs.main, cs.side2, c->ev_lfy));
   {
-    c->stream = b_stream;
     CPlanePack<1> ct; ct.p[0] = c->distmap;
     PostLFb post; post.lf_raw_y = c->lf_raw[1]; post.lf_vals_b = ps->lfv[2];
-    rc = blur_v<16, 1, PostLFb>(c, ct, post, c->blur[B_LF]);
-    c->stream = main_stream;
-    TRY(rc);
+    TRY((blur_v<16, 1, PostLFb>(c, cs.side2, ct, post, c->blur[B_LF])));
   }
   {  // MF (X, Y)
     SrcPack<SrcDiff, 2> s;
@@ -272,7 +246,7 @@ int stage_separate(gz_ctx* c, Psycho* ps, bool side_b = false) {
       post.mf[i] = ps->mf[i];
       post.hf_pre[i] = c->hfp[i];
     }
-    TRY((blur2d<8, 2, SrcDiff, PostMF>(c, s, post, c->blur[B_MF])));
+    TRY((blur2d<8, 2, SrcDiff, PostMF>(c, cs.main, s, post, c->blur[B_MF])));
   }
   {  // HF / UHF
     SrcPack<SrcPlain, 2> s;
@@ -284,40 +258,33 @@ int stage_separate(gz_ctx* c, Psycho* ps, bool side_b = false) {
       post.uhf[i] = ps->uhf[i];
     }
     post.lf_raw_y = c->lf_raw[1];
-    TRY((blur2d<4, 2, SrcPlain, PostHF>(c, s, post, c->blur[B_HF])));
+    TRY((blur2d<4, 2, SrcPlain, PostHF>(c, cs.main, s, post, c->blur[B_HF])));
   }
   return GZ_OK;
 }
 
-// Mask first half: DiffPrecompute + three blurs -> mxb, myb1, myb2.  The three blurs only share
+// Mask first half: DiffPrecompute + three blurs -> mxb, myb1, myb2, on `stream`.  The three blurs only share
 // their input: the two of radius 20 (X: sigma r2 = 9.24; Y second: sigma r1 = 9.04 -- separate
-// taps) are one launch per pass (grid z = plane); with `other` given, the small one (radius 5)
-// goes behind whatever is queued there (the SameNoise blur, the shorter of the two side branches).
-int stage_mask_blurs(gz_ctx* c, const MaskPrePack& pk, hipStream_t other = nullptr) {
+// taps) are one launch per pass (grid z = plane); the small one (radius 5) goes to `small_stream`, behind
+// whatever is queued there (the SameNoise blur, the shorter of the two side branches).
+int stage_mask_blurs(gz_ctx* c, hipStream_t stream, hipStream_t small_stream, const MaskPrePack& pk) {
   dim3 grid(gz_div_up(c->w, 1024), c->h, 2);
-  GZ_LAUNCH(k_mask_pre, grid, dim3(256), c->stream, pk, c->w, c->h, c->pitch);
+  GZ_LAUNCH(k_mask_pre, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
   KCHK(c);
-  if (other) {
-    HIPCHK(c, hipEventRecord(c->ev_mask_pre, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(other, c->ev_mask_pre, 0));
-  }
+  TRY(fork(c, stream, small_stream, c->ev_mask_pre));
   {
     SrcPack<SrcPlain, 2> s; PlanePack<2> t; CPlanePack<2> ct;
     s.s[0].p = c->diffx; s.s[1].p = c->diffy;
     t.p[0] = c->tmp[1]; t.p[1] = c->tmp[2];
     ct.p[0] = c->tmp[1]; ct.p[1] = c->tmp[2];
-    TRY((blur_h_pair<20, SrcPlain>(c, s, t, c->blur[B_MASKX], c->blur[B_MASKY1])));
+    TRY((blur_h<20, SrcPlain, 2, true>(c, stream, s, t, c->blur[B_MASKX], &c->blur[B_MASKY1])));
     PostStore<2> post; post.out[0] = c->mxb; post.out[1] = c->myb2;
-    TRY((blur_v_pair<20>(c, ct, post, c->blur[B_MASKX], c->blur[B_MASKY1])));
+    TRY((blur_v<20, 2, PostStore<2>, true>(c, stream, ct, post, c->blur[B_MASKX], &c->blur[B_MASKY1])));
   }
   {
     SrcPack<SrcPlain, 1> s; s.s[0].p = c->diffy;
     PostStore<1> post; post.out[0] = c->myb1;
-    hipStream_t here = c->stream;
-    if (other) c->stream = other;
-    const int rc = blur2d<5, 1, SrcPlain, PostStore<1>>(c, s, post, c->blur[B_MASKY0]);
-    c->stream = here;
-    TRY(rc);
+    TRY((blur2d<5, 1, SrcPlain, PostStore<1>>(c, small_stream, s, post, c->blur[B_MASKY0])));
   }
   return GZ_OK;
 }
@@ -334,11 +301,11 @@ static void mask_in_psycho(const Psycho& p, MaskIn in[2]) {
   }
 }
 // The original's half, once per image (gz_set_rgb): c->sup0.
-int stage_mask_sup(gz_ctx* c, const MaskIn in[2], float* const out[2]) {
+int stage_mask_sup(gz_ctx* c, hipStream_t stream, const MaskIn in[2], float* const out[2]) {
   MaskSupPack pk;
   for (int i = 0; i < 2; ++i) { pk.in[i] = in[i]; pk.out[i] = out[i]; }
   dim3 grid(gz_div_up(c->w, 1024), c->h, 2);
-  GZ_LAUNCH(k_mask_sup, grid, dim3(256), c->stream, pk, c->w, c->h, c->pitch);
+  GZ_LAUNCH(k_mask_sup, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
   KCHK(c);
   return GZ_OK;
 }
@@ -354,14 +321,14 @@ MaskPrePack mask_pack_psycho(gz_ctx* c, const Psycho& b) {
 int ensure_pip(gz_ctx* c);
 // Mask(xyb0, xyb1) on raw planes (StartBlockComparisons' mask of the original with itself, the
 // stage probe): image 0's half goes through two scratch planes of the probe arena.
-int mask_pack_plain(gz_ctx* c, const float* const a[2], const float* const b[2], MaskPrePack* pk) {
+int mask_pack_plain(gz_ctx* c, hipStream_t stream, const float* const a[2], const float* const b[2], MaskPrePack* pk) {
   MaskIn in0[2];
   for (int i = 0; i < 2; ++i) {
     in0[i] = {nullptr, a[i], 0.0, 1.0, 1};
     pk->in1[i] = {nullptr, b[i], 0.0, 1.0, 1};
   }
   TRY(ensure_pip(c));   // (sup_scratch)
-  TRY(stage_mask_sup(c, in0, c->sup_scratch));
+  TRY(stage_mask_sup(c, stream, in0, c->sup_scratch));
   pk->sup0[0] = c->sup_scratch[0];
   pk->sup0[1] = c->sup_scratch[1];
   pk->out[0] = c->diffx;
@@ -369,73 +336,62 @@ int mask_pack_plain(gz_ctx* c, const float* const a[2], const float* const b[2],
   return GZ_OK;
 }
 
-// The SameNoise blur and the mask branch (DiffPrecompute + three blurs; scratch planes
-// tmp[0..2], snb, diffx, diffy, mxb, myb1, myb2) read only the two PsychoImages, so they run
-// on the side stream while the main stream does Malta; k_combine needs both.  At 1080p a launch is
-// ~1000 workgroups for 256 CUs and the kernels are latency-bound: the overlap is worth ~10 %.
-// cfg.single_stream: 1 = the whole Compare on the main stream (per-kernel profiling; no fork / join events),
-// 0 = the three-stream chain, -1 (default) = by company: three streams for a context that has the device to itself,
-// ONE when other contexts are alive on it (a batch's images in flight).  The side streams buy a lone chain its
-// overlap (1080p 0.326 against 0.371 ms); several images in flight overlap each other instead, and every fork /
-// join costs host time in a runtime four threads are calling into: one stream per image is +65 % at 512 x 512,
-// +12-25 % at 1 MPix, +10 % at 1080p, +4 % at 4K (profiles/r06_chain_experiments.log, section 6).  The choice is
-// made per Compare and changes no result: every Compare joins its side streams before it ends.
-static bool single_stream_wanted(const gz_ctx* c) {
-  if (c->cfg.single_stream >= 0) return c->cfg.single_stream != 0;
-  return slots_taken(c->device) > 1;
-}
-// ... decided ONCE per Compare (choose_streams, at the top of every function that enqueues a diffmap stage) and kept in
-// the context for its stages: contexts come and go on other threads while a Compare is being enqueued, and a fork
-// made for three streams must not meet a join that thinks there was one.
-static void choose_streams(gz_ctx* c) { c->single_now = single_stream_wanted(c); }
-static bool single_stream(const gz_ctx* c) { return c->single_now; }
-int fork_side_branch(gz_ctx* c, const Psycho& p0, const Psycho& p1) {
-  if (single_stream(c)) {
-    SrcPack<SrcSameNoise, 1> s; PlanePack<1> t; CPlanePack<1> ct;
-    s.s[0].a = p0.hf[1]; s.s[0].b = p1.hf[1];
-    t.p[0] = c->tmp[0]; ct.p[0] = c->tmp[0];
-    TRY((blur_h<23, SrcSameNoise, 1>(c, s, t, c->blur[B_SN])));
-    PostStore<1> post; post.out[0] = c->snb;
-    TRY((blur_v<23, 1, PostStore<1>>(c, ct, post, c->blur[B_SN])));
-    return stage_mask_blurs(c, mask_pack_psycho(c, p1));
+// k_combine's arguments for the mask alone (no diffmap): the three mask blurs in, mask planes (and, given, the DC
+// mask planes) out.  stage_diffmap fills in the rest.
+static CombineArgs combine_mask_args(const gz_ctx* c, float* const mask_out[3], float* const mask_dc_out[3]) {
+  CombineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.mask_x_blur = c->mxb; a.mask_y_blur1 = c->myb1; a.mask_y_blur2 = c->myb2;
+  a.luts = c->d_mask_luts;
+  for (int i = 0; i < 3; ++i) {
+    a.mask_out[i] = mask_out ? mask_out[i] : nullptr;
+    a.mask_dc_out[i] = mask_dc_out ? mask_dc_out[i] : nullptr;
   }
-  HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-  HIPCHK(c, hipStreamWaitEvent(c->side_stream2, c->ev_fork, 0));
-  hipStream_t main_stream = c->stream;
-  int rc = GZ_OK;
-  c->stream = c->side_stream2;
+  return a;
+}
+static int launch_combine(gz_ctx* c, hipStream_t stream, const CombineArgs& a) {
+  dim3 grid(gz_div_up(c->w, 1024), c->h);   // (4 pixels per thread)
+  GZ_LAUNCH(k_combine, grid, dim3(256), stream, a, c->w, c->h, c->pitch);
+  KCHK(c);
+  return GZ_OK;
+}
+
+// The SameNoise blur (cs.side2) and the mask branch (cs.side, its radius-5 blur behind the SameNoise blur on
+// cs.side2), forked off cs.main; both branches end in the events stage_diffmap waits for before k_combine.
+int fork_side_branch(gz_ctx* c, const ChainStreams& cs, const Psycho& p0, const Psycho& p1) {
+  TRY(fork(c, cs.main, cs.side, c->ev_fork));
+  TRY(wait_for(c, cs.main, cs.side2, c->ev_fork));
   {  // SameNoiseLevels blur input + blur (sigma 10.67)
     SrcPack<SrcSameNoise, 1> s; PlanePack<1> t; CPlanePack<1> ct;
     s.s[0].a = p0.hf[1]; s.s[0].b = p1.hf[1];
     t.p[0] = c->tmp[0]; ct.p[0] = c->tmp[0];
-    rc = blur_h<23, SrcSameNoise, 1>(c, s, t, c->blur[B_SN]);
+    TRY((blur_h<23, SrcSameNoise, 1>(c, cs.side2, s, t, c->blur[B_SN])));
     PostStore<1> post; post.out[0] = c->snb;
-    if (rc == GZ_OK) rc = blur_v<23, 1, PostStore<1>>(c, ct, post, c->blur[B_SN]);
+    TRY((blur_v<23, 1, PostStore<1>>(c, cs.side2, ct, post, c->blur[B_SN])));
   }
-  c->stream = c->side_stream;
-  if (rc == GZ_OK) rc = stage_mask_blurs(c, mask_pack_psycho(c, p1), c->side_stream2);
-  c->stream = main_stream;
-  TRY(rc);
-  HIPCHK(c, hipEventRecord(c->ev_join, c->side_stream));
-  HIPCHK(c, hipEventRecord(c->ev_join2, c->side_stream2));
-  return GZ_OK;
-}
-int join_mask_branch(gz_ctx* c) {
-  if (single_stream(c)) return GZ_OK;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join2, 0));
-  return GZ_OK;
+  TRY(stage_mask_blurs(c, cs.side, cs.side2, mask_pack_psycho(c, p1)));
+  TRY(record_for(c, cs.side, cs.main, c->ev_join));
+  return record_for(c, cs.side2, cs.main, c->ev_join2);
 }
 
+// Who zeroes d_max_bits, which the chain's last kernel accumulates the image maximum into.
+enum class ClearMax {
+  kReconstruction,   // the full reconstruction at the head of this Compare has (its first workgroup)
+  kCombine,          // k_combine does: a Compare on patched planes has no reconstruction in front
+  kMemset,           // a fill in front of the last blur (a chain that starts behind the reconstruction: the probe)
+};
+// What a Compare is asked for (enqueue_compare; stage_diffmap reads the first two).
+enum CompareWant : unsigned {
+  kWantBlockMax = 1,   // the per-block maxima (d_block_max) beside the image maximum
+  kWantDistmap = 2,    // the distance map stored in c->distmap
+  kWholeChain = 4,     // never start from patched planes (gz_time_compare)
+};
+
 // DiffmapPsychoImage (butteraugli.cc:817-908) + score: p0 = original, p1 = candidate.
-int stage_diffmap(gz_ctx* c, const Psycho& p0, const Psycho& p1, bool want_block_max,
-                  bool max_cleared = false, bool want_distmap = true, bool streams_chosen = false,
-                  bool clear_in_combine = false) {
-  if (!streams_chosen) choose_streams(c);
+int stage_diffmap(gz_ctx* c, const ChainStreams& cs, const Psycho& p0, const Psycho& p1, unsigned want, ClearMax clear) {
   const float hf_asymmetry_ = 0.8f;
-  // side stream: SameNoise blur + the mask branch; main stream: Malta
-  TRY(fork_side_branch(c, p0, p1));
+  // side streams: SameNoise blur + the mask branch; main stream: Malta
+  TRY(fork_side_branch(c, cs, p0, p1));
   MaltaSpec ms[2][3];
   malta_specs(ms);
   dim3 mgrid(gz_div_up(c->w, MW), gz_div_up(c->h, MH), 2);
@@ -447,16 +403,15 @@ int stage_diffmap(gz_ctx* c, const Psycho& p0, const Psycho& p1, bool want_block
     a.pass[2] = {p0.mf[ch], p1.mf[ch], ms[ch][2].nm, ms[ch][2].lf};
     a.out = c->ac[ch];
   }
-  GZ_LAUNCH((k_malta_rolled<3>), mgrid, dim3(256), c->stream, ay, ax, c->w, c->h, c->pitch);
+  GZ_LAUNCH((k_malta_rolled<3>), mgrid, dim3(256), cs.main, ay, ax, c->w, c->h, c->pitch);
   KCHK(c);
-  TRY(join_mask_branch(c));
+  TRY(wait_for(c, cs.side, cs.main, c->ev_join));
+  TRY(wait_for(c, cs.side2, cs.main, c->ev_join2));
   {
-    CombineArgs a;
-    a.mask_x_blur = c->mxb; a.mask_y_blur1 = c->myb1; a.mask_y_blur2 = c->myb2;
+    CombineArgs a = combine_mask_args(c, nullptr, nullptr);
     a.ac0 = c->ac[0]; a.ac1 = c->ac[1];
     a.lf0_x = p0.lfv[0]; a.lf1_x = p1.lfv[0];
     a.lf0_b = p0.lfv[2]; a.lf1_b = p1.lfv[2];
-    a.luts = c->d_mask_luts;
     const double wmul1 = 32.4449876135;
     a.sn_blur = c->snb;
     a.hf0_y = p0.hf[1];
@@ -465,18 +420,15 @@ int stage_diffmap(gz_ctx* c, const Psycho& p0, const Psycho& p1, bool want_block
     a.w_0gt1 = (wmul1 * hf_asymmetry_) * 0.8;   // L2DiffAsymmetric: w *= 0.8 (:678-679)
     a.w_0lt1 = (wmul1 / hf_asymmetry_) * 0.8;
     a.out = c->dsq;
-    for (int i = 0; i < 3; ++i) a.mask_out[i] = a.mask_dc_out[i] = nullptr;
-    a.clear_word = clear_in_combine ? c->d_max_bits : nullptr;
-    dim3 grid(gz_div_up(c->w, 1024), c->h);   // (4 pixels per thread)
-    GZ_LAUNCH(k_combine, grid, dim3(256), c->stream, a, c->w, c->h, c->pitch);
-    KCHK(c);
+    a.clear_word = clear == ClearMax::kCombine ? c->d_max_bits : nullptr;
+    TRY(launch_combine(c, cs.main, a));
   }
   {  // CalculateDiffmap second half: blur(sigma 1.725, border_ratio 1.0) + mix
     SrcPack<SrcPlain, 1> s; s.s[0].p = c->dsq;
-    PostDiffmapMix post; post.d = c->dsq; post.out = want_distmap ? c->distmap : nullptr;
-    if (!max_cleared && !clear_in_combine) HIPCHK(c, hipMemsetAsync(c->d_max_bits, 0, sizeof(unsigned), c->stream));
-    BlockMaxOut bm{want_block_max ? c->d_block_max : nullptr, c->d_max_bits, c->bw, nullptr};
-    TRY((blur2d<3, 1, SrcPlain, PostDiffmapMix, true>(c, s, post, c->blur[B_FINAL], bm)));
+    PostDiffmapMix post; post.d = c->dsq; post.out = (want & kWantDistmap) ? c->distmap : nullptr;
+    if (clear == ClearMax::kMemset) HIPCHK(c, hipMemsetAsync(c->d_max_bits, 0, sizeof(unsigned), cs.main));
+    BlockMaxOut bm{(want & kWantBlockMax) ? c->d_block_max : nullptr, c->d_max_bits, c->bw, nullptr};
+    TRY((blur2d<3, 1, SrcPlain, PostDiffmapMix, true>(c, cs.main, s, post, c->blur[B_FINAL], bm)));
   }
   return GZ_OK;
 }
@@ -509,20 +461,20 @@ int enqueue_scan_offsets(gz_ctx* c, int which, hipStream_t stream, const unsigne
   return GZ_OK;
 }
 
-int stage_chroma_samples(gz_ctx* c, const int16_t* d_coeffs) {
+int stage_chroma_samples(gz_ctx* c, hipStream_t stream, const int16_t* d_coeffs) {
   if (!c->d_csamp) HIPCHK(c, pool_malloc((void**)&c->d_csamp, 2 * csamp_plane(c)));
-  GZ_LAUNCH(k_chroma_samples, dim3(gz_div_up(c->nbc, kBlocksPerWG)), dim3(256), c->stream,
+  GZ_LAUNCH(k_chroma_samples, dim3(gz_div_up(c->nbc, kBlocksPerWG)), dim3(256), stream,
             d_coeffs + (size_t)c->coff[1] * 64, d_coeffs + (size_t)c->coff[2] * 64, c->cbw, c->nbc,
             c->d_csamp);
   KCHK(c);
   return GZ_OK;
 }
 
-int stage_reconstruct(gz_ctx* c, const int16_t* d_coeffs, float* lin0, uint8_t* srgb,
+int stage_reconstruct(gz_ctx* c, hipStream_t stream, const int16_t* d_coeffs, float* lin0, uint8_t* srgb,
                       unsigned* clear_word = nullptr) {
   if (c->cfac == 2) {
-    TRY(stage_chroma_samples(c, d_coeffs));
-    GZ_LAUNCH(k_reconstruct420, dim3(c->bh * gz_div_up(c->bw, 8)), dim3(256), c->stream,
+    TRY(stage_chroma_samples(c, stream, d_coeffs));
+    GZ_LAUNCH(k_reconstruct420, dim3(c->bh * gz_div_up(c->bw, 8)), dim3(256), stream,
               d_coeffs, (const uint8_t*)c->d_csamp, c->w, c->h, c->bw, c->nb, c->cbw, c->cbh,
               c->pitch, c->plane, c->d_srgb_lut, lin0, srgb, clear_word);
     KCHK(c);
@@ -535,100 +487,103 @@ int stage_reconstruct(gz_ctx* c, const int16_t* d_coeffs, float* lin0, uint8_t* 
 #ifdef GZ_EMU
   if (const char* e = getenv("GZ_EMU_RECON_STRIPS")) per = std::max(1, atoi(e));   // (the strip loop on images the emulation can afford)
 #endif
-  GZ_LAUNCH(k_reconstruct, dim3(c->bh * gz_div_up(strips, per)), dim3(256), c->stream,
+  GZ_LAUNCH(k_reconstruct, dim3(c->bh * gz_div_up(strips, per)), dim3(256), stream,
             d_coeffs, c->w, c->h, c->bw, c->nb, c->pitch, c->plane, c->d_srgb_lut, lin0,
             srgb, clear_word, per);
   KCHK(c);
   return GZ_OK;
 }
 
-// One full Compare of the current candidate, everything on the stream.
-// want_distmap = false (the search loop, gz_time_compare): the last kernel leaves the per-block maxima and the
-// image maximum only; c->distmap then holds no distance map (have_distmap_plane).
-// The candidate's linear planes: reconstructed here, unless every change of the candidate since the last full
-// reconstruction was patched into them by the call that made it (c->lin_is_cand; the search loop's steady state:
-// a fifth of a 4K image's blocks change per iteration).  force_full: gz_time_compare, whose repetitions change
-// nothing and must not measure a chain without its first kernel.
+// ---------------------------------------------------------------- the self-checks -----
+// (gz_config.patch_reconstruct == 2) What the calls between two Compares kept current is compared, word for word, with
+// the same planes computed as a whole.  WordDiff: three scratch planes for the whole computation and the device's
+// count of differing 32-bit words, from the pool for the length of a check.
 static std::atomic<unsigned long long> g_compares{0}, g_compares_patched{0}, g_patch_checks{0};   // gz_compare_counters
 static std::atomic<unsigned long long> g_compares_ahead{0}, g_ahead_checks{0};
-static int check_patched_planes(gz_ctx* c) {   // (gz_config.patch_reconstruct == 2)
-  float* full = nullptr;
+struct WordDiff {
+  float* planes = nullptr;
   unsigned* d_bad = nullptr;
-  HIPCHK(c, pool_malloc((void**)&full, sizeof(float) * c->plane * 3));
-  HIPCHK(c, pool_malloc((void**)&d_bad, sizeof(unsigned)));
-  int rc = GZ_OK;
+  WordDiff() = default;
+  WordDiff(const WordDiff&) = delete;
+  WordDiff& operator=(const WordDiff&) = delete;
+  ~WordDiff() { (void)pool_free(planes); (void)pool_free(d_bad); }
+};
+static int word_diff_begin(gz_ctx* c, hipStream_t stream, WordDiff* wd) {
+  HIPCHK(c, pool_malloc((void**)&wd->planes, sizeof(float) * c->plane * 3));
+  HIPCHK(c, pool_malloc((void**)&wd->d_bad, sizeof(unsigned)));
+  HIPCHK(c, hipMemsetAsync(wd->d_bad, 0, sizeof(unsigned), stream));
+  return GZ_OK;
+}
+static void word_diff_count(hipStream_t stream, const WordDiff& wd, const float* a, const float* b, size_t words) {
+  unsigned* d_bad = wd.d_bad;
+  GZ_LAUNCH(k_count_differing_words, dim3(1024), dim3(256), stream, (const unsigned*)a, (const unsigned*)b, words, d_bad);
+}
+static int word_diff_end(gz_ctx* c, hipStream_t stream, const WordDiff& wd, unsigned* bad) {
+  HIPCHK(c, hipMemcpyAsync(bad, wd.d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  HIPCHK(c, hipStreamSynchronize(stream));
+  return GZ_OK;
+}
+// lin[] as the patches left it against a full reconstruction of the candidate.
+static int check_patched_planes(gz_ctx* c, hipStream_t stream) {
+  WordDiff wd;
   unsigned bad = 0;
-  do {
-    if (hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream) != hipSuccess) { rc = GZ_E_HIP; break; }
-    const int strips = gz_div_up(c->bw, kReconBlocks);
-    GZ_LAUNCH(k_reconstruct, dim3(c->bh * strips), dim3(256), c->stream, (const int16_t*)c->d_cand, c->w, c->h, c->bw, c->nb,
-              c->pitch, c->plane, (const float*)c->d_srgb_lut, full, (uint8_t*)nullptr, (unsigned*)nullptr, 1);
-    GZ_LAUNCH(k_count_differing_words, dim3(1024), dim3(256), c->stream, (const unsigned*)c->lin[0], (const unsigned*)full,
-              (size_t)c->plane * 3, d_bad);
-    if (hipMemcpyAsync(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) { rc = GZ_E_HIP; break; }
-  } while (0);
-  (void)pool_free(full);
-  (void)pool_free(d_bad);
-  TRY(rc);
+  TRY(word_diff_begin(c, stream, &wd));
+  float* full = wd.planes;
+  const int strips = gz_div_up(c->bw, kReconBlocks);
+  GZ_LAUNCH(k_reconstruct, dim3(c->bh * strips), dim3(256), stream, (const int16_t*)c->d_cand, c->w, c->h, c->bw, c->nb,
+            c->pitch, c->plane, (const float*)c->d_srgb_lut, full, (uint8_t*)nullptr, (unsigned*)nullptr, 1);
+  word_diff_count(stream, wd, c->lin[0], full, (size_t)c->plane * 3);
+  TRY(word_diff_end(c, stream, wd, &bad));
   ++g_patch_checks;
   if (bad) { c->err = "patched linear planes differ from a full reconstruction"; return GZ_E_STATE; }
   return GZ_OK;
 }
-
-// (gz_config.patch_reconstruct == 2) xyb[] as the calls kept it against the opsin blur of lin[] as a whole.
-static int check_opsin_ahead(gz_ctx* c) {
-  float* kept = nullptr;
-  unsigned* d_bad = nullptr;
-  HIPCHK(c, pool_malloc((void**)&kept, sizeof(float) * c->plane * 3));
-  HIPCHK(c, pool_malloc((void**)&d_bad, sizeof(unsigned)));
-  int rc = GZ_OK;
+// xyb[] as the calls kept it against the opsin blur of lin[] as a whole.
+static int check_opsin_ahead(gz_ctx* c, hipStream_t stream) {
+  WordDiff wd;
   unsigned bad = 0;
-  do {
-    if (hipMemsetAsync(d_bad, 0, sizeof(unsigned), c->stream) != hipSuccess) { rc = GZ_E_HIP; break; }
-    for (int i = 0; i < 3 && rc == GZ_OK; ++i)
-      if (hipMemcpyAsync(kept + (size_t)i * c->plane, c->xyb[i], sizeof(float) * c->plane, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = GZ_E_HIP;
-    if (rc != GZ_OK) break;
-    rc = stage_opsin(c);
-    if (rc != GZ_OK) break;
-    for (int i = 0; i < 3; ++i)
-      GZ_LAUNCH(k_count_differing_words, dim3(1024), dim3(256), c->stream, (const unsigned*)c->xyb[i],
-                (const unsigned*)(kept + (size_t)i * c->plane), (size_t)c->plane, d_bad);
-    if (hipMemcpyAsync(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) { rc = GZ_E_HIP; break; }
-  } while (0);
-  (void)pool_free(kept);
-  (void)pool_free(d_bad);
-  TRY(rc);
+  TRY(word_diff_begin(c, stream, &wd));
+  for (int i = 0; i < 3; ++i)
+    HIPCHK(c, hipMemcpyAsync(wd.planes + (size_t)i * c->plane, c->xyb[i], sizeof(float) * c->plane, hipMemcpyDeviceToDevice, stream));
+  TRY(stage_opsin(c, stream));
+  for (int i = 0; i < 3; ++i) word_diff_count(stream, wd, c->xyb[i], wd.planes + (size_t)i * c->plane, (size_t)c->plane);
+  TRY(word_diff_end(c, stream, wd, &bad));
   ++g_ahead_checks;
   if (bad) { c->err = "the opsin image kept ahead differs from the opsin blur of the whole planes"; return GZ_E_STATE; }
   return GZ_OK;
 }
 
-int enqueue_compare(gz_ctx* c, bool want_block_max, bool want_distmap = false, bool force_full = false) {
-  want_distmap = want_distmap || c->cfg.store_distmap != 0;   // (1: the chain as it was until round 5, A/B)
-  choose_streams(c);
+// One full Compare of the current candidate, everything on the stream (and, forked, the two side streams).
+// want without kWantDistmap (the search loop, gz_time_compare): the last kernel leaves the per-block maxima and the
+// image maximum only; c->distmap then holds no distance map (have_distmap_plane).
+// The candidate's linear planes: reconstructed here, unless every change of the candidate since the last full
+// reconstruction was patched into them by the call that made it (c->lin_is_cand; the search loop's steady state:
+// a fifth of a 4K image's blocks change per iteration).  kWholeChain: gz_time_compare, whose repetitions change
+// nothing and must not measure a chain without its first kernel.
+int enqueue_compare(gz_ctx* c, unsigned want) {
+  if (c->cfg.store_distmap != 0) want |= kWantDistmap;   // (1: the chain as it was until round 5, A/B)
+  c->compare_forked = !single_stream_wanted(c);
+  const ChainStreams cs = chain_streams(c, c->compare_forked);
   ++g_compares;
-  const bool patched = !force_full && c->cfg.patch_reconstruct != 0 && c->lin_is_cand && c->cfac == 1;
+  const bool patched = !(want & kWholeChain) && c->cfg.patch_reconstruct != 0 && c->lin_is_cand && c->cfac == 1;
   if (patched) {
-    if (c->cfg.patch_reconstruct == 2) TRY(check_patched_planes(c));
+    if (c->cfg.patch_reconstruct == 2) TRY(check_patched_planes(c, cs.main));
     ++g_compares_patched;
   } else {
-    TRY(stage_reconstruct(c, c->d_cand, c->lin[0], nullptr, c->d_max_bits));
+    TRY(stage_reconstruct(c, cs.main, c->d_cand, c->lin[0], nullptr, c->d_max_bits));
     c->lin_is_cand = c->cfac == 1 && c->cfg.patch_reconstruct != 0 && (c->nb >= 8192 || c->cfg.patch_reconstruct == 2);
   }
   // ... and their opsin image, when the same calls have kept that current too (xyb_is_cand; consumed here)
   const bool ahead = patched && c->xyb_is_cand;
   c->xyb_is_cand = false;
   if (ahead) {
-    if (c->cfg.patch_reconstruct == 2) TRY(check_opsin_ahead(c));
+    if (c->cfg.patch_reconstruct == 2) TRY(check_opsin_ahead(c, cs.main));
     ++g_compares_ahead;
   } else {
-    TRY(stage_opsin(c));
+    TRY(stage_opsin(c, cs.main));
   }
-  TRY(stage_separate(c, &c->pi1, !single_stream(c)));
-  TRY(stage_diffmap(c, c->pi0, c->pi1, want_block_max, !patched, want_distmap, true, patched));
-  return GZ_OK;
+  TRY(stage_separate(c, cs, &c->pi1));
+  return stage_diffmap(c, cs, c->pi0, c->pi1, want, patched ? ClearMax::kCombine : ClearMax::kReconstruction);
 }
 
 int upload_planes(gz_ctx* c, const float* host, float* const* dev, int n) {
@@ -662,106 +617,26 @@ int ensure_block_mask(gz_ctx* c) {
   if (c->have_block_mask) return GZ_OK;
   TRY(ensure_pip(c));
   if (!c->d_block_mask) HIPCHK(c, pool_malloc((void**)&c->d_block_mask, sizeof(float) * 3 * c->nb));
+  const hipStream_t stream = c->stream;
   dim3 grid(gz_div_up(c->w, 256), c->h);
   c->lin_is_cand = c->xyb_is_cand = false;   // (lin[] takes the original)
-  GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), c->stream, c->d_rgb, c->w, c->h, c->pitch,
+  GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), stream, c->d_rgb, c->w, c->h, c->pitch,
             c->plane, c->d_srgb_lut, c->lin[0]);
   KCHK(c);
-  TRY(stage_opsin(c));
+  TRY(stage_opsin(c, stream));
   MaskPrePack pk;
   {
     const float* const x2[2] = {c->xyb[0], c->xyb[1]};
-    TRY(mask_pack_plain(c, x2, x2, &pk));
+    TRY(mask_pack_plain(c, stream, x2, x2, &pk));
   }
-  TRY(stage_mask_blurs(c, pk));
-  CombineArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.mask_x_blur = c->mxb; ca.mask_y_blur1 = c->myb1; ca.mask_y_blur2 = c->myb2;
-  ca.luts = c->d_mask_luts;
-  for (int i = 0; i < 3; ++i) { ca.mask_out[i] = c->mask_out[i]; ca.mask_dc_out[i] = nullptr; }
-  GZ_LAUNCH(k_combine, dim3(gz_div_up(c->w, 1024), c->h), dim3(256), c->stream, ca, c->w, c->h, c->pitch);   // (4 pixels per thread)
-  KCHK(c);
-  GZ_LAUNCH(k_gather_block_corners, dim3(gz_div_up(c->nb, 256)), dim3(256), c->stream,
+  TRY(stage_mask_blurs(c, stream, stream, pk));
+  TRY(launch_combine(c, stream, combine_mask_args(c, c->mask_out, nullptr)));
+  GZ_LAUNCH(k_gather_block_corners, dim3(gz_div_up(c->nb, 256)), dim3(256), stream,
             (const float*)c->mask_out[0], (const float*)c->mask_out[1],
             (const float*)c->mask_out[2], c->pitch, c->bw, c->nb, c->d_block_mask);
   KCHK(c);
   c->have_block_mask = true;
   return GZ_OK;
-}
-
-// input_order of ComputeBlockZeroingOrder (processor.cc:381-400) for blocks [b0, b1):
-// score = |orig| * csf + bias (order.inc), std::sort ascending on the score -- done with
-// libstdc++'s std::sort on the same sequence the reference builds, because the order of
-// equal scores is implementation-defined and feeds the JPEG bytes.
-void rank_blocks(const int16_t* coeffs, const int16_t* orig, int nb, int new_model, int b0,
-                 int b1, uint8_t* cnt, uint8_t* idx /* [nb][192] */) {
-  static const uint8_t oldCsf[64] = {
-      10, 10, 20, 40, 60, 70, 80, 90, 10, 20, 30, 60, 70, 80, 90, 90,
-      20, 30, 60, 70, 80, 90, 90, 90, 40, 60, 70, 80, 90, 90, 90, 90,
-      60, 70, 80, 90, 90, 90, 90, 90, 70, 80, 90, 90, 90, 90, 90, 90,
-      80, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90};
-  static const int zigzag[64] = {   // kJPEGZigZagOrder, jpeg_data.h:75-84
-      0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42,
-      3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
-      10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
-      21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
-  static const double kWeight[3] = {1.0, 0.22, 0.20};
-  std::vector<std::pair<int, float> > order;
-  order.reserve(192);
-  for (int b = b0; b < b1; ++b) {
-    order.clear();
-    for (int ch = 0; ch < 3; ++ch) {
-      const int16_t* blk = coeffs + ((size_t)ch * nb + b) * 64;
-      const int16_t* ob = orig + ((size_t)ch * nb + b) * 64;
-      for (int k = 1; k < 64; ++k) {
-        if (blk[k] == 0) continue;
-        const int i = ch * 64 + k;
-        float score;
-        if (new_model)
-          score = abs((int)ob[k]) * kOrderCsf[i] + kOrderBias[i];
-        else
-          score = static_cast<float>((abs((int)ob[k]) - zigzag[k] / 64.0) * kWeight[ch] / oldCsf[k]);
-        order.push_back(std::make_pair(i, score));
-      }
-    }
-    std::sort(order.begin(), order.end(),
-              [](const std::pair<int, float>& x, const std::pair<int, float>& y) {
-                return x.second < y.second; });
-    cnt[b] = (uint8_t)order.size();
-    for (size_t i = 0; i < order.size(); ++i) idx[(size_t)b * 192 + i] = (uint8_t)order[i].first;
-  }
-}
-
-void rank_all(const int16_t* coeffs, const int16_t* orig, int nb, int new_model,
-              std::vector<int32_t>* off, std::vector<uint8_t>* idx) {
-  std::vector<uint8_t> cnt(nb), wide((size_t)nb * 192);
-  // threads from the cores this PROCESS may run on (a rank of a multi-GPU job is bound to its share
-  // of the host: bench.py Env.bind_cpus), not from the machine's
-  unsigned nt = std::thread::hardware_concurrency();
-#if defined(__linux__)
-  {
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof(set), &set) == 0 && CPU_COUNT(&set) > 0) nt = (unsigned)CPU_COUNT(&set);
-  }
-#endif
-  nt = std::max(1u, std::min(nt, 32u));
-  if (nb < 4096) nt = 1;
-  std::vector<std::thread> th;
-  const int per = (nb + (int)nt - 1) / (int)nt;
-  for (unsigned t = 0; t < nt; ++t) {
-    const int b0 = (int)t * per, b1 = std::min(nb, b0 + per);
-    if (b0 >= b1) break;
-    th.emplace_back(rank_blocks, coeffs, orig, nb, new_model, b0, b1, cnt.data(), wide.data());
-  }
-  for (auto& t : th) t.join();
-  off->resize(nb + 1);
-  int total = 0;
-  for (int b = 0; b < nb; ++b) { (*off)[b] = total; total += cnt[b]; }
-  (*off)[nb] = total;
-  idx->resize(total);
-  for (int b = 0; b < nb; ++b)
-    memcpy(idx->data() + (*off)[b], wide.data() + (size_t)b * 192, cnt[b]);
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// The caching allocator and the stream / event pools, pinned staging, gz_ctx (one image on one GPU), DeviceScope, the error macros, the plane arena.
+// The caching allocator and the stream / event pools, gz_ctx (one image on one GPU), DeviceScope, the error macros, pinned staging (HostStage and its helpers, the result buffer), the plane arena.
 // (part of the one translation unit gz_api.hip, which includes these files in order; split by
 // concern in round 5 -- no declaration here is visible outside libguetzli_amd.so but the C ABI)
 #pragma once
@@ -231,6 +231,7 @@ void pool_event_destroy(hipEvent_t e_) {
 // Pinned host staging for the small per-iteration uploads (step lists, coefficient edits,
 // next_cand, Huffman codes): the caller's buffer is copied here, the H2D copy is asynchronous
 // and nobody has to wait for it -- the buffer is only waited for when it is reused.
+// (stage_reserve / stage_sent / stage_free and the result buffer: below the error macros they use)
 struct HostStage {
   void* h = nullptr;
   size_t cap = 0;
@@ -260,7 +261,7 @@ struct gz_ctx {
   // mask: DiffPrecompute + three blurs), forked and joined with events
   hipStream_t side_stream = nullptr, side_stream2 = nullptr;
   bool prio_streams = false;   // (see create_context)
-  bool single_now = false;   // (chain.h choose_streams: this Compare's kernels on the main stream only)
+  bool compare_forked = false;   // the Compare enqueued last went onto the side streams too (written by chain.h enqueue_compare only)
   gz_config cfg;             // run-time configuration (include/guetzli_amd.h): the environment's, read once at gz_create
   int slot = -1;             // the context's slot on its device (slot_take); its stream set has rotation slot % 4
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_mask_pre = nullptr;
@@ -428,6 +429,48 @@ namespace {
       return GZ_E_HIP;                                                               \
     }                                                                                \
   } while (0)
+
+// Reserves `bytes` of the staging buffer (waiting for its previous upload if that is still
+// running) and returns it; stage_sent() marks the upload that was just enqueued on `stream`.
+static int stage_reserve(gz_ctx* c, HostStage* st, size_t bytes, void** out) {
+  if (!st->ev) HIPCHK(c, pool_event_create(&st->ev));
+  if (st->busy) {
+    HIPCHK(c, hipEventSynchronize(st->ev));
+    st->busy = false;
+  }
+  if (bytes > st->cap) {
+    if (st->h) (void)pool_host_free(st->h);
+    st->h = nullptr;
+    st->cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    HIPCHK(c, pool_host_malloc(&st->h, cap));
+    st->cap = cap;
+  }
+  *out = st->h;
+  return GZ_OK;
+}
+static int stage_sent(gz_ctx* c, HostStage* st, hipStream_t stream) {
+  HIPCHK(c, hipEventRecord(st->ev, stream));
+  st->busy = true;
+  return GZ_OK;
+}
+static int result_buffer(gz_ctx* c, size_t bytes, void** out) {
+  if (bytes > c->h_res_cap) {
+    if (c->h_res) (void)pool_host_free(c->h_res);
+    c->h_res = nullptr;
+    c->h_res_cap = 0;
+    const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
+    HIPCHK(c, pool_host_malloc(&c->h_res, cap));
+    c->h_res_cap = cap;
+  }
+  *out = c->h_res;
+  return GZ_OK;
+}
+static void stage_free(HostStage* st) {
+  if (st->ev) { (void)hipEventSynchronize(st->ev); pool_event_destroy(st->ev); }
+  if (st->h) (void)pool_host_free(st->h);
+  st->h = nullptr; st->ev = nullptr; st->cap = 0; st->busy = false;
+}
 
 const int kNumPlanes = 9 + 9 + 3 + 3 + 3 + 2 + 2 + 10 + 2;   // pi0, pi1, lin, tmp, xyb, lf_raw, hfp, 10 singles, sup0[2]
 

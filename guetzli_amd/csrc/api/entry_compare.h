@@ -124,7 +124,7 @@ int gz_reconstruct(gz_ctx* c, uint8_t* srgb, float* linear) {
   if (!c) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
   if (linear) c->lin_is_cand = c->xyb_is_cand = false;   // (rewritten as a whole: nothing to keep track of)
-  TRY(stage_reconstruct(c, c->d_cand, linear ? c->lin[0] : nullptr, srgb ? c->d_srgb_out : nullptr));
+  TRY(stage_reconstruct(c, c->stream, c->d_cand, linear ? c->lin[0] : nullptr, srgb ? c->d_srgb_out : nullptr));
   if (srgb) HIPCHK(c, hipMemcpyAsync(srgb, c->d_srgb_out, (size_t)3 * c->w * c->h, hipMemcpyDeviceToHost, c->stream));
   if (linear) for (int i = 0; i < 3; ++i) TRY(download_plane(c, c->lin[i], linear + (size_t)i * c->w * c->h));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -136,7 +136,7 @@ int gz_compare(gz_ctx* c, float* distance, float* distmap, float* block_max) {
   if (!c || !distance) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
   c->have_distmap = c->h_block_max_valid = false;
-  TRY(enqueue_compare(c, true, distmap != nullptr));   // (the map is stored only for a caller that takes it)
+  TRY(enqueue_compare(c, kWantBlockMax | (distmap ? kWantDistmap : 0u)));   // (the map is stored only for a caller that takes it)
   void* res = nullptr;
   TRY(result_buffer(c, 4, &res));
   HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits, 4, hipMemcpyDeviceToHost, c->stream));
@@ -165,7 +165,7 @@ int gz_compare_begin(gz_ctx* c) {
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
   HIPCHK(c, hipEventRecord(c->ev_candidate, c->stream));   // gz_jpeg_scan waits for this only
   c->h_block_max_valid = false;
-  TRY(enqueue_compare(c, true));
+  TRY(enqueue_compare(c, kWantBlockMax));
   c->compare_pending = true;
   c->distance_in_desc = false;
   return GZ_OK;
@@ -200,7 +200,7 @@ int gz_compare_enqueue(gz_ctx* c, int iters) {
   DeviceScope ds_(c);
   if (!c || iters < 0) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
-  for (int i = 0; i < iters; ++i) TRY(enqueue_compare(c, true, false, true));   // (always the whole chain, as gz_time_compare)
+  for (int i = 0; i < iters; ++i) TRY(enqueue_compare(c, kWantBlockMax | kWholeChain));   // (always the whole chain, as gz_time_compare)
   return GZ_OK;
 }
 
@@ -222,7 +222,7 @@ int gz_time_compare(gz_ctx* c, int iters, float* total_ms) {
   HIPCHK(c, hipEventCreate(&e0));
   HIPCHK(c, hipEventCreate(&e1));
   HIPCHK(c, hipEventRecord(e0, c->stream));
-  for (int i = 0; i < iters; ++i) TRY(enqueue_compare(c, true, false, true));   // (always the whole chain)
+  for (int i = 0; i < iters; ++i) TRY(enqueue_compare(c, kWantBlockMax | kWholeChain));   // (always the whole chain)
   HIPCHK(c, hipEventRecord(e1, c->stream));
   HIPCHK(c, hipEventSynchronize(e1));
   HIPCHK(c, hipEventElapsedTime(total_ms, e0, e1));

@@ -260,12 +260,12 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), c->stream, c->d_rgb, c->w, c->h, c->pitch,
             c->plane, c->d_srgb_lut, c->lin[0]);
   KCHK(c);
-  TRY(stage_opsin(c));
-  TRY(stage_separate(c, &c->pi0));
+  TRY(stage_opsin(c, c->stream));
+  TRY(stage_separate(c, chain_streams(c, false), &c->pi0));
   {  // the original's half of every Compare's DiffPrecompute
     MaskIn in0[2];
     mask_in_psycho(c->pi0, in0);
-    TRY(stage_mask_sup(c, in0, c->sup0));
+    TRY(stage_mask_sup(c, c->stream, in0, c->sup0));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GZ_OK;

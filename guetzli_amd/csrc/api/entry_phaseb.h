@@ -147,10 +147,10 @@ static int order_auto_enqueue(gz_ctx* c, int direction, int max_block_dist, doub
     // order, the descent and the distance that arrives with them would wait for the coder
     // (ADVICE r3).  Nothing on the main stream reads d_next_cand before the order's kernels.
     // In batch mode -- the evaluation in flight was put on ONE stream because other contexts are alive (chain.h,
-    // choose_streams) -- the copy stays on the main stream too: on the side stream it shares a hardware queue with
+    // enqueue_compare) -- the copy stays on the main stream too: on the side stream it shares a hardware queue with
     // ANOTHER image's main stream and waits there behind that image's kernels, and the order with it (8 x 4K
     // 40.7 -> 43.0 MPix/s, 16 x 1080p 34.6 -> 36.2, 64 x 1 MPix 29.6 -> 32.6: r06_chain_experiments.log, section 11).
-    const bool beside = c->compare_pending && !c->single_now;
+    const bool beside = c->compare_pending && c->compare_forked;
     hipStream_t up = beside ? c->side_stream : c->stream;
     void* h = nullptr;
     TRY(stage_reserve(c, &c->stage_main, sizeof(int) * nb, &h));
@@ -374,7 +374,7 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
       // are now: 100 us (4K) of the chain's critical path that run while the host takes its serial steps, whose
       // edits then cost the tiles around them (gz_apply_coeff_edits).  Not in a batch: the other images use the time.
       ahead = c->cfg.opsin_ahead != 0 && !single_stream_wanted(c);
-      if (ahead) TRY(stage_opsin(c));
+      if (ahead) TRY(stage_opsin(c, c->stream));
     }
     claims.commit(patch, ahead);
     return GZ_OK;
@@ -465,7 +465,7 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
         }
         for (int i = 0; i < nt; ++i) c->tile_mark[(size_t)tl[i]] = 0;
       }
-      rc_tiles = tl && (long)nt * 4 <= (long)gx * gy ? stage_opsin(c, tl, nt) : stage_opsin(c);
+      rc_tiles = tl && (long)nt * 4 <= (long)gx * gy ? stage_opsin(c, c->stream, tl, nt) : stage_opsin(c, c->stream);
     }
   }
   TRY(stage_sent(c, &c->stage_edits, c->stream));   // (the staging buffer is free again behind the kernels)

@@ -16,29 +16,10 @@ int gz_probe_blur(gz_ctx* c, const float* in, float sigma, float border_ratio, f
   float* src = c->xyb[0];
   c->xyb_is_cand = false;   // (xyb[] as scratch)
   TRY(upload_planes(c, in, &src, 1));
-  SrcPack<SrcPlain, 1> s;
-  s.s[0].p = src;
+  SrcPack<SrcPlain, 1> s; s.s[0].p = src;
   PostStore<1> post; post.out[0] = c->xyb[1];
-  int rc = GZ_OK;
   // the same kernels gz_compare uses for each radius: fused below 16, two passes from 16 up
-  PlanePack<1> t; CPlanePack<1> ct;
-  t.p[0] = c->tmp[0]; ct.p[0] = c->tmp[0];
-#define GZ_BLUR_CASE(R)                                                     \
-  case R:                                                                   \
-    rc = blur2d<R, 1, SrcPlain, PostStore<1>>(c, s, post, cfg);             \
-    break;
-#define GZ_BLUR_CASE2(R)                                                    \
-  case R:                                                                   \
-    rc = blur_h<R, SrcPlain, 1>(c, s, t, cfg);                              \
-    if (rc == GZ_OK) rc = blur_v<R, 1, PostStore<1>>(c, ct, post, cfg);     \
-    break;
-  switch (cfg.r) {
-    GZ_BLUR_CASE(2) GZ_BLUR_CASE(3) GZ_BLUR_CASE(4) GZ_BLUR_CASE(5) GZ_BLUR_CASE(8)
-    GZ_BLUR_CASE2(16) GZ_BLUR_CASE2(20) GZ_BLUR_CASE2(23)
-    default: c->err = "unsupported blur radius"; rc = GZ_E_ARG;
-  }
-#undef GZ_BLUR_CASE
-#undef GZ_BLUR_CASE2
+  int rc = blur_plane(c, c->stream, s, c->tmp[0], post, cfg);
   if (rc == GZ_OK) rc = download_plane(c, c->xyb[1], out);
   (void)hipStreamSynchronize(c->stream);
   (void)pool_free(cfg.d_scale);
@@ -50,7 +31,7 @@ int gz_probe_opsin(gz_ctx* c, const float* rgb3, float* xyb3) {
   if (!c || !rgb3 || !xyb3) return GZ_E_ARG;
   c->lin_is_cand = c->xyb_is_cand = false;
   TRY(upload_planes(c, rgb3, c->lin, 3));
-  TRY(stage_opsin(c));
+  TRY(stage_opsin(c, c->stream));
   for (int i = 0; i < 3; ++i) TRY(download_plane(c, c->xyb[i], xyb3 + (size_t)i * c->w * c->h));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GZ_OK;
@@ -62,7 +43,7 @@ int gz_probe_separate_frequencies(gz_ctx* c, const float* xyb3, float* out10) {
   TRY(ensure_pip(c));
   c->xyb_is_cand = false;
   TRY(upload_planes(c, xyb3, c->xyb, 3));
-  TRY(stage_separate(c, &c->pip));
+  TRY(stage_separate(c, chain_streams(c, false), &c->pip));
   const size_t n = (size_t)c->w * c->h;
   for (int i = 0; i < 3; ++i) TRY(download_plane(c, c->pip.lfv[i], out10 + i * n));
   for (int i = 0; i < 2; ++i) TRY(download_plane(c, c->pip.mf[i], out10 + (3 + i) * n));
@@ -80,12 +61,13 @@ int gz_probe_diffmap(gz_ctx* c, const float* rgb0, const float* rgb1, float* dif
   TRY(ensure_pip(c));
   c->lin_is_cand = c->xyb_is_cand = false;
   TRY(upload_planes(c, rgb0, c->lin, 3));
-  TRY(stage_opsin(c));
-  TRY(stage_separate(c, &c->pip));
+  TRY(stage_opsin(c, c->stream));
+  TRY(stage_separate(c, chain_streams(c, false), &c->pip));
   TRY(upload_planes(c, rgb1, c->lin, 3));
-  TRY(stage_opsin(c));
-  TRY(stage_separate(c, &c->pi1));
-  TRY(stage_diffmap(c, c->pip, c->pi1, false));
+  TRY(stage_opsin(c, c->stream));
+  TRY(stage_separate(c, chain_streams(c, false), &c->pi1));
+  // (the diffmap stage alone takes the side streams, by the context's stream mode; no block maxima)
+  TRY(stage_diffmap(c, chain_streams(c, !single_stream_wanted(c)), c->pip, c->pi1, kWantDistmap, ClearMax::kMemset));
   if (diffmap) TRY(download_plane(c, c->distmap, diffmap));
   unsigned bits = 0;
   HIPCHK(c, hipMemcpyAsync(&bits, c->d_max_bits, 4, hipMemcpyDeviceToHost, c->stream));
@@ -107,17 +89,9 @@ int gz_probe_mask(gz_ctx* c, const float* xyb0, const float* xyb1, float* mask3,
   const float* const ca2[2] = {a[0], a[1]};
   const float* const cb2[2] = {b[0], b[1]};
   MaskPrePack pk;
-  TRY(mask_pack_plain(c, ca2, cb2, &pk));
-  TRY(stage_mask_blurs(c, pk));
-  CombineArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.mask_x_blur = c->mxb; ca.mask_y_blur1 = c->myb1; ca.mask_y_blur2 = c->myb2;
-  ca.luts = c->d_mask_luts;
-  ca.out = nullptr;
-  for (int i = 0; i < 3; ++i) { ca.mask_out[i] = c->mask_out[i]; ca.mask_dc_out[i] = c->mask_dc_out[i]; }
-  dim3 grid(gz_div_up(c->w, 1024), c->h);   // (4 pixels per thread)
-  GZ_LAUNCH(k_combine, grid, dim3(256), c->stream, ca, c->w, c->h, c->pitch);
-  KCHK(c);
+  TRY(mask_pack_plain(c, c->stream, ca2, cb2, &pk));
+  TRY(stage_mask_blurs(c, c->stream, c->stream, pk));
+  TRY(launch_combine(c, c->stream, combine_mask_args(c, c->mask_out, c->mask_dc_out)));
   const size_t n = (size_t)c->w * c->h;
   for (int i = 0; i < 3; ++i) {
     TRY(download_plane(c, c->mask_out[i], mask3 + i * n));

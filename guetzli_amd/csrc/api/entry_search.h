@@ -1,10 +1,86 @@
-// C ABI: phase A -- candidate ranking, the per-block zeroing search for every component mask and frame, CompareBlock for independent blocks (the Comparator seam).
+// C ABI: phase A -- candidate ranking (on the host: rank_blocks / rank_all, and on the device), the per-block zeroing search for every component mask and frame, CompareBlock for independent blocks (the Comparator seam).
 // (part of the one translation unit gz_api.hip, which includes these files in order; split by
 // concern in round 5 -- no declaration here is visible outside libguetzli_amd.so but the C ABI)
 #pragma once
 
-extern "C" {
+namespace {
+// input_order of ComputeBlockZeroingOrder (processor.cc:381-400) for blocks [b0, b1):
+// score = |orig| * csf + bias (order.inc), std::sort ascending on the score -- done with
+// libstdc++'s std::sort on the same sequence the reference builds, because the order of
+// equal scores is implementation-defined and feeds the JPEG bytes.
+void rank_blocks(const int16_t* coeffs, const int16_t* orig, int nb, int new_model, int b0,
+                 int b1, uint8_t* cnt, uint8_t* idx /* [nb][192] */) {
+  static const uint8_t oldCsf[64] = {
+      10, 10, 20, 40, 60, 70, 80, 90, 10, 20, 30, 60, 70, 80, 90, 90,
+      20, 30, 60, 70, 80, 90, 90, 90, 40, 60, 70, 80, 90, 90, 90, 90,
+      60, 70, 80, 90, 90, 90, 90, 90, 70, 80, 90, 90, 90, 90, 90, 90,
+      80, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90, 90};
+  static const int zigzag[64] = {   // kJPEGZigZagOrder, jpeg_data.h:75-84
+      0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42,
+      3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
+      10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
+      21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+  static const double kWeight[3] = {1.0, 0.22, 0.20};
+  std::vector<std::pair<int, float> > order;
+  order.reserve(192);
+  for (int b = b0; b < b1; ++b) {
+    order.clear();
+    for (int ch = 0; ch < 3; ++ch) {
+      const int16_t* blk = coeffs + ((size_t)ch * nb + b) * 64;
+      const int16_t* ob = orig + ((size_t)ch * nb + b) * 64;
+      for (int k = 1; k < 64; ++k) {
+        if (blk[k] == 0) continue;
+        const int i = ch * 64 + k;
+        float score;
+        if (new_model)
+          score = abs((int)ob[k]) * kOrderCsf[i] + kOrderBias[i];
+        else
+          score = static_cast<float>((abs((int)ob[k]) - zigzag[k] / 64.0) * kWeight[ch] / oldCsf[k]);
+        order.push_back(std::make_pair(i, score));
+      }
+    }
+    std::sort(order.begin(), order.end(),
+              [](const std::pair<int, float>& x, const std::pair<int, float>& y) {
+                return x.second < y.second; });
+    cnt[b] = (uint8_t)order.size();
+    for (size_t i = 0; i < order.size(); ++i) idx[(size_t)b * 192 + i] = (uint8_t)order[i].first;
+  }
+}
 
+void rank_all(const int16_t* coeffs, const int16_t* orig, int nb, int new_model,
+              std::vector<int32_t>* off, std::vector<uint8_t>* idx) {
+  std::vector<uint8_t> cnt(nb), wide((size_t)nb * 192);
+  // threads from the cores this PROCESS may run on (a rank of a multi-GPU job is bound to its share
+  // of the host: bench.py Env.bind_cpus), not from the machine's
+  unsigned nt = std::thread::hardware_concurrency();
+#if defined(__linux__)
+  {
+    cpu_set_t set;
+    CPU_ZERO(&set);
+    if (sched_getaffinity(0, sizeof(set), &set) == 0 && CPU_COUNT(&set) > 0) nt = (unsigned)CPU_COUNT(&set);
+  }
+#endif
+  nt = std::max(1u, std::min(nt, 32u));
+  if (nb < 4096) nt = 1;
+  std::vector<std::thread> th;
+  const int per = (nb + (int)nt - 1) / (int)nt;
+  for (unsigned t = 0; t < nt; ++t) {
+    const int b0 = (int)t * per, b1 = std::min(nb, b0 + per);
+    if (b0 >= b1) break;
+    th.emplace_back(rank_blocks, coeffs, orig, nb, new_model, b0, b1, cnt.data(), wide.data());
+  }
+  for (auto& t : th) t.join();
+  off->resize(nb + 1);
+  int total = 0;
+  for (int b = 0; b < nb; ++b) { (*off)[b] = total; total += cnt[b]; }
+  (*off)[nb] = total;
+  idx->resize(total);
+  for (int b = 0; b < nb; ++b)
+    memcpy(idx->data() + (*off)[b], wide.data() + (size_t)b * 192, cnt[b]);
+}
+}  // namespace
+
+extern "C" {
 
 int gz_rank_zeroing_candidates(const int16_t* coeffs, const int16_t* orig, int nb,
                                int new_model, int32_t* offsets, uint8_t* idx) {
@@ -73,7 +149,7 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
   a.cbw = c->cbw;
   a.samples = nullptr;
   if (mode != 0) {   // the chroma samples of the image as it stands
-    TRY(stage_chroma_samples(c, c->d_cand));
+    TRY(stage_chroma_samples(c, c->stream, c->d_cand));
     a.samples = c->d_csamp;
   }
   a.lookahead = lookahead;

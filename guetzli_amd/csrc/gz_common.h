@@ -8,8 +8,11 @@
 
 #ifdef GZ_EMU
 #include "hip_emu.h"
+#ifndef GZ_EMU_LOG_LAUNCH   // (an emulation header that keeps no enqueue log)
+#define GZ_EMU_LOG_LAUNCH(kern, grid, block, stream) ((void)0)
+#endif
 #define GZ_LAUNCH(kern, grid, block, stream, ...) \
-  hipemu::launch((grid), (block), [=]() { kern(__VA_ARGS__); })
+  (GZ_EMU_LOG_LAUNCH(#kern, (grid), (block), (stream)), hipemu::launch((grid), (block), [=]() { kern(__VA_ARGS__); }))
 #else
 #include <hip/hip_runtime.h>
 #define GZ_LAUNCH(kern, grid, block, stream, ...) \

@@ -30,6 +30,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 struct dim3 {
@@ -118,6 +119,43 @@ inline void fiber_init(int t) {
   makecontext(&s.fibers[t], (void (*)())fiber_entry, 0);
 #endif
 }
+// The enqueue log (tests/test_enqueue_order.py), opt-in like the fault injection below: between gz_emu_enqueue_log_start()
+// and _stop() every launch, event record / wait, asynchronous copy / fill and synchronise adds one line, in call order.
+// Streams and events are named by their first appearance in the log (s0, s1, ..., e0, ...), so a log does not depend
+// on what ran before it.  It records what was enqueued where; it models no ordering.
+struct EnqueueLog {
+  std::mutex mu;
+  bool on = false;
+  std::string text;
+  std::vector<const void*> streams, events;
+};
+inline EnqueueLog& enqueue_log() { static EnqueueLog l; return l; }
+inline std::string log_name(std::vector<const void*>& seen, char prefix, const void* handle) {
+  const size_t i = std::find(seen.begin(), seen.end(), handle) - seen.begin();
+  if (i == seen.size()) seen.push_back(handle);
+  return prefix + std::to_string(i);
+}
+// One line: `what`, then " s<k>" / " e<k>" for the handles given in the order of `order` ("se", "es", "s", "e").
+inline void log_enqueue(const std::string& what, const char* order, const void* stream, const void* event) {
+  EnqueueLog& l = enqueue_log();
+  std::lock_guard<std::mutex> lk(l.mu);
+  if (!l.on) return;
+  l.text += what;
+  for (; *order; ++order)
+    l.text += " " + (*order == 's' ? log_name(l.streams, 's', stream) : log_name(l.events, 'e', event));
+  l.text += "\n";
+}
+inline void log_launch(const char* kern, dim3 grid, dim3 block, const void* stream) {
+  std::string name;   // the kernel's base name: `kern` up to its template arguments, without parentheses
+  for (const char* p = kern; *p && *p != '<'; ++p)
+    if (*p != '(' && *p != ')' && *p != ' ') name += *p;
+  log_enqueue("launch " + name + " grid " + std::to_string(grid.x) + "x" + std::to_string(grid.y) + "x" + std::to_string(grid.z) +
+                  " block " + std::to_string(block.x), "s", stream, nullptr);
+}
+}  // namespace hipemu
+// (GZ_LAUNCH's emulation arm, gz_common.h: the kernel's text and the stream, in front of the launch itself)
+#define GZ_EMU_LOG_LAUNCH(kern, grid, block, stream) hipemu::log_launch((kern), (grid), (block), (stream))
+namespace hipemu {
 // Launch fault injection (tests/test_hip_failures.py), in the style of gz_emu_fail_alloc below: every launch is
 // counted; gz_emu_fail_launch(n) makes the (n + 1)-th launch from now on not run its body (once), and the next
 // hipGetLastError() then returns a launch failure (once).  (Launches run on one thread: no lock.)
@@ -324,6 +362,24 @@ extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_fail_
   b.fail_at = n < 0 ? -1 : b.calls + n;
 }
 extern "C" __attribute__((used, visibility("default"))) inline long gz_emu_launch_calls(void) { return hipemu::launch_book().calls; }
+extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_enqueue_log_start(void) {
+  hipemu::EnqueueLog& l = hipemu::enqueue_log();
+  std::lock_guard<std::mutex> lk(l.mu);
+  l.on = true;
+  l.text.clear(); l.streams.clear(); l.events.clear();
+}
+extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_enqueue_log_stop(void) {
+  hipemu::EnqueueLog& l = hipemu::enqueue_log();
+  std::lock_guard<std::mutex> lk(l.mu);
+  l.on = false;
+}
+// Copies up to cap bytes of the log's text to `out`; returns the text's length.
+extern "C" __attribute__((used, visibility("default"))) inline long gz_emu_enqueue_log_fetch(char* out, long cap) {
+  hipemu::EnqueueLog& l = hipemu::enqueue_log();
+  std::lock_guard<std::mutex> lk(l.mu);
+  if (out && cap > 0) memcpy(out, l.text.data(), std::min((size_t)cap, l.text.size()));
+  return (long)l.text.size();
+}
 extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_live(long* device_bytes, long* host_bytes, long* blocks,
                                                                                 long* events) {
   hipemu::AllocBook& b = hipemu::alloc_book();
@@ -368,19 +424,38 @@ inline hipError_t hipHostFree(void* p) {
   return hipSuccess;
 }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t stream) {
+  static const char* const kinds[] = {"h2d", "d2h", "d2d", "h2h", "default"};
+  hipemu::log_enqueue(std::string("memcpy ") + kinds[kind] + " " + std::to_string(n), "s", stream, nullptr);
+  memcpy(d, s, n);
+  return hipSuccess;
+}
 inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
-inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return hipSuccess; }
+inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t stream) {
+  hipemu::log_enqueue("memset " + std::to_string(n), "s", stream, nullptr);
+  memset(d, v, n);
+  return hipSuccess;
+}
+// (distinct non-null handles, so that host code that compares streams takes the device's branch; nothing dereferences one)
+inline hipError_t hipStreamCreate(hipStream_t* s) {
+  static uintptr_t made = 0;
+  std::lock_guard<std::mutex> lk(hipemu::alloc_book().mu);
+  *s = (hipStream_t)(++made);
+  return hipSuccess;
+}
 inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t stream) { hipemu::log_enqueue("stream_sync", "s", stream, nullptr); return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 inline void hipemu_count_event(int d) { hipemu::AllocBook& b = hipemu::alloc_book(); std::lock_guard<std::mutex> lk(b.mu); b.events += d; }
 inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipEmuEvent; hipemu_count_event(+1); return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hipemu_count_event(-1); delete e; return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
-inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t stream) {
+  hipemu::log_enqueue("record", "es", stream, e);
+  e->t = std::chrono::steady_clock::now();
+  return hipSuccess;
+}
+inline hipError_t hipEventSynchronize(hipEvent_t e) { hipemu::log_enqueue("event_sync", "e", nullptr, e); return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t stream, hipEvent_t e, unsigned) { hipemu::log_enqueue("wait", "se", stream, e); return hipSuccess; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hipEmuEvent; hipemu_count_event(+1); return hipSuccess; }
 enum { hipEventDisableTiming = 2 };
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
