@@ -528,6 +528,49 @@ class Context:
         self._chk(self.L.lib.gz_order_build_auto_end(self.handle, _ptr(total), _ptr(btc), _ptr(below)))
         return int(total[0]), int(btc[0]), int(below[0])
 
+    def order_build_auto_descend_begin(self, direction, max_block_dist, target_mul, use_distmap, next_cand,
+                                       per_block, threshold, max_levels, limit=None):
+        nc = np.ascontiguousarray(next_cand, np.int32)
+        assert nc.size == getattr(self, "search_blocks", self.nb)
+        self._chk(self.L.lib.gz_order_build_auto_descend_begin(self.handle, direction, max_block_dist, target_mul,
+                                                               int(use_distmap), _ptr(nc), int(limit is not None),
+                                                               float(limit or 0.0), float(per_block), int(threshold),
+                                                               int(max_levels)))
+
+    def order_descend(self, last, threshold, max_levels):
+        """The cut log [levels][3] = (lo, hi, cut) of the partitions made."""
+        log = np.zeros((max(max_levels, 1), 3), np.uint64)
+        levels = np.zeros(1, np.int32)
+        self._chk(self.L.lib.gz_order_descend(self.handle, int(last), int(threshold), int(max_levels), _ptr(log),
+                                              _ptr(levels)))
+        return log[:int(levels[0])].copy()
+
+    def order_descend_begin(self, per_block, threshold, max_levels):
+        self._chk(self.L.lib.gz_order_descend_begin(self.handle, float(per_block), int(threshold), int(max_levels)))
+
+    def order_descend_end(self, cap_levels=12):
+        """(cut log [levels][3], last): the position the device derived and descended to."""
+        log = np.zeros((max(cap_levels, 1), 3), np.uint64)
+        levels = np.zeros(1, np.int32)
+        last = np.zeros(1, np.uint64)
+        self._chk(self.L.lib.gz_order_descend_end(self.handle, _ptr(log), int(cap_levels), _ptr(levels), _ptr(last)))
+        return log[:int(levels[0])].copy(), int(last[0])
+
+    def order_exported(self):
+        n = np.zeros(1, np.uint64)
+        self._chk(self.L.lib.gz_order_exported(self.handle, _ptr(n)))
+        return int(n[0])
+
+    def order_host_mirror(self, entries):
+        """The context's page-locked copy of the order, grown to `entries`: a view that lives as long as the context
+        does and no later order_host_mirror asks for more."""
+        p = C.c_void_p()
+        self._chk(self.L.lib.gz_order_host_mirror(self.handle, int(entries), C.byref(p)))
+        if not p.value or entries == 0:
+            return np.zeros(0, self.ORDER_DTYPE)
+        buf = (C.c_char * (self.ORDER_DTYPE.itemsize * int(entries))).from_address(p.value)
+        return np.frombuffer(buf, self.ORDER_DTYPE)
+
     def order_advance(self, val_threshold, direction):
         self._chk(self.L.lib.gz_order_advance(self.handle, float(val_threshold), direction))
 
@@ -559,8 +602,11 @@ class Context:
         self._chk(self.L.lib.gz_order_partition(self.handle, lo, hi, _ptr(cut)))
         return int(cut[0])
 
-    def order_fetch(self, lo, hi):
-        out = np.zeros(hi - lo, self.ORDER_DTYPE)
+    def order_fetch(self, lo, hi, out=None):
+        """Entries [lo, hi) into `out` (a view of order_host_mirror's array lands without a second copy)."""
+        if out is None:
+            out = np.zeros(hi - lo, self.ORDER_DTYPE)
+        assert out.dtype == self.ORDER_DTYPE and out.size >= hi - lo
         self._chk(self.L.lib.gz_order_fetch(self.handle, lo, hi, _ptr(out)))
         return out
 

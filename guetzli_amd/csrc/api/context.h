@@ -239,6 +239,40 @@ struct HostStage {
   bool busy = false;
 };
 
+// What is in flight between a _begin and its _end: phase B's order, the descent enqueued behind it, and the Compare
+// whose distance may arrive with them.  The transitions are the only writers (entry_phaseb.h, entry_compare.h, set_frame).
+struct Pending {
+  enum Landing { kNoOrder, kOwnBuffer, kResultsSlot };   // the order's results land in h_order_results / h_desc[kDescResultsSlot]
+  enum Distance { kNoCompare, kMaxBits, kWithResults };  // gz_compare_end copies d_max_bits / finds the distance in the results slot too
+  // how much a call makes void: the order and the descent behind it (gz_order_build_auto_end fails, gz_order_descend_end
+  // returns nothing), the distance's ride with them too, and (a new frame) the Compare and the exported prefix as well
+  enum Void { kOrder, kRide, kEverything };
+  Landing order = kNoOrder;
+  Distance compare = kNoCompare;
+  int levels = -1;         // of the pending descent (-1: none)
+  unsigned epoch = 0;      // the descent enqueued last (0: none yet): what its states in h_desc carry
+  unsigned published = 0;  // the descent whose results slot the order's results and the distance are in
+  bool exported = false;   // descent `epoch` ran k_desc_export into the host mirror
+  bool busy() const { return order != kNoOrder || levels >= 0 || compare != kNoCompare; }
+  unsigned next_epoch() { exported = false; if (++epoch == 0) epoch = 1; return epoch; }
+  void compare_begun() { compare = kMaxBits; }
+  void order_begun(Landing where) { order = where; }
+  // published: its first level put the order's results -- and a pending Compare's distance -- into the results slot
+  void descent_begun(int levels_, bool published_, bool exported_) {
+    levels = levels_; exported = exported_;
+    if (published_) { published = epoch; if (compare != kNoCompare) compare = kWithResults; }
+  }
+  void order_taken() { order = kNoOrder; }
+  int descent_taken() { const int launched = levels; levels = -1; return launched; }
+  void distance_taken() { compare = kNoCompare; }
+  void mirror_replaced() { exported = false; }   // (what k_desc_export wrote went with the old array)
+  void void_up_to(Void v) {
+    order = kNoOrder; levels = -1;
+    if (v >= kRide && compare == kWithResults) compare = kMaxBits;
+    if (v == kEverything) { compare = kNoCompare; exported = false; }
+  }
+};
+
 struct gz_ctx {
   int device = 0;
   int w = 0, h = 0, bw = 0, bh = 0, nb = 0, pitch = 0;
@@ -329,20 +363,15 @@ struct gz_ctx {
   PartScalars* d_part = nullptr;
   // gz_order_build_auto_begin .. _end: results land here (pinned; not the shared landing area,
   // which gz_compare_end uses in between)
-  struct OrderPending { unsigned long long total; unsigned counters[2]; };
-  OrderPending* h_order_pending = nullptr;
-  bool order_pending = false;
-  // quick-select descent decided on the device (gz_order_descend*): per-level ranges and pivots,
-  // the ranges' pinned copy for the host's replay
+  struct OrderResults { unsigned long long total; unsigned counters[2]; };
+  OrderResults* h_order_results = nullptr;
+  // quick-select descent decided on the device (gz_order_descend*): per-level ranges and pivots, the ranges' pinned
+  // copy for the host's replay [kDescStates] -- with gz_order_build_auto_descend_begin the order's counters (and the
+  // distance of the Compare in flight) arrive in it too, in h_desc[kDescResultsSlot]
   DescState* d_desc_st = nullptr; DescPivot* d_desc_pv = nullptr; DescState* h_desc = nullptr;
-  unsigned desc_epoch = 0; int desc_levels = 0; bool desc_pending = false;
-  // gz_order_build_auto_descend_begin: the order's counters (and the distance of the Compare in
-  // flight) arrive with the descent's state, in h_desc[kDescMaxLevels + 1]
+  Pending pending;
   void* h_order_mirror = nullptr;      // gz_order_host_mirror: pinned, order entries land in it directly
   size_t order_mirror_cap = 0;         // entries
-  bool results_in_desc = false, distance_in_desc = false;
-  unsigned results_epoch = 0;          // the descent (desc_epoch) that published them
-  unsigned export_epoch = 0;           // the descent whose k_desc_export wrote into the host mirror (0: none)
   unsigned* d_order_nb = nullptr;                                 // [nb]
   unsigned long long* d_order_off = nullptr;                      // [nb+1]: [nb] = the order's size; the first 4 nb BYTES: every block's offset inside its group
   unsigned* d_order_counters = nullptr;                           // [2]
@@ -358,8 +387,9 @@ struct gz_ctx {
   // mask of d_rgb); pi0 and sup0 have no flag: gz_set_rgb writes them, and a failed gz_set_rgb leaves them undefined.
   // The candidate: have_cand (d_cand holds one), and what is derived from it: lin_is_cand, xyb_is_cand, have_distmap
   // (the last Compare's distance map and block maxima are in place), h_block_max_valid (h_block_max is d_block_max).
-  // Pending two-phase calls: order_pending, desc_pending, results_in_desc, distance_in_desc, compare_pending,
-  // scan_pending, adv_pending, export_epoch (void_pending_order, set_frame).
+  // Pending two-phase calls: `pending` (the order, its descent, the Compare: written by Pending's transitions only),
+  // scan_pending, adv_pending.  A pending state is entered as the last state change before `return GZ_OK`; a call that
+  // replaces what a pending call worked on voids it first (void_up_to), and a voided call's _end fails or returns nothing.
   // Rules:  DROP BEFORE WRITE -- a call that writes d_orig, d_cand, d_rgb / pi0, lin[] or xyb[] drops every claim that
   // depends on that buffer before its first copy or launch.  RE-ARM ONLY ON SUCCESS -- a claim is set again only as the
   // last state change before `return GZ_OK`.  Dropping is always safe: it costs one full reconstruction or opsin pass.
@@ -375,7 +405,6 @@ struct gz_ctx {
   std::vector<unsigned char> tile_mark;   // opsin tiles already listed (gz_apply_coeff_edits)
   std::vector<float> h_block_max;
   bool h_block_max_valid = false;
-  bool compare_pending = false;
   int h_jq[192] = {0};       // the matrix d_jq holds
   unsigned* d_step_delta = nullptr; bool have_step_delta = false;   // AC statistics change of the last bulk steps
   hipEvent_t ev_steps = nullptr; bool step_delta_event = false;     // ... are in place (recorded when more work follows them on the stream)
@@ -430,6 +459,19 @@ namespace {
     }                                                                                \
   } while (0)
 
+// Growing buffers that share one capacity: the old ones go back to the pool -- behind everything on `behind`, if
+// given: the pool hands memory on without waiting -- with the pointers null and the capacity zero BEFORE the allocations
+// that may fail (nothing is left half-owned), and the capacity set behind the last of them.
+struct Regrown { void** p; size_t bytes; };
+static int regrow(gz_ctx* c, bool host, hipStream_t behind, size_t* cap, size_t new_cap, std::initializer_list<Regrown> bufs) {
+  if (behind) HIPCHK(c, hipStreamSynchronize(behind));
+  for (const Regrown& b : bufs) { if (host) pool_host_free(*b.p); else pool_free(*b.p); *b.p = nullptr; }
+  *cap = 0;
+  for (const Regrown& b : bufs) HIPCHK(c, host ? pool_host_malloc(b.p, b.bytes) : pool_malloc(b.p, b.bytes));
+  *cap = new_cap;
+  return GZ_OK;
+}
+
 // Reserves `bytes` of the staging buffer (waiting for its previous upload if that is still
 // running) and returns it; stage_sent() marks the upload that was just enqueued on `stream`.
 static int stage_reserve(gz_ctx* c, HostStage* st, size_t bytes, void** out) {
@@ -439,12 +481,8 @@ static int stage_reserve(gz_ctx* c, HostStage* st, size_t bytes, void** out) {
     st->busy = false;
   }
   if (bytes > st->cap) {
-    if (st->h) (void)pool_host_free(st->h);
-    st->h = nullptr;
-    st->cap = 0;
     const size_t cap = bytes + bytes / 2 + 4096;
-    HIPCHK(c, pool_host_malloc(&st->h, cap));
-    st->cap = cap;
+    if (int rc = regrow(c, true, nullptr, &st->cap, cap, {{&st->h, cap}})) return rc;
   }
   *out = st->h;
   return GZ_OK;
@@ -456,12 +494,8 @@ static int stage_sent(gz_ctx* c, HostStage* st, hipStream_t stream) {
 }
 static int result_buffer(gz_ctx* c, size_t bytes, void** out) {
   if (bytes > c->h_res_cap) {
-    if (c->h_res) (void)pool_host_free(c->h_res);
-    c->h_res = nullptr;
-    c->h_res_cap = 0;
     const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    HIPCHK(c, pool_host_malloc(&c->h_res, cap));
-    c->h_res_cap = cap;
+    if (int rc = regrow(c, true, nullptr, &c->h_res_cap, cap, {{&c->h_res, cap}})) return rc;
   }
   *out = c->h_res;
   return GZ_OK;
@@ -473,15 +507,6 @@ static void stage_free(HostStage* st) {
 }
 
 const int kNumPlanes = 9 + 9 + 3 + 3 + 3 + 2 + 2 + 10 + 2;   // pi0, pi1, lin, tmp, xyb, lf_raw, hfp, 10 singles, sup0[2]
-
-// A pending order build is void (gz_order_build_auto_end fails); descent: a descent pending behind it too
-// (gz_order_descend_end returns nothing); distance: and the distance of a Compare that was to arrive with it.
-void void_pending_order(gz_ctx* c, bool descent = false, bool distance = false) {
-  c->order_pending = false;
-  c->results_in_desc = false;
-  if (descent) c->desc_pending = false;
-  if (distance) c->distance_in_desc = false;
-}
 
 // A new frame layout: the candidate, the search and whatever was pending or kept belonged to the old one (a stale
 // gz_order_build_auto_end / gz_order_descend_end / gz_compare_end / gz_jpeg_scan_end must fail, not return its data).
@@ -497,12 +522,10 @@ void set_frame(gz_ctx* c, int factor) {
   c->have_cand = false;
   c->lin_is_cand = c->xyb_is_cand = false;
   c->have_search = false;
-  void_pending_order(c, true, true);
-  c->compare_pending = false;
+  c->pending.void_up_to(Pending::kEverything);
   c->scan_pending = false;
   c->have_distmap = false;
   c->have_scan = false;
-  c->export_epoch = 0;
 }
 size_t csamp_plane(const gz_ctx* c) {   // bytes of one chroma sample plane of a 4:2:0 frame
   return (size_t)((c->w + 15) / 16 * 8) * (size_t)((c->h + 15) / 16 * 8);

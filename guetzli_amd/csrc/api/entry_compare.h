@@ -94,12 +94,9 @@ int gz_set_coeff_blocks(gz_ctx* c, const int32_t* block_index, int n, const int1
     if (block_index[i] < 0 || block_index[i] >= c->nb) return GZ_E_ARG;
   c->lin_is_cand = c->xyb_is_cand = false;
   if ((size_t)n > c->blkidx_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
-    (void)pool_free(c->d_blkidx); (void)pool_free(c->d_blkdata);
-    c->d_blkidx = nullptr; c->d_blkdata = nullptr;
-    c->blkidx_cap = std::max<size_t>((size_t)n, std::min<size_t>((size_t)c->nb, 2 * c->blkidx_cap + 1024));
-    HIPCHK(c, pool_malloc((void**)&c->d_blkidx, sizeof(int32_t) * c->blkidx_cap));
-    HIPCHK(c, pool_malloc((void**)&c->d_blkdata, c->blkidx_cap * 384));
+    const size_t cap = std::max<size_t>((size_t)n, std::min<size_t>((size_t)c->nb, 2 * c->blkidx_cap + 1024));
+    TRY(regrow(c, false, c->stream, &c->blkidx_cap, cap,
+               {{(void**)&c->d_blkidx, sizeof(int32_t) * cap}, {(void**)&c->d_blkdata, cap * 384}}));
   }
   HIPCHK(c, hipMemcpyAsync(c->d_blkidx, block_index, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_blkdata, blocks, (size_t)n * 384, hipMemcpyHostToDevice, c->stream));
@@ -166,23 +163,21 @@ int gz_compare_begin(gz_ctx* c) {
   HIPCHK(c, hipEventRecord(c->ev_candidate, c->stream));   // gz_jpeg_scan waits for this only
   c->h_block_max_valid = false;
   TRY(enqueue_compare(c, kWantBlockMax));
-  c->compare_pending = true;
-  c->distance_in_desc = false;
+  c->pending.compare_begun();
   return GZ_OK;
 }
 
 int gz_compare_end(gz_ctx* c, float* distance) {
   DeviceScope ds_(c);
   if (!c || !distance) return GZ_E_ARG;
-  if (!c->compare_pending) { c->err = "gz_compare_begin must precede gz_compare_end"; return GZ_E_STATE; }
-  if (c->distance_in_desc) {
+  if (c->pending.compare == Pending::kNoCompare) { c->err = "gz_compare_begin must precede gz_compare_end"; return GZ_E_STATE; }
+  if (c->pending.compare == Pending::kWithResults) {
     // gz_order_build_auto_descend_begin behind this evaluation: the distance comes with its results
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const DescState& p = c->h_desc[kDescMaxLevels + 1];
-    if (p.epoch != c->results_epoch || p.depth != 1) { c->err = "the distance did not arrive with the descent"; return GZ_E_STATE; }
+    const DescState& p = c->h_desc[kDescResultsSlot];
+    if (p.epoch != c->pending.published || p.depth != 1) { c->err = "the distance did not arrive with the descent"; return GZ_E_STATE; }
     const unsigned bits = (unsigned)p.cut;
     memcpy(&c->last_distance, &bits, 4);
-    c->distance_in_desc = false;
   } else {
     void* res = nullptr;
     TRY(result_buffer(c, 4, &res));
@@ -192,7 +187,7 @@ int gz_compare_end(gz_ctx* c, float* distance) {
   }
   *distance = c->last_distance;
   c->have_distmap = true;
-  c->compare_pending = false;
+  c->pending.distance_taken();
   return GZ_OK;
 }
 

@@ -36,7 +36,7 @@ int gz_set_config(gz_ctx* c, const gz_config* in) {
   if (in->blur_packed < -1 || in->blur_packed > 1 || in->single_stream < -1 || in->single_stream > 1 || (in->tile_rows != 0 && in->tile_rows != 16 && in->tile_rows != 32) ||
       in->patch_reconstruct < 0 || in->patch_reconstruct > 2)
     return GZ_E_ARG;
-  if (c->compare_pending || c->scan_pending || c->order_pending || c->desc_pending) {
+  if (c->pending.busy() || c->scan_pending) {
     c->err = "gz_set_config while work of the context is in flight";
     return GZ_E_STATE;
   }
@@ -297,7 +297,7 @@ void gz_destroy(gz_ctx* c) {
   (void)pool_free(c->d_order); (void)pool_free(c->d_pos_l); (void)pool_free(c->d_pos_r); (void)pool_free(c->d_chunk);
   (void)pool_free(c->d_part); (void)pool_free(c->d_order_nb); (void)pool_free(c->d_order_off);
   (void)pool_free(c->d_order_groups);
-  if (c->h_order_pending) (void)pool_host_free(c->h_order_pending);
+  if (c->h_order_results) (void)pool_host_free(c->h_order_results);
   if (c->h_order_mirror) (void)pool_host_free(c->h_order_mirror);
   if (c->h_desc) (void)pool_host_free(c->h_desc);
   if (c->h_scan_result) (void)pool_host_free(c->h_scan_result);

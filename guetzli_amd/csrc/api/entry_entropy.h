@@ -99,7 +99,7 @@ int gz_jpeg_scan_begin(gz_ctx* c, int ncomp, const uint8_t* depth, const uint16_
   }
   // own stream, behind the candidate (not behind a Compare that gz_compare_begin enqueued)
   hipStream_t es = c->entropy_stream;
-  if (!c->compare_pending) HIPCHK(c, hipEventRecord(c->ev_candidate, c->stream));
+  if (c->pending.compare == Pending::kNoCompare) HIPCHK(c, hipEventRecord(c->ev_candidate, c->stream));
   HIPCHK(c, hipStreamWaitEvent(es, c->ev_candidate, 0));
   {
     void* h = nullptr;

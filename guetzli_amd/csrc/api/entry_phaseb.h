@@ -4,7 +4,7 @@
 #pragma once
 
 extern "C" {
-
+static bool is_direction(int d) { return d == 1 || d == -1; }
 
 // ------------------------------------------------- global candidate order (phase B) ----
 static int ensure_order_capacity(gz_ctx* c, size_t n) {
@@ -13,20 +13,21 @@ static int ensure_order_capacity(gz_ctx* c, size_t n) {
     HIPCHK(c, pool_malloc((void**)&c->d_order_counters, sizeof(unsigned) * 2));
   }
   if (n <= c->order_cap) return GZ_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
-  (void)pool_free(c->d_order); (void)pool_free(c->d_pos_l); (void)pool_free(c->d_pos_r); (void)pool_free(c->d_chunk);
-  c->d_order = nullptr; c->d_pos_l = nullptr; c->d_pos_r = nullptr; c->d_chunk = nullptr;
-  c->order_cap = 0;
   const size_t cap = n + n / 8 + 4096;
-  HIPCHK(c, pool_malloc((void**)&c->d_order, sizeof(OrderEntry) * cap));
   c->chunk_cap = cap / kPartChunk + 2;
   // (gz_order_partition records at most cap / 2 swapped pairs per side; the descent's per-chunk
   // stopper lists need a full chunk's worth per chunk)
-  HIPCHK(c, pool_malloc((void**)&c->d_pos_l, sizeof(unsigned) * c->chunk_cap * kPartChunk));
-  HIPCHK(c, pool_malloc((void**)&c->d_pos_r, sizeof(unsigned) * c->chunk_cap * kPartChunk));
-  HIPCHK(c, pool_malloc((void**)&c->d_chunk, sizeof(unsigned) * 4 * c->chunk_cap));
-  c->order_cap = cap;
-  return GZ_OK;
+  const size_t pos_bytes = sizeof(unsigned) * c->chunk_cap * kPartChunk;
+  return regrow(c, false, c->stream, &c->order_cap, cap,
+                {{(void**)&c->d_order, sizeof(OrderEntry) * cap}, {(void**)&c->d_pos_l, pos_bytes},
+                 {(void**)&c->d_pos_r, pos_bytes}, {(void**)&c->d_chunk, sizeof(unsigned) * 4 * c->chunk_cap}});
+}
+
+// d_edit_pos / d_edit_val: coefficient edits, and the bulk steps' (blocks, counts) staging
+static int ensure_edit_capacity(gz_ctx* c, size_t n) {
+  const size_t cap = n + n / 2 + 4096;
+  return n <= c->edit_cap ? GZ_OK : regrow(c, false, c->stream, &c->edit_cap, cap, {{(void**)&c->d_edit_pos, sizeof(int) * cap},
+                                                                                   {(void**)&c->d_edit_val, sizeof(short) * cap}});
 }
 
 // gz_order_advance's update of max_block_error, if it is still due (it normally rides on the next order's
@@ -78,26 +79,39 @@ static int order_build_enqueue(gz_ctx* c, int direction, int count_below, float 
   return GZ_OK;
 }
 
+// The order's size and its two counters on their way to pinned memory of the host, behind the construction
+// (dst: nullptr = the context's own buffer, where an _end finds them).
+static int order_results_enqueue(gz_ctx* c, gz_ctx::OrderResults* dst) {
+  if (!dst && !c->h_order_results) HIPCHK(c, pool_host_malloc((void**)&c->h_order_results, sizeof(*c->h_order_results)));
+  if (!dst) dst = c->h_order_results;
+  HIPCHK(c, hipMemcpyAsync(&dst->total, c->d_order_off + c->sg_n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dst->counters, c->d_order_counters, 8, hipMemcpyDeviceToHost, c->stream));
+  return GZ_OK;
+}
+// ... and taken from where they landed (own: nullptr = the results slot of descent `published`), once the stream
+// has been waited for: the order is the context's current one.
+static int order_results_take(gz_ctx* c, const gz_ctx::OrderResults* own, uint64_t* total, int32_t* blocks_to_change,
+                              uint64_t* below) {
+  const DescState& p = c->h_desc[kDescResultsSlot];   // (read only without `own`)
+  if (!own && (p.epoch != c->pending.published || p.depth != 1)) { c->err = "the order's results did not arrive with the descent"; return GZ_E_STATE; }
+  const gz_ctx::OrderResults r = own ? *own : gz_ctx::OrderResults{p.lo, {(unsigned)p.hi, (unsigned)p.last}};
+  if (r.total > c->order_cap) { c->err = "order larger than the candidate count"; return GZ_E_STATE; }
+  c->order_n = (size_t)r.total;
+  *total = r.total;
+  *blocks_to_change = (int32_t)r.counters[0];
+  if (below) *below = r.counters[1];
+  return GZ_OK;
+}
+
 static int order_build_device(gz_ctx* c, int direction, int count_below, float limit,
                               uint64_t* total, int32_t* blocks_to_change, uint64_t* below,
                               bool sizes_done = false) {
-  const int nb = c->sg_n;
   TRY(order_build_enqueue(c, direction, count_below, limit, sizes_done));
   void* res = nullptr;
-  TRY(result_buffer(c, 16, &res));
-  HIPCHK(c, hipMemcpyAsync(res, c->d_order_off + nb, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync((char*)res + 8, c->d_order_counters, 8, hipMemcpyDeviceToHost, c->stream));
+  TRY(result_buffer(c, sizeof(gz_ctx::OrderResults), &res));
+  TRY(order_results_enqueue(c, (gz_ctx::OrderResults*)res));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  unsigned long long n = 0;
-  unsigned counters[2] = {0, 0};
-  memcpy(&n, res, 8);
-  memcpy(counters, (char*)res + 8, 8);
-  if (n > c->order_cap) { c->err = "order larger than the candidate count"; return GZ_E_STATE; }
-  c->order_n = (size_t)n;
-  *total = n;
-  *blocks_to_change = (int32_t)counters[0];
-  if (below) *below = counters[1];
-  return GZ_OK;
+  return order_results_take(c, (const gz_ctx::OrderResults*)res, total, blocks_to_change, below);
 }
 
 int gz_order_build(gz_ctx* c, int direction, const int32_t* next_cand,
@@ -105,10 +119,10 @@ int gz_order_build(gz_ctx* c, int direction, const int32_t* next_cand,
                    float limit, uint64_t* total, int32_t* blocks_to_change, uint64_t* below) {
   DeviceScope ds_(c);
   if (!c || !next_cand || !max_block_error || !block_weight || !total || !blocks_to_change ||
-      (direction != 1 && direction != -1) || (count_below && !below))
+      !is_direction(direction) || (count_below && !below))
     return GZ_E_ARG;
   if (!c->have_search) { c->err = "gz_block_zeroing_orders must precede gz_order_build"; return GZ_E_STATE; }
-  void_pending_order(c);
+  c->pending.void_up_to(Pending::kOrder);   // (and the descent behind it: it worked on the order this one replaces)
   const int nb = c->sg_n;
   TRY(ensure_order_block_arrays(c));
   c->adv_pending = false;   // (the caller's own max_block_error and weights replace the device's)
@@ -133,7 +147,7 @@ static int order_auto_enqueue(gz_ctx* c, int direction, int max_block_dist, doub
                               int use_distmap, const int32_t* next_cand) {
   if (!c->have_search) { c->err = "gz_block_zeroing_orders must precede gz_order_build_auto"; return GZ_E_STATE; }
   // (a comparison that is still in flight on the same stream delivers the map in time)
-  if (use_distmap && !c->have_distmap && !c->compare_pending) { c->err = "no distance map yet"; return GZ_E_STATE; }
+  if (use_distmap && !c->have_distmap && c->pending.compare == Pending::kNoCompare) { c->err = "no distance map yet"; return GZ_E_STATE; }
   const int nb = c->sg_n;
   TRY(ensure_order_block_arrays(c));
   TRY(ensure_order_capacity(c, std::max<size_t>(c->search_total, 1)));   // also: the counters
@@ -150,7 +164,7 @@ static int order_auto_enqueue(gz_ctx* c, int direction, int max_block_dist, doub
     // enqueue_compare) -- the copy stays on the main stream too: on the side stream it shares a hardware queue with
     // ANOTHER image's main stream and waits there behind that image's kernels, and the order with it (8 x 4K
     // 40.7 -> 43.0 MPix/s, 16 x 1080p 34.6 -> 36.2, 64 x 1 MPix 29.6 -> 32.6: r06_chain_experiments.log, section 11).
-    const bool beside = c->compare_pending && c->compare_forked;
+    const bool beside = c->pending.compare != Pending::kNoCompare && c->compare_forked;
     hipStream_t up = beside ? c->side_stream : c->stream;
     void* h = nullptr;
     TRY(stage_reserve(c, &c->stage_main, sizeof(int) * nb, &h));
@@ -191,10 +205,10 @@ int gz_order_build_auto(gz_ctx* c, int direction, int max_block_dist, double tar
                         int use_distmap, const int32_t* next_cand, int count_below, float limit,
                         uint64_t* total, int32_t* blocks_to_change, uint64_t* below) {
   DeviceScope ds_(c);
-  if (!c || !next_cand || !total || !blocks_to_change || (direction != 1 && direction != -1) ||
+  if (!c || !next_cand || !total || !blocks_to_change || !is_direction(direction) ||
       max_block_dist < 0 || (count_below && !below))
     return GZ_E_ARG;
-  void_pending_order(c, true);
+  c->pending.void_up_to(Pending::kOrder);
   TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
   return order_build_device(c, direction, count_below, limit, total, blocks_to_change, below, true);
 }
@@ -202,68 +216,29 @@ int gz_order_build_auto(gz_ctx* c, int direction, int max_block_dist, double tar
 int gz_order_build_auto_begin(gz_ctx* c, int direction, int max_block_dist, double target_mul,
                               int use_distmap, const int32_t* next_cand, int count_below, float limit) {
   DeviceScope ds_(c);
-  if (!c || !next_cand || (direction != 1 && direction != -1) || max_block_dist < 0) return GZ_E_ARG;
-  void_pending_order(c, true);
+  if (!c || !next_cand || !is_direction(direction) || max_block_dist < 0) return GZ_E_ARG;
+  c->pending.void_up_to(Pending::kOrder);
   TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
   TRY(order_build_enqueue(c, direction, count_below, limit, true));
-  if (!c->h_order_pending) HIPCHK(c, pool_host_malloc((void**)&c->h_order_pending, sizeof(*c->h_order_pending)));
-  HIPCHK(c, hipMemcpyAsync(&c->h_order_pending->total, c->d_order_off + c->sg_n, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_order_pending->counters, c->d_order_counters, 8, hipMemcpyDeviceToHost, c->stream));
-  c->order_pending = true;
+  TRY(order_results_enqueue(c, nullptr));
+  c->pending.order_begun(Pending::kOwnBuffer);
   return GZ_OK;
 }
 
 int gz_order_build_auto_end(gz_ctx* c, uint64_t* total, int32_t* blocks_to_change, uint64_t* below) {
   DeviceScope ds_(c);
   if (!c || !total || !blocks_to_change || !below) return GZ_E_ARG;
-  if (!c->order_pending) { c->err = "gz_order_build_auto_begin must precede gz_order_build_auto_end"; return GZ_E_STATE; }
-  c->order_pending = false;
+  const Pending::Landing where = c->pending.order;
+  if (where == Pending::kNoOrder) { c->err = "gz_order_build_auto_begin must precede gz_order_build_auto_end"; return GZ_E_STATE; }
+  c->pending.order_taken();
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  gz_ctx::OrderPending r;
-  if (c->results_in_desc) {   // (gz_order_build_auto_descend_begin: with the descent's state)
-    const DescState& p = c->h_desc[kDescMaxLevels + 1];
-    if (p.epoch != c->results_epoch || p.depth != 1) { c->err = "the order's results did not arrive with the descent"; return GZ_E_STATE; }
-    r.total = p.lo;
-    r.counters[0] = (unsigned)p.hi;
-    r.counters[1] = (unsigned)p.last;
-    c->results_in_desc = false;
-  } else {
-    r = *c->h_order_pending;
-  }
-  if (r.total > c->order_cap) { c->err = "order larger than the candidate count"; return GZ_E_STATE; }
-  c->order_n = (size_t)r.total;
-  *total = r.total;
-  *blocks_to_change = (int32_t)r.counters[0];
-  *below = r.counters[1];
-  return GZ_OK;
-}
-
-static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, float per_block,
-                           uint64_t threshold, int max_levels, size_t n_bound, bool publish);
-
-// gz_order_build_auto_begin + gz_order_descend_begin in one call, with ONE transfer of results.
-int gz_order_build_auto_descend_begin(gz_ctx* c, int direction, int max_block_dist, double target_mul,
-                                      int use_distmap, const int32_t* next_cand, int count_below,
-                                      float limit, float per_block, uint64_t threshold, int max_levels) {
-  DeviceScope ds_(c);
-  if (!c || !next_cand || (direction != 1 && direction != -1) || max_block_dist < 0 || max_levels < 0)
-    return GZ_E_ARG;
-  void_pending_order(c, true, true);
-  TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
-  TRY(order_build_enqueue(c, direction, count_below, limit, true));
-  TRY(descend_enqueue(c, 1, 0, 0, per_block, threshold, max_levels, std::max<size_t>(c->search_total, 1), true));
-  if (!c->results_in_desc) {   // (no level was launched: the order is too large for the descent's tables)
-    if (!c->h_order_pending) HIPCHK(c, pool_host_malloc((void**)&c->h_order_pending, sizeof(*c->h_order_pending)));
-    HIPCHK(c, hipMemcpyAsync(&c->h_order_pending->total, c->d_order_off + c->sg_n, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_order_pending->counters, c->d_order_counters, 8, hipMemcpyDeviceToHost, c->stream));
-  }
-  c->order_pending = true;
-  return GZ_OK;
+  // (kResultsSlot: gz_order_build_auto_descend_begin, with the descent's state)
+  return order_results_take(c, where == Pending::kOwnBuffer ? c->h_order_results : nullptr, total, blocks_to_change, below);
 }
 
 int gz_order_advance(gz_ctx* c, float val_threshold, int direction) {
   DeviceScope ds_(c);
-  if (!c || (direction != 1 && direction != -1)) return GZ_E_ARG;
+  if (!c || !is_direction(direction)) return GZ_E_ARG;
   if (!c->d_weight) { c->err = "gz_order_build_auto must precede gz_order_advance"; return GZ_E_STATE; }
   // max_block_error[i] += block_weight[i] * val_threshold * direction -- due, not launched: the next order's
   // k_weights_gather makes the update with the weights it is about to replace (nothing reads max_block_error before
@@ -299,10 +274,69 @@ static PatchPlanes patch_planes(const gz_ctx* c, bool on) {
   return pp;
 }
 
+// gz_apply_candidate_steps' two arms: n (block, count) pairs in the staging buffer h (blocks, then counts), d_blocks
+// their place in device memory.  With the symbol statistics' quantiser known (gz_jpeg_histograms), the steps also
+// report what they do to the AC histograms (gz_steps_histogram_delta), and the touched block positions of the
+// candidate's linear planes are transformed again behind the statistics (chain.h, enqueue_compare) while they are a
+// minority (patch): beyond that the next Compare reconstructs the image.
+static int steps_with_statistics(gz_ctx* c, const int* h, int* d_blocks, int n, int direction, const StepGeom& sg,
+                                 bool patch, PatchClaims* claims) {
+  // (zeroed once: k_steps_hist_sum leaves the counters zeroed)
+  if (!c->d_step_delta) {
+    HIPCHK(c, pool_malloc((void**)&c->d_step_delta, sizeof(unsigned) * 768 * kStepDeltaCopies));
+    HIPCHK(c, hipMemsetAsync(c->d_step_delta, 0, sizeof(unsigned) * 768 * kStepDeltaCopies, c->stream));
+  }
+  if (!c->h_step_delta) HIPCHK(c, pool_host_malloc(&c->h_step_delta, sizeof(int) * 768));
+  // (persistent workgroups: four per CU's worth at most, each wavefront taking several blocks)
+  // (the kernel reads the staging buffer itself -- page-locked and mapped: a copy command in front of
+  // it costs more in hand-overs between commands than the 8 bytes per block cost over the bus)
+  GZ_LAUNCH(k_apply_steps_hist, dim3(std::min(gz_div_up(n, 4), kStepHistGrid)), dim3(256), c->stream, h,
+            h + n, n, direction, (const int*)c->d_next_cand,
+            (const unsigned char*)c->d_out_idx, (const short*)c->d_orig, (short*)c->d_cand,
+            (const int*)c->d_q, (const int*)c->d_jq, sg, c->d_step_delta, patch ? d_blocks : (int*)nullptr);
+  // the staging buffer is free again behind THIS kernel (the only reader): marked before anything can fail, so
+  // that no path returns with the kernel still reading a buffer the next stage_reserve hands out
+  TRY(stage_sent(c, &c->stage_main, c->stream));
+  KCHK(c);
+  GZ_LAUNCH(k_steps_hist_sum, dim3(1), dim3(256), c->stream, c->d_step_delta, (int*)c->h_step_delta);
+  KCHK(c);
+  c->have_step_delta = true;
+  c->step_delta_event = false;
+  bool ahead = false;
+  if (patch) {
+    // gz_steps_histogram_delta waits for the sums, not for the stream: the patches run while the host reads them
+    if (!c->ev_steps) HIPCHK(c, pool_event_create(&c->ev_steps));
+    HIPCHK(c, hipEventRecord(c->ev_steps, c->stream));
+    c->step_delta_event = true;
+    GZ_LAUNCH((k_reconstruct_listed<false>), dim3(gz_div_up(n, kBlocksPerWG)), dim3(256), c->stream, (const int*)d_blocks, n,
+              (const int16_t*)c->d_cand, c->nb, patch_planes(c, true));
+    KCHK(c);
+    // ... and, for a context that has the device to itself, the next Compare's opsin blur of the planes as they
+    // are now: 100 us (4K) of the chain's critical path that run while the host takes its serial steps, whose
+    // edits then cost the tiles around them (gz_apply_coeff_edits).  Not in a batch: the other images use the time.
+    ahead = c->cfg.opsin_ahead != 0 && !single_stream_wanted(c);
+    if (ahead) TRY(stage_opsin(c, c->stream));
+  }
+  claims->commit(patch, ahead);
+  return GZ_OK;
+}
+
+// Without them: the pairs go to device memory, the steps are applied, nothing is kept current.
+static int steps_plain(gz_ctx* c, const int* h, int* d_blocks, int n, int direction, const StepGeom& sg) {
+  HIPCHK(c, hipMemcpyAsync(d_blocks, h, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  TRY(stage_sent(c, &c->stage_main, c->stream));
+  GZ_LAUNCH(k_apply_steps, dim3(gz_div_up(n, 4)), dim3(256), c->stream, (const int*)d_blocks,
+            (const int*)d_blocks + n, n, direction, (const int*)c->d_next_cand,
+            (const unsigned char*)c->d_out_idx, (const short*)c->d_orig, (short*)c->d_cand,
+            (const int*)c->d_q, sg);
+  KCHK(c);
+  return GZ_OK;
+}
+
 int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
                              const int32_t* counts, int n) {
   DeviceScope ds_(c);
-  if (!c || n < 0 || (n > 0 && (!blocks || !counts)) || (direction != 1 && direction != -1))
+  if (!c || n < 0 || (n > 0 && (!blocks || !counts)) || !is_direction(direction))
     return GZ_E_ARG;
   if (!c->have_search || !c->d_next_cand || !c->have_cand || !c->have_orig) {
     c->err = "gz_order_build must precede gz_apply_candidate_steps";
@@ -315,20 +349,9 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
     for (int i = 0; i < n; ++i) bad |= (unsigned)((unsigned)blocks[i] >= sg_n) | (unsigned)((unsigned)counts[i] > 192u);
     if (bad) return GZ_E_ARG;
   }
-  // the touched block positions of the candidate's linear planes are transformed again behind the statistics
-  // (chain.h, enqueue_compare), while they are a minority: beyond that the next Compare reconstructs the image
   const bool patch = c->have_jq && patch_wanted(c, n);
   PatchClaims claims(c);
-  if ((size_t)2 * n > c->edit_cap) {   // the edit buffers double as (blocks, counts) staging
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
-    (void)pool_free(c->d_edit_pos); (void)pool_free(c->d_edit_val);
-    c->d_edit_pos = nullptr; c->d_edit_val = nullptr;
-    c->edit_cap = (size_t)2 * n + (size_t)n + 4096;
-    HIPCHK(c, pool_malloc((void**)&c->d_edit_pos, sizeof(int) * c->edit_cap));
-    HIPCHK(c, pool_malloc((void**)&c->d_edit_val, sizeof(short) * c->edit_cap));
-  }
-  int* d_blocks = c->d_edit_pos;
-  int* d_counts = c->d_edit_pos + n;
+  TRY(ensure_edit_capacity(c, (size_t)2 * n));   // the edit buffers double as (blocks, counts) staging
   void* h = nullptr;
   TRY(stage_reserve(c, &c->stage_main, sizeof(int) * 2 * n, &h));
   memcpy(h, blocks, sizeof(int) * n);
@@ -337,56 +360,9 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
   for (int i = 0; i < 3; ++i) sg.coff[i] = c->coff[i];
   sg.comp_mask = c->sg_mask;
   c->have_step_delta = false;
-  if (c->have_jq) {
-    // with the symbol statistics' quantiser known, the steps also report what they do to the
-    // AC histograms (gz_steps_histogram_delta)
-    // (zeroed once: k_steps_hist_sum leaves the counters zeroed)
-    if (!c->d_step_delta) {
-      HIPCHK(c, pool_malloc((void**)&c->d_step_delta, sizeof(unsigned) * 768 * kStepDeltaCopies));
-      HIPCHK(c, hipMemsetAsync(c->d_step_delta, 0, sizeof(unsigned) * 768 * kStepDeltaCopies, c->stream));
-    }
-    if (!c->h_step_delta) HIPCHK(c, pool_host_malloc(&c->h_step_delta, sizeof(int) * 768));
-    // (persistent workgroups: four per CU's worth at most, each wavefront taking several blocks)
-    // (the kernel reads the staging buffer itself -- page-locked and mapped: a copy command in front of
-    // it costs more in hand-overs between commands than the 8 bytes per block cost over the bus)
-    GZ_LAUNCH(k_apply_steps_hist, dim3(std::min(gz_div_up(n, 4), kStepHistGrid)), dim3(256), c->stream, (const int*)h,
-              (const int*)h + n, n, direction, (const int*)c->d_next_cand,
-              (const unsigned char*)c->d_out_idx, (const short*)c->d_orig, (short*)c->d_cand,
-              (const int*)c->d_q, (const int*)c->d_jq, sg, c->d_step_delta, patch ? d_blocks : (int*)nullptr);
-    // the staging buffer is free again behind THIS kernel (the only reader): marked before anything can fail, so
-    // that no path returns with the kernel still reading a buffer the next stage_reserve hands out
-    TRY(stage_sent(c, &c->stage_main, c->stream));
-    KCHK(c);
-    GZ_LAUNCH(k_steps_hist_sum, dim3(1), dim3(256), c->stream, c->d_step_delta, (int*)c->h_step_delta);
-    KCHK(c);
-    c->have_step_delta = true;
-    c->step_delta_event = false;
-    bool ahead = false;
-    if (patch) {
-      // gz_steps_histogram_delta waits for the sums, not for the stream: the patches run while the host reads them
-      if (!c->ev_steps) HIPCHK(c, pool_event_create(&c->ev_steps));
-      HIPCHK(c, hipEventRecord(c->ev_steps, c->stream));
-      c->step_delta_event = true;
-      GZ_LAUNCH((k_reconstruct_listed<false>), dim3(gz_div_up(n, kBlocksPerWG)), dim3(256), c->stream, (const int*)d_blocks, n,
-                (const int16_t*)c->d_cand, c->nb, patch_planes(c, true));
-      KCHK(c);
-      // ... and, for a context that has the device to itself, the next Compare's opsin blur of the planes as they
-      // are now: 100 us (4K) of the chain's critical path that run while the host takes its serial steps, whose
-      // edits then cost the tiles around them (gz_apply_coeff_edits).  Not in a batch: the other images use the time.
-      ahead = c->cfg.opsin_ahead != 0 && !single_stream_wanted(c);
-      if (ahead) TRY(stage_opsin(c, c->stream));
-    }
-    claims.commit(patch, ahead);
-    return GZ_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(d_blocks, h, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream));
-  TRY(stage_sent(c, &c->stage_main, c->stream));
-  GZ_LAUNCH(k_apply_steps, dim3(gz_div_up(n, 4)), dim3(256), c->stream, (const int*)d_blocks,
-            (const int*)d_counts, n, direction, (const int*)c->d_next_cand,
-            (const unsigned char*)c->d_out_idx, (const short*)c->d_orig, (short*)c->d_cand,
-            (const int*)c->d_q, sg);
-  KCHK(c);
-  return GZ_OK;   // the caller's buffers were copied to the staging buffer: no wait
+  // (either way the caller's buffers were copied to the staging buffer: no wait)
+  return c->have_jq ? steps_with_statistics(c, (const int*)h, c->d_edit_pos, n, direction, sg, patch, &claims)
+                    : steps_plain(c, (const int*)h, c->d_edit_pos, n, direction, sg);
 }
 
 int gz_steps_histogram_delta(gz_ctx* c, int32_t* ac_delta) {
@@ -403,6 +379,26 @@ int gz_steps_histogram_delta(gz_ctx* c, int32_t* ac_delta) {
   return GZ_OK;
 }
 
+// The opsin tiles (T2 pixels wide, th rows) that meet a block edited at one of the n positions, grown by 2 pixels:
+// each once, in the order the edits meet them, into tl (at most four per edit); returns how many.
+static int list_edited_tiles(gz_ctx* c, const int32_t* pos, int n, int th, int* tl) {
+  const int gx = gz_div_up(c->w, T2), gy = gz_div_up(c->h, th);
+  int nt = 0;
+  if (c->tile_mark.size() != (size_t)gx * gy) c->tile_mark.assign((size_t)gx * gy, 0);
+  for (int i = 0; i < n; ++i) {
+    const int b = (pos[i] >> 6) % c->nb, bx = b % c->bw, by = b / c->bw;
+    const int tx0 = std::max(0, 8 * bx - 2) / T2, tx1 = std::min(c->w - 1, 8 * bx + 9) / T2;
+    const int ty0 = std::max(0, 8 * by - 2) / th, ty1 = std::min(c->h - 1, 8 * by + 9) / th;
+    for (int ty = ty0; ty <= ty1; ++ty)
+      for (int tx = tx0; tx <= tx1; ++tx) {
+        unsigned char& m = c->tile_mark[(size_t)ty * gx + tx];
+        if (!m) { m = 1; tl[nt++] = ty * gx + tx; }
+      }
+  }
+  for (int i = 0; i < nt; ++i) c->tile_mark[(size_t)tl[i]] = 0;
+  return nt;
+}
+
 int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int n) {
   DeviceScope ds_(c);
   if (!c || n < 0 || (n > 0 && (!pos || !val))) return GZ_E_ARG;
@@ -417,14 +413,7 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
   // the kernel reads them straight from the page-locked staging buffer (two copies of a few KB on
   // the stream cost more than the bytes' trip over the bus).  Bulk edits go through device memory.
   const bool direct = n <= 4096;
-  if (!direct && (size_t)n > c->edit_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
-    (void)pool_free(c->d_edit_pos); (void)pool_free(c->d_edit_val);
-    c->d_edit_pos = nullptr; c->d_edit_val = nullptr;
-    c->edit_cap = (size_t)n + (size_t)n / 2 + 4096;
-    HIPCHK(c, pool_malloc((void**)&c->d_edit_pos, sizeof(int) * c->edit_cap));
-    HIPCHK(c, pool_malloc((void**)&c->d_edit_val, sizeof(short) * c->edit_cap));
-  }
+  if (!direct) TRY(ensure_edit_capacity(c, (size_t)n));
   void* h = nullptr;
   // (+ the list of opsin tiles around the edited blocks: at most four per edit, behind the values)
   const size_t tiles_at = ((sizeof(int) + sizeof(short)) * (size_t)n + 15) & ~(size_t)15;
@@ -448,24 +437,11 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
       // the opsin image enqueued ahead (gz_apply_candidate_steps): a pixel's value depends on the linear planes
       // within 2 pixels of it (radius-2 blur), so the tiles that meet an edited block grown by 2 are computed again
       // -- or the image, when the edits are many (the last iterations of a search)
-      const int th = opsin_tile_rows(c), gx = gz_div_up(c->w, T2), gy = gz_div_up(c->h, th);
-      int nt = 0;
+      const int th = opsin_tile_rows(c);
       int* tl = direct ? (int*)((char*)h + tiles_at) : nullptr;
-      if (tl) {
-        if (c->tile_mark.size() != (size_t)gx * gy) c->tile_mark.assign((size_t)gx * gy, 0);
-        for (int i = 0; i < n; ++i) {
-          const int b = (pos[i] >> 6) % c->nb, bx = b % c->bw, by = b / c->bw;
-          const int tx0 = std::max(0, 8 * bx - 2) / T2, tx1 = std::min(c->w - 1, 8 * bx + 9) / T2;
-          const int ty0 = std::max(0, 8 * by - 2) / th, ty1 = std::min(c->h - 1, 8 * by + 9) / th;
-          for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) {
-              unsigned char& m = c->tile_mark[(size_t)ty * gx + tx];
-              if (!m) { m = 1; tl[nt++] = ty * gx + tx; }
-            }
-        }
-        for (int i = 0; i < nt; ++i) c->tile_mark[(size_t)tl[i]] = 0;
-      }
-      rc_tiles = tl && (long)nt * 4 <= (long)gx * gy ? stage_opsin(c, c->stream, tl, nt) : stage_opsin(c, c->stream);
+      const int nt = tl ? list_edited_tiles(c, pos, n, th, tl) : 0;
+      const long tiles = (long)gz_div_up(c->w, T2) * gz_div_up(c->h, th);
+      rc_tiles = tl && (long)nt * 4 <= tiles ? stage_opsin(c, c->stream, tl, nt) : stage_opsin(c, c->stream);
     }
   }
   TRY(stage_sent(c, &c->stage_edits, c->stream));   // (the staging buffer is free again behind the kernels)
@@ -478,7 +454,7 @@ int gz_apply_coeff_edits(gz_ctx* c, const int32_t* pos, const int16_t* val, int 
 int gz_order_upload(gz_ctx* c, const void* entries, uint64_t n) {
   DeviceScope ds_(c);
   if (!c || (n > 0 && !entries)) return GZ_E_ARG;
-  void_pending_order(c);
+  c->pending.void_up_to(Pending::kOrder);   // (as gz_order_build)
   TRY(ensure_order_capacity(c, (size_t)n));
   if (n > 0)
     HIPCHK(c, hipMemcpyAsync(c->d_order, entries, sizeof(OrderEntry) * n, hipMemcpyHostToDevice, c->stream));
@@ -500,8 +476,7 @@ int gz_order_partition(gz_ctx* c, uint64_t lo, uint64_t hi, uint64_t* cut) {
   unsigned* base_r = c->d_chunk + 3 * c->chunk_cap;
   OrderEntry* a = c->d_order;
   PartScalars* ps = c->d_part;
-  unsigned* pos_l = c->d_pos_l;
-  unsigned* pos_r = c->d_pos_r;
+  unsigned *pos_l = c->d_pos_l, *pos_r = c->d_pos_r;
   const size_t lo_s = (size_t)lo, hi_s = (size_t)hi;
   GZ_LAUNCH(k_part_median, dim3(1), dim3(1), c->stream, a, lo_s, hi_s, ps);
   KCHK(c);
@@ -534,14 +509,9 @@ int gz_order_host_mirror(gz_ctx* c, uint64_t entries, void** out) {
   DeviceScope ds_(c);
   if (!c || !out) return GZ_E_ARG;
   if (entries > c->order_mirror_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // (no transfer into the old one is in flight)
-    if (c->h_order_mirror) (void)pool_host_free(c->h_order_mirror);
-    c->h_order_mirror = nullptr;
-    c->order_mirror_cap = 0;
-    c->export_epoch = 0;   // (what k_desc_export wrote went with the old array)
-    const size_t cap = (size_t)entries + (size_t)entries / 8 + 4096;
-    HIPCHK(c, pool_host_malloc(&c->h_order_mirror, sizeof(OrderEntry) * cap));
-    c->order_mirror_cap = cap;
+    c->pending.mirror_replaced();
+    const size_t cap = (size_t)entries + (size_t)entries / 8 + 4096;   // (behind the stream: no transfer into the old one is in flight)
+    TRY(regrow(c, true, c->stream, &c->order_mirror_cap, cap, {{&c->h_order_mirror, sizeof(OrderEntry) * cap}}));
   }
   *out = c->h_order_mirror;
   return GZ_OK;
@@ -552,39 +522,51 @@ int gz_order_fetch(gz_ctx* c, uint64_t lo, uint64_t hi, void* out) {
   if (!c || !out || lo > hi || hi > c->order_n) return GZ_E_ARG;
   const size_t bytes = sizeof(OrderEntry) * (size_t)(hi - lo);
   const char* mirror = (const char*)c->h_order_mirror;
-  if (bytes > 0 && mirror && (const char*)out >= mirror &&
-      (const char*)out + bytes <= mirror + sizeof(OrderEntry) * c->order_mirror_cap) {
-    // into the context's pinned mirror: no landing area, no second copy
-    HIPCHK(c, hipMemcpyAsync(out, c->d_order + lo, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return GZ_OK;
-  }
-  if (bytes > 0 && bytes <= ((size_t)4 << 20)) {   // the usual case: through the pinned landing area
-    void* res = nullptr;
-    TRY(result_buffer(c, bytes, &res));
-    HIPCHK(c, hipMemcpyAsync(res, c->d_order + lo, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(out, res, bytes);
-    return GZ_OK;
-  }
-  if (hi > lo)
-    HIPCHK(c, hipMemcpyAsync(out, c->d_order + lo, bytes, hipMemcpyDeviceToHost, c->stream));
+  // into the context's pinned mirror: no landing area, no second copy
+  const bool pinned = mirror && (const char*)out >= mirror &&
+                      (const char*)out + bytes <= mirror + sizeof(OrderEntry) * c->order_mirror_cap;
+  void* dst = out;
+  // the usual case: through the pinned landing area
+  if (!pinned && bytes > 0 && bytes <= ((size_t)4 << 20)) TRY(result_buffer(c, bytes, &dst));
+  if (bytes > 0) HIPCHK(c, hipMemcpyAsync(dst, c->d_order + lo, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (dst != out) memcpy(out, dst, bytes);
   return GZ_OK;
 }
 
 
 // ---- quick-select descent decided on the device (gz_kernels_order.h: k_desc_count / k_desc_swap)
-static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, float per_block,
-                           uint64_t threshold, int max_levels, size_t n_bound, bool publish = false) {
+// What a descent does to the context's current order; epoch: of this descent.
+static DescArgs desc_args(const gz_ctx* c, unsigned epoch, bool big, int derive, uint64_t n0, uint64_t last0,
+                          float per_block, uint64_t threshold, bool publish) {
+  DescArgs A;
+  A.a = c->d_order; A.st = c->d_desc_st; A.pv = c->d_desc_pv;
+  A.cnt_l = c->d_chunk; A.cnt_r = c->d_chunk + c->chunk_cap;
+  A.lpos = c->d_pos_l; A.rpos = c->d_pos_r;
+  A.max_chunks = big ? kDescMaxChunksBig : kDescMaxChunks;
+  A.epoch = epoch;
+  A.threshold = threshold < 16 ? 16 : threshold;
+  A.derive = derive; A.n0 = n0; A.last0 = last0; A.per_block = per_block;
+  A.total = c->d_order_off ? c->d_order_off + c->sg_n : nullptr;
+  A.counters = c->d_order_counters;
+  A.publish = publish ? 1 : 0;
+  A.max_bits = c->d_max_bits;
+  return A;
+}
+
+// What descend_enqueue put on the stream: levels launched; published: the first of them wrote the results slot;
+// exported: k_desc_export behind the last.  The caller makes it pending (Pending::descent_begun) or waits for it.
+struct DescentBegun { int levels; bool published, exported; };
+
+static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, float per_block, uint64_t threshold,
+                           int max_levels, size_t n_bound, bool publish, DescentBegun* out) {
   if (!c->d_desc_st) {
-    HIPCHK(c, pool_malloc((void**)&c->d_desc_st, sizeof(DescState) * (kDescMaxLevels + 3)));
+    HIPCHK(c, pool_malloc((void**)&c->d_desc_st, sizeof(DescState) * kDescStates));
     HIPCHK(c, pool_malloc((void**)&c->d_desc_pv, sizeof(DescPivot) * kDescMaxLevels));
-    HIPCHK(c, pool_host_malloc((void**)&c->h_desc, sizeof(DescState) * (kDescMaxLevels + 3)));
-    HIPCHK(c, hipMemsetAsync(c->d_desc_st, 0, sizeof(DescState) * (kDescMaxLevels + 3), c->stream));
-    c->desc_epoch = 0;
+    HIPCHK(c, pool_host_malloc((void**)&c->h_desc, sizeof(DescState) * kDescStates));
+    HIPCHK(c, hipMemsetAsync(c->d_desc_st, 0, sizeof(DescState) * kDescStates, c->stream));
   }
-  if (++c->desc_epoch == 0) c->desc_epoch = 1;
+  const unsigned epoch = c->pending.next_epoch();
   int levels = std::max(0, std::min(max_levels, kDescMaxLevels));
   const size_t nchunks = std::max<size_t>(1, (n_bound + kPartChunk - 1) / kPartChunk);
   bool big = nchunks > (size_t)kDescMaxChunks;   // (orders beyond 8.4 M entries: the instantiation with the larger tables)
@@ -592,25 +574,7 @@ static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, f
   if (getenv("GZ_EMU_DESC_BIG")) big = true;
 #endif
   if (nchunks > (size_t)kDescMaxChunksBig || nchunks > c->chunk_cap) levels = 0;   // the host drives these
-  DescArgs A;
-  A.a = c->d_order;
-  A.st = c->d_desc_st;
-  A.pv = c->d_desc_pv;
-  A.cnt_l = c->d_chunk;
-  A.cnt_r = c->d_chunk + c->chunk_cap;
-  A.lpos = c->d_pos_l;
-  A.rpos = c->d_pos_r;
-  A.max_chunks = big ? kDescMaxChunksBig : kDescMaxChunks;
-  A.epoch = c->desc_epoch;
-  A.threshold = threshold < 16 ? 16 : threshold;
-  A.derive = derive;
-  A.n0 = n0;
-  A.last0 = last0;
-  A.total = c->d_order_off ? c->d_order_off + c->sg_n : nullptr;
-  A.counters = c->d_order_counters;
-  A.per_block = per_block;
-  A.publish = publish && levels > 0 ? 1 : 0;
-  A.max_bits = c->d_max_bits;
+  const DescArgs A = desc_args(c, epoch, big, derive, n0, last0, per_block, threshold, publish && levels > 0);
   int swap_groups = std::min<int>((int)((n_bound + 1 + kPartChunk - 1) / kPartChunk), kDescSwapGrid);
   int count_groups = (int)std::min<size_t>(nchunks, (size_t)kDescCountGrid);
 #ifdef GZ_EMU
@@ -628,34 +592,28 @@ static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, f
   }
   // gz_order_build_auto_descend_begin: the prefix the driver fetches next goes to its host mirror
   // behind the last level (the driver's own bound on such a fetch: 2^19 entries)
-  c->export_epoch = 0;
-  if (publish && levels > 0 && c->h_order_mirror) {
+  const bool exported = publish && levels > 0 && c->h_order_mirror;
+  if (exported) {
     const unsigned long long max_entries = std::min<unsigned long long>(c->order_mirror_cap, 1ull << 19);
     // (its first workgroup also writes the descent's state into c->h_desc: no copy on the stream)
     GZ_LAUNCH(k_desc_export, dim3(128), dim3(256), c->stream, A, levels, (OrderEntry*)c->h_order_mirror, max_entries,
               (DescState*)c->h_desc);
     KCHK(c);
-    c->export_epoch = c->desc_epoch;
   } else {
-    HIPCHK(c, hipMemcpyAsync(c->h_desc, c->d_desc_st, sizeof(DescState) * (kDescMaxLevels + 3),
-                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_desc, c->d_desc_st, sizeof(DescState) * kDescStates, hipMemcpyDeviceToHost, c->stream));
   }
-  c->desc_levels = levels;
-  c->desc_pending = true;
-  if (A.publish) {
-    c->results_in_desc = true;
-    c->distance_in_desc = c->compare_pending;
-    c->results_epoch = c->desc_epoch;
-  }
+  *out = DescentBegun{levels, A.publish != 0, exported};
   return GZ_OK;
 }
 
-static int descend_collect(gz_ctx* c, uint64_t* log, int cap_levels, int* levels) {
+// The cut log of the `levels` launched as descent `pending.epoch`, once the stream has been waited for.
+static int descend_collect(gz_ctx* c, int launched, uint64_t* log, int cap_levels, int* levels) {
+  const unsigned epoch = c->pending.epoch;
   int n = 0;
-  for (int l = 0; l < c->desc_levels && n < cap_levels; ++l) {
+  for (int l = 0; l < launched && n < cap_levels; ++l) {
     const DescState& before = c->h_desc[l];
     const DescState& after = c->h_desc[l + 1];
-    if (after.epoch != c->desc_epoch || before.epoch != c->desc_epoch) break;
+    if (after.epoch != epoch || before.epoch != epoch) break;
     if (!(after.cut > before.lo && after.cut <= before.hi)) { c->err = "descent: cut outside its range"; return GZ_E_STATE; }
     log[3 * n + 0] = before.lo;
     log[3 * n + 1] = before.hi;
@@ -672,26 +630,49 @@ int gz_order_descend(gz_ctx* c, uint64_t last, uint64_t threshold, int max_level
   if (!c || !log || !levels || max_levels < 0) return GZ_E_ARG;
   *levels = 0;
   if (c->order_n == 0 || last >= c->order_n) return c->order_n == 0 ? GZ_OK : GZ_E_ARG;
-  TRY(descend_enqueue(c, 0, c->order_n, last, 0.0f, threshold, max_levels, c->order_n));
+  DescentBegun d{};
+  TRY(descend_enqueue(c, 0, c->order_n, last, 0.0f, threshold, max_levels, c->order_n, false, &d));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->desc_pending = false;
-  return descend_collect(c, log, max_levels, levels);
+  c->pending.descent_taken();   // (an earlier one that was pending: its states have been overwritten)
+  return descend_collect(c, d.levels, log, max_levels, levels);
 }
 
 int gz_order_descend_begin(gz_ctx* c, float per_block, uint64_t threshold, int max_levels) {
   DeviceScope ds_(c);
   if (!c || max_levels < 0) return GZ_E_ARG;
-  if (!c->order_pending) { c->err = "gz_order_build_auto_begin must precede gz_order_descend_begin"; return GZ_E_STATE; }
-  return descend_enqueue(c, 1, 0, 0, per_block, threshold, max_levels, std::max<size_t>(c->search_total, 1));
+  if (c->pending.order == Pending::kNoOrder) { c->err = "gz_order_build_auto_begin must precede gz_order_descend_begin"; return GZ_E_STATE; }
+  DescentBegun d{};
+  TRY(descend_enqueue(c, 1, 0, 0, per_block, threshold, max_levels, std::max<size_t>(c->search_total, 1), false, &d));
+  c->pending.descent_begun(d.levels, d.published, d.exported);
+  return GZ_OK;
+}
+
+// gz_order_build_auto_begin + gz_order_descend_begin in one call, with ONE transfer of results.
+int gz_order_build_auto_descend_begin(gz_ctx* c, int direction, int max_block_dist, double target_mul,
+                                      int use_distmap, const int32_t* next_cand, int count_below,
+                                      float limit, float per_block, uint64_t threshold, int max_levels) {
+  DeviceScope ds_(c);
+  if (!c || !next_cand || !is_direction(direction) || max_block_dist < 0 || max_levels < 0)
+    return GZ_E_ARG;
+  c->pending.void_up_to(Pending::kRide);   // (a failure below leaves gz_compare_end to fetch the distance itself)
+  TRY(order_auto_enqueue(c, direction, max_block_dist, target_mul, use_distmap, next_cand));
+  TRY(order_build_enqueue(c, direction, count_below, limit, true));
+  DescentBegun d{};
+  TRY(descend_enqueue(c, 1, 0, 0, per_block, threshold, max_levels, std::max<size_t>(c->search_total, 1), true, &d));
+  // (not published: no level was launched, the order is too large for the descent's tables)
+  if (!d.published) TRY(order_results_enqueue(c, nullptr));
+  c->pending.order_begun(d.published ? Pending::kResultsSlot : Pending::kOwnBuffer);
+  c->pending.descent_begun(d.levels, d.published, d.exported);
+  return GZ_OK;
 }
 
 int gz_order_exported(gz_ctx* c, uint64_t* entries) {
   if (!c || !entries) return GZ_E_ARG;
   *entries = 0;
-  if (c->desc_pending || c->order_pending) { c->err = "gz_order_descend_end must precede gz_order_exported"; return GZ_E_STATE; }
-  if (c->export_epoch == 0 || c->export_epoch != c->desc_epoch || !c->h_desc) return GZ_OK;
-  const DescState& p = c->h_desc[kDescMaxLevels + 2];
-  if (p.epoch == c->export_epoch && p.depth == 2 && p.lo <= c->order_n) *entries = p.lo;
+  if (c->pending.levels >= 0 || c->pending.order != Pending::kNoOrder) { c->err = "gz_order_descend_end must precede gz_order_exported"; return GZ_E_STATE; }
+  if (!c->pending.exported || !c->h_desc) return GZ_OK;
+  const DescState& p = c->h_desc[kDescExportSlot];
+  if (p.epoch == c->pending.epoch && p.depth == 2 && p.lo <= c->order_n) *entries = p.lo;
   return GZ_OK;
 }
 
@@ -700,10 +681,9 @@ int gz_order_descend_end(gz_ctx* c, uint64_t* log, int cap_levels, int* levels, 
   if (!c || !log || !levels || !last || cap_levels < 0) return GZ_E_ARG;
   *levels = 0;
   *last = 0;
-  if (!c->desc_pending) return GZ_OK;   // nothing was enqueued (or another build took its place)
-  if (c->order_pending) { c->err = "gz_order_build_auto_end must precede gz_order_descend_end"; return GZ_E_STATE; }
-  c->desc_pending = false;
-  TRY(descend_collect(c, log, cap_levels, levels));
+  if (c->pending.levels < 0) return GZ_OK;   // nothing was enqueued (or another build took its place)
+  if (c->pending.order != Pending::kNoOrder) { c->err = "gz_order_build_auto_end must precede gz_order_descend_end"; return GZ_E_STATE; }
+  TRY(descend_collect(c, c->pending.descent_taken(), log, cap_levels, levels));
   if (*levels > 0) *last = c->h_desc[0].last;
 #ifdef GZ_EMU
   // test hook of the emulation build only (tests/test_host_encoder.py): a device that derived

@@ -111,7 +111,7 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
     else { c->err = "a 4:2:0 frame is searched with component mask 1 or 6"; return GZ_E_ARG; }
   }
   TRY(ensure_block_mask(c));
-  void_pending_order(c);   // a new search grid: a pending order of the old one is void
+  c->pending.void_up_to(Pending::kOrder);   // a new search grid: a pending order of the old one is void, and its descent
   TRY(flush_order_advance(c));   // (an update of max_block_error that is still due belongs to the old grid)
   const int nb = c->nb;   // capacity of the per-block arrays: the luma grid
   const int gn = mode == 2 ? c->nbc : c->nb;

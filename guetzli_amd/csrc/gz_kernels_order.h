@@ -721,6 +721,10 @@ __global__ __launch_bounds__(256) void k_part_swap(OrderEntry* __restrict__ a, s
 constexpr int kDescMaxChunks = 4096;      // chunk tables of a workgroup: ranges up to 8.4 M entries (33 KB of LDS)
 constexpr int kDescMaxChunksBig = 16384;  // the instantiation for larger orders: up to 33.5 M entries (131 KB: one workgroup per CU)
 constexpr int kDescMaxLevels = 12;
+// The descent's state array: the range before every level and behind the last one, [0, kDescMaxLevels], then
+constexpr int kDescResultsSlot = kDescMaxLevels + 1;   // what the first level publishes (DescArgs::publish)
+constexpr int kDescExportSlot = kDescMaxLevels + 2;    // k_desc_export's report
+constexpr int kDescStates = kDescMaxLevels + 3;
 constexpr int kDescCountGrid = 2048;   // workgroups of k_desc_count (eight fit on a CU)
 constexpr int kDescSwapGrid = 1024;    // workgroups of k_desc_swap (four fit on a CU: 33 KB of LDS)
 
@@ -737,7 +741,7 @@ struct DescPivot {
 };
 struct DescArgs {
   OrderEntry* a;
-  DescState* st;                   // [kDescMaxLevels + 3]: the ranges, the results slot (publish), k_desc_export's
+  DescState* st;                   // [kDescStates]: the ranges, the results slot (publish), k_desc_export's
   DescPivot* pv;                   // [kDescMaxLevels]
   unsigned* cnt_l;                 // [chunks]
   unsigned* cnt_r;
@@ -752,7 +756,7 @@ struct DescArgs {
   const unsigned* counters;        // [0] blocks_to_change
   float per_block;                 // coefficients to change per block (processor.cc:685-687)
   // publish: the first level also copies what the host waits for at this point of an iteration
-  // into st[kDescMaxLevels + 1] -- lo = the order's size, hi = blocks_to_change, last = entries
+  // into st[kDescResultsSlot] -- lo = the order's size, hi = blocks_to_change, last = entries
   // below the limit, cut = the bits of the last Compare's distance, depth = 1 -- so that ONE
   // transfer of st brings everything (three small device-to-host copies less on the stream).
   int publish;
@@ -808,7 +812,7 @@ __global__ __launch_bounds__(256) void k_desc_count(DescArgs A, int level) {
     r.cut = A.max_bits ? *A.max_bits : 0u;
     r.depth = 1;
     r.epoch = A.epoch;
-    A.st[kDescMaxLevels + 1] = r;
+    A.st[kDescResultsSlot] = r;
   }
   DescState s;
   if (!desc_load(A, level, &s)) return;
@@ -1085,7 +1089,7 @@ __global__ __launch_bounds__(256) void k_desc_swap(DescArgs A, int level) {
 // the descent ended in -- what the search driver fetches next (guetzli_amd/host/processor.cc:
 // DeviceOrder::Prefetch) -- written straight into the context's page-locked host mirror, when the
 // descent got as far as the driver's own condition asks (range <= threshold) and the prefix fits
-// max_entries.  st[kDescMaxLevels + 2] tells the host: lo = entries exported (0: none), depth = 2.
+// max_entries.  st[kDescExportSlot] tells the host: lo = entries exported (0: none), depth = 2.
 // One dispatch on the stream instead of a host round trip after it.
 __global__ __launch_bounds__(256) void k_desc_export(DescArgs A, int levels, OrderEntry* __restrict__ dst,
                                                      unsigned long long max_entries,
@@ -1107,15 +1111,15 @@ __global__ __launch_bounds__(256) void k_desc_export(DescArgs A, int levels, Ord
     if (blockIdx.x == 0) {
       DescState r;
       r.lo = s_hi; r.hi = 0; r.last = 0; r.cut = 0; r.depth = 2; r.epoch = A.epoch;
-      A.st[kDescMaxLevels + 2] = r;
+      A.st[kDescExportSlot] = r;
       s_own = r;
     }
   }
   __syncthreads();
   // the descent's state (ranges, results slot, this kernel's own slot) for the host, straight into
   // its page-locked copy: thread 0 of the first workgroup has just written the last of it
-  if (blockIdx.x == 0 && host_state && threadIdx.x < kDescMaxLevels + 3)
-    host_state[threadIdx.x] = threadIdx.x == kDescMaxLevels + 2 ? s_own : A.st[threadIdx.x];
+  if (blockIdx.x == 0 && host_state && threadIdx.x < kDescStates)
+    host_state[threadIdx.x] = threadIdx.x == kDescExportSlot ? s_own : A.st[threadIdx.x];
   const unsigned long long n = s_hi;
   // 16 bytes (two entries) per thread and step
   const unsigned long long pairs = n >> 1;

@@ -123,6 +123,122 @@ def patched(single_stream):
     return run
 
 
+# ---- phase B's order protocol (entry_phaseb.h): the synchronous, the split and the fused form
+PER_BLOCK, THRESHOLD, LEVELS = 2.0, 16, 12   # the descent's derivation of `last`, its floor, the log's capacity
+
+
+def searched(L, **config):
+    """A candidate with phase A's block search made, max_block_error zeroed and a distance map in place."""
+    ctx = candidate(L, **config)
+    off, _, _ = ctx.block_zeroing_orders()
+    ctx.order_reset()
+    ctx.compare()
+    return ctx, off
+
+
+def launches(text, kernel):
+    return sum(ln.startswith("launch %s " % kernel) for ln in text.splitlines())
+
+
+def phase_b_fused(single_stream):
+    """The search loop's iteration: the next order and its descent enqueued behind the evaluation in flight as ONE
+    call, whose results and the Compare's distance arrive in the descent's state; gz_order_advance's update then rides
+    on the next order's k_weights_gather."""
+    def run(L):
+        ctx, off = searched(L, single_stream=single_stream)
+        with ctx:
+            next_cand = np.zeros(ctx.nb, np.int32)
+            with Log(L) as log:
+                ctx.order_host_mirror(int(off[-1]))
+                ctx.compare_begin()
+                ctx.order_build_auto_descend_begin(1, 1, 1.0, True, next_cand, PER_BLOCK, THRESHOLD, LEVELS)
+                ctx.compare_end()
+                total, btc, _ = ctx.order_build_auto_end()
+                cuts, last = ctx.order_descend_end(LEVELS)
+                exported = ctx.order_exported()
+                ctx.order_advance(0.25, 1)
+                ctx.compare_begin()
+                ctx.order_build_auto_descend_begin(1, 1, 1.0, True, next_cand, PER_BLOCK, THRESHOLD, LEVELS)
+                ctx.compare_end()
+                total2, _, _ = ctx.order_build_auto_end()
+                cuts2, _ = ctx.order_descend_end(LEVELS)
+            assert total > THRESHOLD and btc > 0 and len(cuts) >= 1 and 0 < last < total
+            assert 0 < exported <= total, "k_desc_export wrote no prefix into the host mirror"
+            assert total2 > 0 and len(cuts2) >= 1
+            assert launches(log.text, "k_desc_export") == 2
+            assert launches(log.text, "k_order_advance") == 0, "the advance was to ride on k_weights_gather"
+        return log.text
+    return run
+
+
+def phase_b_split(L):
+    """gz_order_build_auto_begin, gz_order_descend_begin behind it, the ends; two advances in a row."""
+    ctx, _ = searched(L, single_stream=0)
+    with ctx:
+        next_cand = np.zeros(ctx.nb, np.int32)
+        with Log(L) as log:
+            ctx.order_build_auto_begin(1, 1, 1.0, True, next_cand)
+            ctx.order_descend_begin(PER_BLOCK, THRESHOLD, LEVELS)
+            total, btc, _ = ctx.order_build_auto_end()
+            cuts, last = ctx.order_descend_end(LEVELS)
+            ctx.order_advance(0.25, 1)
+            ctx.order_advance(0.5, 1)
+        assert total > THRESHOLD and btc > 0 and len(cuts) >= 1 and 0 < last < total
+        assert launches(log.text, "k_desc_export") == 0
+        assert launches(log.text, "k_order_advance") == 1, "the first of two advances is made by a launch of its own"
+    return log.text
+
+
+def phase_b_sync(L):
+    """The order from the caller's arrays, the descent and one partition in one call each, the fetches' three paths
+    (into the pinned mirror, through the landing area into pageable memory, an empty range), an upload."""
+    ctx, off = searched(L, single_stream=0)
+    with ctx:
+        nb = ctx.nb
+        with Log(L) as log:
+            total, btc, _ = ctx.order_build(1, np.zeros(nb, np.int32), np.zeros(nb, np.float32),
+                                            np.ones(nb, np.float32))
+            cuts = ctx.order_descend(total // 4, THRESHOLD, LEVELS)
+            cut = ctx.order_partition(0, total)
+            mirror = ctx.order_host_mirror(total)
+            ctx.order_fetch(0, total, out=mirror)
+            entries = ctx.order_fetch(0, total)
+            ctx.order_fetch(total, total)
+            ctx.order_upload(entries)
+        assert total == int(off[-1]) and btc > 0 and len(cuts) >= 1 and 0 < cut <= total
+        assert np.array_equal(mirror, entries)
+        assert launches(log.text, "k_order_sizes") == 1 and launches(log.text, "k_part_swap") == 1
+    return log.text
+
+
+def bulk_steps_without_statistics(L):
+    """gz_apply_candidate_steps before any gz_jpeg_histograms: k_apply_steps, no symbol statistics."""
+    ctx, off = searched(L, single_stream=0)
+    with ctx:
+        nb = ctx.nb
+        ctx.order_build_auto(1, 1, 1.0, True, np.zeros(nb, np.int32))
+        sel = np.flatnonzero((np.arange(nb) % 3 == 0) & (np.diff(off) > 0)).astype(np.int32)
+        with Log(L) as log:
+            ctx.apply_candidate_steps(1, sel, np.ones(sel.size, np.int32))
+        assert sel.size > 0
+        assert launches(log.text, "k_apply_steps") == 1 and launches(log.text, "k_apply_steps_hist") == 0
+    return log.text
+
+
+def bulk_edits(L):
+    """gz_apply_coeff_edits with more than 4096 positions: through device memory, not the staging buffer."""
+    with candidate(L, single_stream=0) as ctx:
+        n = 4100
+        assert n <= 3 * ctx.nb * 64
+        pos = (np.arange(n, dtype=np.int64) * 6 + 1).astype(np.int32)   # distinct, spread over all three components
+        assert pos[-1] < 3 * ctx.nb * 64
+        with Log(L) as log:
+            ctx.apply_coeff_edits(pos, np.full(n, 3, np.int16))
+        assert launches(log.text, "k_apply_coeff_edits") == 1
+        assert sum(ln.startswith("memcpy h2d ") for ln in log.text.splitlines()) == 2, "the device-memory arm"
+    return log.text
+
+
 def compare_420(L):
     with L.context(rgb(), TARGET) as ctx:
         ctx.set_config(single_stream=0)
@@ -163,6 +279,12 @@ SCENARIOS = {
     "compare_one_stream_distmap": compare(1, True),
     "patched_three_streams": patched(0),
     "patched_one_stream": patched(1),
+    "phase_b_fused_three_streams": phase_b_fused(0),
+    "phase_b_fused_one_stream": phase_b_fused(1),
+    "phase_b_split": phase_b_split,
+    "phase_b_sync": phase_b_sync,
+    "bulk_steps_without_statistics": bulk_steps_without_statistics,
+    "bulk_edits": bulk_edits,
     "compare_420": compare_420,
     "block_zeroing_orders": block_zeroing_orders,
     "probes": probes,
