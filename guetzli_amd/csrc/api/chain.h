@@ -132,14 +132,16 @@ int blur_plane(gz_ctx* c, hipStream_t stream, const SrcPack<SrcPlain, 1>& src, f
   return GZ_E_ARG;
 }
 
-int setup_blur_cfg(gz_ctx* c, BlurCfg* cfg, float sigma, float border_ratio) {
+// ctx_owns: cfg is a member of the context, whose record takes the scales; a local cfg's block is its caller's to free.
+int setup_blur_cfg(gz_ctx* c, BlurCfg* cfg, float sigma, float border_ratio, bool ctx_owns) {
   make_taps_host(sigma, cfg);
   cfg->border_ratio = border_ratio;
   std::vector<float> xl, xh, yl, yh;
   border_scales_host(*cfg, c->w, &xl, &xh);
   border_scales_host(*cfg, c->h, &yl, &yh);
   const int r = cfg->r;
-  if (cfg->d_scale == nullptr) HIPCHK(c, pool_malloc((void**)&cfg->d_scale, sizeof(float) * 4 * r));
+  if (ctx_owns) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&cfg->d_scale, sizeof(float) * 4 * r}}));
+  else HIPCHK(c, pool_malloc((void**)&cfg->d_scale, sizeof(float) * 4 * r));
   std::vector<float> all;
   all.insert(all.end(), xl.begin(), xl.end());
   all.insert(all.end(), xh.begin(), xh.end());
@@ -439,10 +441,11 @@ int enqueue_scan_offsets(gz_ctx* c, int which, hipStream_t stream, const unsigne
                          unsigned long long* d_off) {
   const int max_tiles = gz_div_up(c->nb, kScanTile) + 1;
   const size_t bytes = (size_t)max_tiles * (8 + 8 + 4) + 64;
-  if (!c->d_scan_state[which]) {
-    HIPCHK(c, pool_malloc(&c->d_scan_state[which], bytes));
+  if (!c->made.scan_state[which]) {
+    TRY(regrow(c, stream, nullptr, 0, {{&c->d_scan_state[which], bytes}}));
     HIPCHK(c, hipMemsetAsync(c->d_scan_state[which], 0, bytes, stream));   // ticket 0, no epoch yet
     c->scan_epoch[which] = 0;
+    c->made.scan_state[which] = true;
   }
   char* base = (char*)c->d_scan_state[which];
   ScanState st;
@@ -462,7 +465,7 @@ int enqueue_scan_offsets(gz_ctx* c, int which, hipStream_t stream, const unsigne
 }
 
 int stage_chroma_samples(gz_ctx* c, hipStream_t stream, const int16_t* d_coeffs) {
-  if (!c->d_csamp) HIPCHK(c, pool_malloc((void**)&c->d_csamp, 2 * csamp_plane(c)));
+  if (!c->d_csamp) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->d_csamp, 2 * csamp_plane(c)}}));
   GZ_LAUNCH(k_chroma_samples, dim3(gz_div_up(c->nbc, kBlocksPerWG)), dim3(256), stream,
             d_coeffs + (size_t)c->coff[1] * 64, d_coeffs + (size_t)c->coff[2] * 64, c->cbw, c->nbc,
             c->d_csamp);
@@ -600,7 +603,7 @@ int download_plane(gz_ctx* c, const float* dev, float* host) {
 
 int ensure_pip(gz_ctx* c) {
   if (c->have_pip) return GZ_OK;
-  HIPCHK(c, pool_malloc((void**)&c->extra_arena, sizeof(float) * c->plane * 17));
+  TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->extra_arena, sizeof(float) * c->plane * 17}}));
   for (int i = 0; i < 17; ++i) c->free_planes.push_back(c->extra_arena + (size_t)i * c->plane);
   alloc_psycho(c, &c->pip);
   for (int i = 0; i < 3; ++i) { c->mask_out[i] = take_plane(c); c->mask_dc_out[i] = take_plane(c); }
@@ -616,7 +619,7 @@ int ensure_pip(gz_ctx* c) {
 int ensure_block_mask(gz_ctx* c) {
   if (c->have_block_mask) return GZ_OK;
   TRY(ensure_pip(c));
-  if (!c->d_block_mask) HIPCHK(c, pool_malloc((void**)&c->d_block_mask, sizeof(float) * 3 * c->nb));
+  if (!c->d_block_mask) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->d_block_mask, sizeof(float) * 3 * c->nb}}));
   const hipStream_t stream = c->stream;
   dim3 grid(gz_div_up(c->w, 256), c->h);
   c->lin_is_cand = c->xyb_is_cand = false;   // (lin[] takes the original)

@@ -184,6 +184,10 @@ hipError_t pool_stream_set_create(StreamSet* out, bool prio_main, int rot) {
   return e;
 #endif
 }
+// The streams of a set that leaves the pool, or never got into it (a set whose creation failed half way has null ones).
+inline void stream_set_teardown(const StreamSet& s_) {
+  for (hipStream_t s : {s_.own, s_.side, s_.side2, s_.entropy}) if (s) (void)hipStreamDestroy(s);
+}
 void pool_stream_set_destroy(const StreamSet& s_, bool prio_main, int rot) {
 #ifndef GZ_EMU
   if (s_.own && s_.side && s_.side2 && s_.entropy && pool_limit_bytes() != 0) {
@@ -195,10 +199,7 @@ void pool_stream_set_destroy(const StreamSet& s_, bool prio_main, int rot) {
     if (p.sets.count(key) < 4) { p.sets.insert(std::make_pair(key, s_)); return; }
   }
 #endif
-  if (s_.own) (void)hipStreamDestroy(s_.own);
-  if (s_.side) (void)hipStreamDestroy(s_.side);
-  if (s_.side2) (void)hipStreamDestroy(s_.side2);
-  if (s_.entropy) (void)hipStreamDestroy(s_.entropy);
+  stream_set_teardown(s_);
 }
 hipError_t pool_event_create(hipEvent_t* out) {
 #ifndef GZ_EMU
@@ -231,7 +232,7 @@ void pool_event_destroy(hipEvent_t e_) {
 // Pinned host staging for the small per-iteration uploads (step lists, coefficient edits,
 // next_cand, Huffman codes): the caller's buffer is copied here, the H2D copy is asynchronous
 // and nobody has to wait for it -- the buffer is only waited for when it is reused.
-// (stage_reserve / stage_sent / stage_free and the result buffer: below the error macros they use)
+// (stage_reserve / stage_sent and the result buffer: below the error macros they use)
 struct HostStage {
   void* h = nullptr;
   size_t cap = 0;
@@ -274,6 +275,14 @@ struct Pending {
 };
 
 struct gz_ctx {
+  // What the context owns: the ADDRESSES of its members that hold a device block, a pinned block or an event, each
+  // entered once, when regrow() / own_event() first fill it (the context lives on the heap and never moves).
+  // gz_destroy gives back what they hold by walking these two lists; nothing else frees a member.
+  struct Owned { void** p; bool host; };
+  std::vector<Owned> owned;
+  std::vector<hipEvent_t*> owned_events;
+  // The groups made on first use, each made only through its mark here (regrow() below: set last)
+  struct Made { bool entropy = false, rank = false, order_blocks = false, part = false, descent = false, step_delta = false, scan_state[2] = {false, false}; } made;
   int device = 0;
   int w = 0, h = 0, bw = 0, bh = 0, nb = 0, pitch = 0;
   size_t plane = 0;   // floats per plane
@@ -390,6 +399,8 @@ struct gz_ctx {
   // Pending two-phase calls: `pending` (the order, its descent, the Compare: written by Pending's transitions only),
   // scan_pending, adv_pending.  A pending state is entered as the last state change before `return GZ_OK`; a call that
   // replaces what a pending call worked on voids it first (void_up_to), and a voided call's _end fails or returns nothing.
+  // Memory has no claim of its own: a group of buffers made on first use is there if and only if its mark in `made` is
+  // set, and the mark is set behind the group's allocations AND its initialising memsets / copies (regrow, below).
   // Rules:  DROP BEFORE WRITE -- a call that writes d_orig, d_cand, d_rgb / pi0, lin[] or xyb[] drops every claim that
   // depends on that buffer before its first copy or launch.  RE-ARM ONLY ON SUCCESS -- a claim is set again only as the
   // last state change before `return GZ_OK`.  Dropping is always safe: it costs one full reconstruction or opsin pass.
@@ -459,30 +470,61 @@ namespace {
     }                                                                                \
   } while (0)
 
-// Growing buffers that share one capacity: the old ones go back to the pool -- behind everything on `behind`, if
-// given: the pool hands memory on without waiting -- with the pointers null and the capacity zero BEFORE the allocations
-// that may fail (nothing is left half-owned), and the capacity set behind the last of them.
-struct Regrown { void** p; size_t bytes; };
-static int regrow(gz_ctx* c, bool host, hipStream_t behind, size_t* cap, size_t new_cap, std::initializer_list<Regrown> bufs) {
-  if (behind) HIPCHK(c, hipStreamSynchronize(behind));
-  for (const Regrown& b : bufs) { if (host) pool_host_free(*b.p); else pool_free(*b.p); *b.p = nullptr; }
-  *cap = 0;
-  for (const Regrown& b : bufs) HIPCHK(c, host ? pool_host_malloc(b.p, b.bytes) : pool_malloc(b.p, b.bytes));
-  *cap = new_cap;
+// The one way a context comes by memory: the buffers of `bufs`, device or pinned, all of them or none.  What they held
+// goes back to the pool first, the pointers null and the capacity zero BEFORE the allocations that may fail; if one
+// fails, those already obtained go back too (nothing is left half-owned).  Every member is entered into the context's
+// record the first time it is filled.
+// Growing buffers that share a capacity: `cap` is set behind the last allocation, and the old buffers are given back
+// behind everything on `behind`, if given: the pool hands memory on without waiting.
+// A group made once: cap == nullptr, and the caller sets the group's mark (gz_ctx::made) as its LAST statement, behind
+// the memsets and copies that initialise the group -- a failed attempt is repeated in full by the next call, which waits
+// for `behind` only if that attempt left it something to give back.
+struct Regrown { void** p; size_t bytes; bool host = false; };
+static void give_back(void** p, bool host) { if (host) pool_host_free(*p); else pool_free(*p); *p = nullptr; }
+static int regrow(gz_ctx* c, hipStream_t behind, size_t* cap, size_t new_cap, std::initializer_list<Regrown> bufs) {
+  const bool held = std::any_of(bufs.begin(), bufs.end(), [](const Regrown& b) { return *b.p != nullptr; });
+  if (behind && (cap || held)) HIPCHK(c, hipStreamSynchronize(behind));
+  for (const Regrown& b : bufs) give_back(b.p, b.host);
+  if (cap) *cap = 0;
+  for (const Regrown& b : bufs) {
+    const hipError_t e = b.host ? pool_host_malloc(b.p, b.bytes) : pool_malloc(b.p, b.bytes);
+    if (e != hipSuccess) {
+      *b.p = nullptr;
+      for (const Regrown& u : bufs) give_back(u.p, u.host);
+      (void)hipGetLastError();   // (the repeated call's first launch check must not find this failure)
+      c->err = std::string(b.host ? "pinned" : "device") + " allocation of " + std::to_string(b.bytes) + " bytes: " + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? GZ_E_NOMEM : GZ_E_HIP;
+    }
+    if (std::none_of(c->owned.begin(), c->owned.end(), [&](const gz_ctx::Owned& o) { return o.p == b.p; })) c->owned.push_back({b.p, b.host});
+  }
+  if (cap) *cap = new_cap;
   return GZ_OK;
+}
+// ... and by an event (one member, filled once).
+static int own_event(gz_ctx* c, hipEvent_t* e) {
+  HIPCHK(c, pool_event_create(e));
+  c->owned_events.push_back(e);
+  return GZ_OK;
+}
+// gz_destroy's walk of the record (the caller has synchronised the streams).
+static void release_owned(gz_ctx* c) {
+  for (hipEvent_t* e : c->owned_events) { pool_event_destroy(*e); *e = nullptr; }
+  for (const gz_ctx::Owned& o : c->owned) give_back(o.p, o.host);
+  c->owned_events.clear();
+  c->owned.clear();
 }
 
 // Reserves `bytes` of the staging buffer (waiting for its previous upload if that is still
 // running) and returns it; stage_sent() marks the upload that was just enqueued on `stream`.
 static int stage_reserve(gz_ctx* c, HostStage* st, size_t bytes, void** out) {
-  if (!st->ev) HIPCHK(c, pool_event_create(&st->ev));
+  if (!st->ev) if (int rc = own_event(c, &st->ev)) return rc;
   if (st->busy) {
     HIPCHK(c, hipEventSynchronize(st->ev));
     st->busy = false;
   }
   if (bytes > st->cap) {
     const size_t cap = bytes + bytes / 2 + 4096;
-    if (int rc = regrow(c, true, nullptr, &st->cap, cap, {{&st->h, cap}})) return rc;
+    if (int rc = regrow(c, nullptr, &st->cap, cap, {{&st->h, cap, true}})) return rc;
   }
   *out = st->h;
   return GZ_OK;
@@ -495,15 +537,10 @@ static int stage_sent(gz_ctx* c, HostStage* st, hipStream_t stream) {
 static int result_buffer(gz_ctx* c, size_t bytes, void** out) {
   if (bytes > c->h_res_cap) {
     const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    if (int rc = regrow(c, true, nullptr, &c->h_res_cap, cap, {{&c->h_res, cap}})) return rc;
+    if (int rc = regrow(c, nullptr, &c->h_res_cap, cap, {{&c->h_res, cap, true}})) return rc;
   }
   *out = c->h_res;
   return GZ_OK;
-}
-static void stage_free(HostStage* st) {
-  if (st->ev) { (void)hipEventSynchronize(st->ev); pool_event_destroy(st->ev); }
-  if (st->h) (void)pool_host_free(st->h);
-  st->h = nullptr; st->ev = nullptr; st->cap = 0; st->busy = false;
 }
 
 const int kNumPlanes = 9 + 9 + 3 + 3 + 3 + 2 + 2 + 10 + 2;   // pi0, pi1, lin, tmp, xyb, lf_raw, hfp, 10 singles, sup0[2]

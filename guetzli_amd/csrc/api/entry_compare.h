@@ -95,7 +95,7 @@ int gz_set_coeff_blocks(gz_ctx* c, const int32_t* block_index, int n, const int1
   c->lin_is_cand = c->xyb_is_cand = false;
   if ((size_t)n > c->blkidx_cap) {
     const size_t cap = std::max<size_t>((size_t)n, std::min<size_t>((size_t)c->nb, 2 * c->blkidx_cap + 1024));
-    TRY(regrow(c, false, c->stream, &c->blkidx_cap, cap,
+    TRY(regrow(c, c->stream, &c->blkidx_cap, cap,
                {{(void**)&c->d_blkidx, sizeof(int32_t) * cap}, {(void**)&c->d_blkdata, cap * 384}}));
   }
   HIPCHK(c, hipMemcpyAsync(c->d_blkidx, block_index, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));

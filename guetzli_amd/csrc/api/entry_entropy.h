@@ -8,14 +8,12 @@ extern "C" {
 
 // ------------------------------------------------------------- device entropy coder ----
 static int ensure_entropy_buffers(gz_ctx* c) {
-  if (c->d_jq) return GZ_OK;
-  HIPCHK(c, pool_malloc((void**)&c->d_jq, sizeof(int) * 192));
-  HIPCHK(c, pool_malloc((void**)&c->d_hist, sizeof(unsigned) * 1536));
-  HIPCHK(c, pool_malloc((void**)&c->d_code_depth, 1536));
-  HIPCHK(c, pool_malloc((void**)&c->d_code_bits, sizeof(unsigned short) * 1536));
-  HIPCHK(c, pool_malloc((void**)&c->d_mcu_bits, sizeof(unsigned) * c->nb));
-  HIPCHK(c, pool_malloc((void**)&c->d_mcu_off, sizeof(unsigned long long) * (c->nb + 1)));
-  HIPCHK(c, pool_malloc((void**)&c->d_ff_count, sizeof(unsigned long long)));
+  if (c->made.entropy) return GZ_OK;
+  TRY(regrow(c, nullptr, nullptr, 0,
+             {{(void**)&c->d_jq, sizeof(int) * 192}, {(void**)&c->d_hist, sizeof(unsigned) * 1536}, {(void**)&c->d_code_depth, 1536},
+              {(void**)&c->d_code_bits, sizeof(unsigned short) * 1536}, {(void**)&c->d_mcu_bits, sizeof(unsigned) * c->nb},
+              {(void**)&c->d_mcu_off, sizeof(unsigned long long) * (c->nb + 1)}, {(void**)&c->d_ff_count, sizeof(unsigned long long)}}));
+  c->made.entropy = true;
   return GZ_OK;
 }
 
@@ -89,13 +87,8 @@ int gz_jpeg_scan_begin(gz_ctx* c, int ncomp, const uint8_t* depth, const uint16_
   // once, so that no host round trip is needed between counting the bits and writing them.
   const size_t cap_words = (size_t)c->nb * 3 * (64 + 1) + 8;
   if (cap_words > c->words_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->entropy_stream));   // the pool hands memory on without waiting
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)pool_free(c->d_words);
-    c->d_words = nullptr;
-    c->words_cap = 0;
-    HIPCHK(c, pool_malloc((void**)&c->d_words, sizeof(unsigned) * cap_words));
-    c->words_cap = cap_words;
+    HIPCHK(c, hipStreamSynchronize(c->entropy_stream));   // the pool hands memory on without waiting: behind both streams
+    TRY(regrow(c, c->stream, &c->words_cap, cap_words, {{(void**)&c->d_words, sizeof(unsigned) * cap_words}}));
   }
   // own stream, behind the candidate (not behind a Compare that gz_compare_begin enqueued)
   hipStream_t es = c->entropy_stream;
@@ -145,7 +138,7 @@ int gz_jpeg_scan_begin(gz_ctx* c, int ncomp, const uint8_t* depth, const uint16_
             c->d_ff_count);
   KCHK(c);
   // (a buffer of its own: the calls allowed between the two halves use result_buffer)
-  if (!c->h_scan_result) HIPCHK(c, pool_host_malloc(&c->h_scan_result, 16));
+  if (!c->h_scan_result) TRY(regrow(c, nullptr, nullptr, 0, {{&c->h_scan_result, 16, true}}));
   HIPCHK(c, hipMemcpyAsync(c->h_scan_result, d_total, 8, hipMemcpyDeviceToHost, es));
   HIPCHK(c, hipMemcpyAsync((char*)c->h_scan_result + 8, c->d_ff_count, 8, hipMemcpyDeviceToHost, es));
   c->have_scan = false;
@@ -193,11 +186,8 @@ int gz_jpeg_scan_keep(gz_ctx* c) {
   if (!c->have_scan) { c->err = "no scan to keep"; return GZ_E_STATE; }
   const size_t need_words = (size_t)((c->scan_bits + 7) / 8 / 4 + 4);
   if (need_words > c->words_kept_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the pool hands memory on without waiting
-    (void)pool_free(c->d_words_kept);
-    c->d_words_kept = nullptr;
-    c->words_kept_cap = need_words + need_words / 4 + 1024;
-    HIPCHK(c, pool_malloc((void**)&c->d_words_kept, sizeof(unsigned) * c->words_kept_cap));
+    const size_t cap = need_words + need_words / 4 + 1024;
+    TRY(regrow(c, c->stream, &c->words_kept_cap, cap, {{(void**)&c->d_words_kept, sizeof(unsigned) * cap}}));
   }
   HIPCHK(c, hipMemcpyAsync(c->d_words_kept, c->d_words, sizeof(unsigned) * need_words,
                            hipMemcpyDeviceToDevice, c->stream));

@@ -8,9 +8,9 @@ static bool is_direction(int d) { return d == 1 || d == -1; }
 
 // ------------------------------------------------- global candidate order (phase B) ----
 static int ensure_order_capacity(gz_ctx* c, size_t n) {
-  if (!c->d_part) {
-    HIPCHK(c, pool_malloc((void**)&c->d_part, sizeof(PartScalars)));
-    HIPCHK(c, pool_malloc((void**)&c->d_order_counters, sizeof(unsigned) * 2));
+  if (!c->made.part) {
+    TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->d_part, sizeof(PartScalars)}, {(void**)&c->d_order_counters, sizeof(unsigned) * 2}}));
+    c->made.part = true;
   }
   if (n <= c->order_cap) return GZ_OK;
   const size_t cap = n + n / 8 + 4096;
@@ -18,7 +18,7 @@ static int ensure_order_capacity(gz_ctx* c, size_t n) {
   // (gz_order_partition records at most cap / 2 swapped pairs per side; the descent's per-chunk
   // stopper lists need a full chunk's worth per chunk)
   const size_t pos_bytes = sizeof(unsigned) * c->chunk_cap * kPartChunk;
-  return regrow(c, false, c->stream, &c->order_cap, cap,
+  return regrow(c, c->stream, &c->order_cap, cap,
                 {{(void**)&c->d_order, sizeof(OrderEntry) * cap}, {(void**)&c->d_pos_l, pos_bytes},
                  {(void**)&c->d_pos_r, pos_bytes}, {(void**)&c->d_chunk, sizeof(unsigned) * 4 * c->chunk_cap}});
 }
@@ -26,7 +26,7 @@ static int ensure_order_capacity(gz_ctx* c, size_t n) {
 // d_edit_pos / d_edit_val: coefficient edits, and the bulk steps' (blocks, counts) staging
 static int ensure_edit_capacity(gz_ctx* c, size_t n) {
   const size_t cap = n + n / 2 + 4096;
-  return n <= c->edit_cap ? GZ_OK : regrow(c, false, c->stream, &c->edit_cap, cap, {{(void**)&c->d_edit_pos, sizeof(int) * cap},
+  return n <= c->edit_cap ? GZ_OK : regrow(c, c->stream, &c->edit_cap, cap, {{(void**)&c->d_edit_pos, sizeof(int) * cap},
                                                                                    {(void**)&c->d_edit_val, sizeof(short) * cap}});
 }
 
@@ -42,16 +42,14 @@ static int flush_order_advance(gz_ctx* c) {
 }
 
 static int ensure_order_block_arrays(gz_ctx* c) {
-  if (c->d_order_nb) return GZ_OK;
-  const int nb = c->nb;
-  HIPCHK(c, pool_malloc((void**)&c->d_order_nb, sizeof(unsigned) * nb));
-  HIPCHK(c, pool_malloc((void**)&c->d_order_off, sizeof(unsigned long long) * (nb + 1)));
-  HIPCHK(c, pool_malloc((void**)&c->d_order_groups, sizeof(unsigned) * 2 * gz_div_up(nb, kOrderGroup)));
-  HIPCHK(c, pool_malloc((void**)&c->d_next_cand, sizeof(int) * nb));
-  HIPCHK(c, pool_malloc((void**)&c->d_weight, sizeof(float) * nb));
-  HIPCHK(c, pool_malloc((void**)&c->d_max_err, sizeof(float) * nb));
-  HIPCHK(c, pool_malloc((void**)&c->d_wflag, nb));
+  if (c->made.order_blocks) return GZ_OK;
+  const size_t nb = (size_t)c->nb;
+  TRY(regrow(c, c->stream, nullptr, 0,
+             {{(void**)&c->d_order_nb, sizeof(unsigned) * nb}, {(void**)&c->d_order_off, sizeof(unsigned long long) * (nb + 1)},
+              {(void**)&c->d_order_groups, sizeof(unsigned) * 2 * gz_div_up(c->nb, kOrderGroup)}, {(void**)&c->d_next_cand, sizeof(int) * nb},
+              {(void**)&c->d_weight, sizeof(float) * nb}, {(void**)&c->d_max_err, sizeof(float) * nb}, {(void**)&c->d_wflag, nb}}));
   HIPCHK(c, hipMemsetAsync(c->d_max_err, 0, sizeof(float) * nb, c->stream));
+  c->made.order_blocks = true;
   return GZ_OK;
 }
 
@@ -82,7 +80,7 @@ static int order_build_enqueue(gz_ctx* c, int direction, int count_below, float 
 // The order's size and its two counters on their way to pinned memory of the host, behind the construction
 // (dst: nullptr = the context's own buffer, where an _end finds them).
 static int order_results_enqueue(gz_ctx* c, gz_ctx::OrderResults* dst) {
-  if (!dst && !c->h_order_results) HIPCHK(c, pool_host_malloc((void**)&c->h_order_results, sizeof(*c->h_order_results)));
+  if (!dst && !c->h_order_results) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->h_order_results, sizeof(*c->h_order_results), true}}));
   if (!dst) dst = c->h_order_results;
   HIPCHK(c, hipMemcpyAsync(&dst->total, c->d_order_off + c->sg_n, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(dst->counters, c->d_order_counters, 8, hipMemcpyDeviceToHost, c->stream));
@@ -182,7 +180,7 @@ static int order_auto_enqueue(gz_ctx* c, int direction, int max_block_dist, doub
   const float target = c->target;
   const float* d_bmax = c->d_block_max;
   if (c->sg_factor == 2 && use_distmap) {   // search grid of 16x16 areas: group the 8x8 maxima
-    if (!c->d_gmax) HIPCHK(c, pool_malloc((void**)&c->d_gmax, sizeof(float) * ((c->w + 15) / 16) * ((c->h + 15) / 16)));
+    if (!c->d_gmax) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->d_gmax, sizeof(float) * ((c->w + 15) / 16) * ((c->h + 15) / 16)}}));
     GZ_LAUNCH(k_block_max_group, dim3(gz_div_up(nb, 256)), dim3(256), c->stream,
               (const float*)c->d_block_max, c->bw, c->bh, bw, bh, 2, c->d_gmax);
     KCHK(c);
@@ -239,7 +237,7 @@ int gz_order_build_auto_end(gz_ctx* c, uint64_t* total, int32_t* blocks_to_chang
 int gz_order_advance(gz_ctx* c, float val_threshold, int direction) {
   DeviceScope ds_(c);
   if (!c || !is_direction(direction)) return GZ_E_ARG;
-  if (!c->d_weight) { c->err = "gz_order_build_auto must precede gz_order_advance"; return GZ_E_STATE; }
+  if (!c->made.order_blocks) { c->err = "gz_order_build_auto must precede gz_order_advance"; return GZ_E_STATE; }
   // max_block_error[i] += block_weight[i] * val_threshold * direction -- due, not launched: the next order's
   // k_weights_gather makes the update with the weights it is about to replace (nothing reads max_block_error before
   // it; whoever else touches it or the weights calls flush_order_advance first)
@@ -282,11 +280,11 @@ static PatchPlanes patch_planes(const gz_ctx* c, bool on) {
 static int steps_with_statistics(gz_ctx* c, const int* h, int* d_blocks, int n, int direction, const StepGeom& sg,
                                  bool patch, PatchClaims* claims) {
   // (zeroed once: k_steps_hist_sum leaves the counters zeroed)
-  if (!c->d_step_delta) {
-    HIPCHK(c, pool_malloc((void**)&c->d_step_delta, sizeof(unsigned) * 768 * kStepDeltaCopies));
+  if (!c->made.step_delta) {
+    TRY(regrow(c, c->stream, nullptr, 0, {{(void**)&c->d_step_delta, sizeof(unsigned) * 768 * kStepDeltaCopies}, {&c->h_step_delta, sizeof(int) * 768, true}}));
     HIPCHK(c, hipMemsetAsync(c->d_step_delta, 0, sizeof(unsigned) * 768 * kStepDeltaCopies, c->stream));
+    c->made.step_delta = true;
   }
-  if (!c->h_step_delta) HIPCHK(c, pool_host_malloc(&c->h_step_delta, sizeof(int) * 768));
   // (persistent workgroups: four per CU's worth at most, each wavefront taking several blocks)
   // (the kernel reads the staging buffer itself -- page-locked and mapped: a copy command in front of
   // it costs more in hand-overs between commands than the 8 bytes per block cost over the bus)
@@ -305,7 +303,7 @@ static int steps_with_statistics(gz_ctx* c, const int* h, int* d_blocks, int n, 
   bool ahead = false;
   if (patch) {
     // gz_steps_histogram_delta waits for the sums, not for the stream: the patches run while the host reads them
-    if (!c->ev_steps) HIPCHK(c, pool_event_create(&c->ev_steps));
+    if (!c->ev_steps) TRY(own_event(c, &c->ev_steps));
     HIPCHK(c, hipEventRecord(c->ev_steps, c->stream));
     c->step_delta_event = true;
     GZ_LAUNCH((k_reconstruct_listed<false>), dim3(gz_div_up(n, kBlocksPerWG)), dim3(256), c->stream, (const int*)d_blocks, n,
@@ -338,7 +336,7 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
   DeviceScope ds_(c);
   if (!c || n < 0 || (n > 0 && (!blocks || !counts)) || !is_direction(direction))
     return GZ_E_ARG;
-  if (!c->have_search || !c->d_next_cand || !c->have_cand || !c->have_orig) {
+  if (!c->have_search || !c->made.order_blocks || !c->have_cand || !c->have_orig) {
     c->err = "gz_order_build must precede gz_apply_candidate_steps";
     return GZ_E_STATE;
   }
@@ -511,7 +509,7 @@ int gz_order_host_mirror(gz_ctx* c, uint64_t entries, void** out) {
   if (entries > c->order_mirror_cap) {
     c->pending.mirror_replaced();
     const size_t cap = (size_t)entries + (size_t)entries / 8 + 4096;   // (behind the stream: no transfer into the old one is in flight)
-    TRY(regrow(c, true, c->stream, &c->order_mirror_cap, cap, {{&c->h_order_mirror, sizeof(OrderEntry) * cap}}));
+    TRY(regrow(c, c->stream, &c->order_mirror_cap, cap, {{&c->h_order_mirror, sizeof(OrderEntry) * cap, true}}));
   }
   *out = c->h_order_mirror;
   return GZ_OK;
@@ -560,11 +558,11 @@ struct DescentBegun { int levels; bool published, exported; };
 
 static int descend_enqueue(gz_ctx* c, int derive, uint64_t n0, uint64_t last0, float per_block, uint64_t threshold,
                            int max_levels, size_t n_bound, bool publish, DescentBegun* out) {
-  if (!c->d_desc_st) {
-    HIPCHK(c, pool_malloc((void**)&c->d_desc_st, sizeof(DescState) * kDescStates));
-    HIPCHK(c, pool_malloc((void**)&c->d_desc_pv, sizeof(DescPivot) * kDescMaxLevels));
-    HIPCHK(c, pool_host_malloc((void**)&c->h_desc, sizeof(DescState) * kDescStates));
+  if (!c->made.descent) {
+    TRY(regrow(c, c->stream, nullptr, 0, {{(void**)&c->d_desc_st, sizeof(DescState) * kDescStates}, {(void**)&c->d_desc_pv, sizeof(DescPivot) * kDescMaxLevels},
+                                          {(void**)&c->h_desc, sizeof(DescState) * kDescStates, true}}));
     HIPCHK(c, hipMemsetAsync(c->d_desc_st, 0, sizeof(DescState) * kDescStates, c->stream));
+    c->made.descent = true;
   }
   const unsigned epoch = c->pending.next_epoch();
   int levels = std::max(0, std::min(max_levels, kDescMaxLevels));

@@ -11,15 +11,15 @@ extern "C" {
 int gz_probe_blur(gz_ctx* c, const float* in, float sigma, float border_ratio, float* out) {
   DeviceScope ds_(c);
   if (!c || !in || !out) return GZ_E_ARG;
-  BlurCfg cfg;
-  TRY(setup_blur_cfg(c, &cfg, sigma, border_ratio));
+  BlurCfg cfg;   // a local: its scales are this call's, freed below on every path, and never enter the context's record
+  int rc = setup_blur_cfg(c, &cfg, sigma, border_ratio, false);
   float* src = c->xyb[0];
   c->xyb_is_cand = false;   // (xyb[] as scratch)
-  TRY(upload_planes(c, in, &src, 1));
+  if (rc == GZ_OK) rc = upload_planes(c, in, &src, 1);
   SrcPack<SrcPlain, 1> s; s.s[0].p = src;
   PostStore<1> post; post.out[0] = c->xyb[1];
   // the same kernels gz_compare uses for each radius: fused below 16, two passes from 16 up
-  int rc = blur_plane(c, c->stream, s, c->tmp[0], post, cfg);
+  if (rc == GZ_OK) rc = blur_plane(c, c->stream, s, c->tmp[0], post, cfg);
   if (rc == GZ_OK) rc = download_plane(c, c->xyb[1], out);
   (void)hipStreamSynchronize(c->stream);
   (void)pool_free(cfg.d_scale);

@@ -120,16 +120,14 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
   c->sg_n = gn;
   c->sg_factor = mode == 2 ? 2 : 1;
   c->sg_mask = comp_mask;
-  if (!c->d_rank_cnt) {
-    HIPCHK(c, pool_malloc((void**)&c->d_rank_cnt, sizeof(int32_t) * nb));
-    HIPCHK(c, pool_malloc((void**)&c->d_rank_idx, (size_t)nb * 192));
-    HIPCHK(c, pool_malloc((void**)&c->d_rank_tables, sizeof(float) * 384));
-    HIPCHK(c, pool_malloc((void**)&c->d_out_cnt, sizeof(int32_t) * nb));
-    HIPCHK(c, pool_malloc((void**)&c->d_out_idx, (size_t)nb * 192));
-    HIPCHK(c, pool_malloc((void**)&c->d_out_err, sizeof(float) * nb * 192));
-    HIPCHK(c, pool_malloc((void**)&c->d_csr_off, sizeof(int32_t) * ((size_t)nb + 1)));
+  if (!c->made.rank) {
+    TRY(regrow(c, c->stream, nullptr, 0,
+               {{(void**)&c->d_rank_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_rank_idx, (size_t)nb * 192}, {(void**)&c->d_rank_tables, sizeof(float) * 384},
+                {(void**)&c->d_out_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_out_idx, (size_t)nb * 192},
+                {(void**)&c->d_out_err, sizeof(float) * nb * 192}, {(void**)&c->d_csr_off, sizeof(int32_t) * ((size_t)nb + 1)}}));
     HIPCHK(c, hipMemcpyAsync(c->d_rank_tables, kOrderCsf, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_rank_tables + 192, kOrderBias, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
+    c->made.rank = true;
   }
   {  // input_order of every block, ranked on the device with std::sort's permutation
     RankArgs r;
@@ -233,6 +231,12 @@ static void search_args_common(gz_ctx* c, SearchArgs* a) {
   a->out_cnt = c->d_out_cnt; a->out_idx = c->d_out_idx; a->out_err = c->d_out_err;
 }
 
+// gz_compare_blocks / _block_pixels: positions, payload and results share one device block kept by the context
+static int ensure_cmp_stage(gz_ctx* c, size_t need) {
+  const size_t cap = std::max<size_t>(need, 4096);
+  return need <= c->cmp_stage_cap ? GZ_OK : regrow(c, c->stream, &c->cmp_stage_cap, cap, {{&c->d_cmp_stage, cap}});
+}
+
 int gz_compare_blocks(gz_ctx* c, int n, const int32_t* block_xy, const int16_t* coeffs, double* out) {
   DeviceScope ds_(c);
   if (!c || n < 0 || (n > 0 && (!block_xy || !coeffs || !out))) return GZ_E_ARG;
@@ -244,15 +248,7 @@ int gz_compare_blocks(gz_ctx* c, int n, const int32_t* block_xy, const int16_t* 
   TRY(ensure_block_mask(c));
   // staging: positions, coefficients and results share one device block kept by the context
   const size_t need = (size_t)n * (8 + 384 + 8);
-  if (need > c->cmp_stage_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)pool_free(c->d_cmp_stage);
-    c->d_cmp_stage = nullptr;
-    c->cmp_stage_cap = 0;
-    const size_t cap = std::max<size_t>(need, 4096);
-    HIPCHK(c, pool_malloc(&c->d_cmp_stage, cap));
-    c->cmp_stage_cap = cap;
-  }
+  TRY(ensure_cmp_stage(c, need));
   int32_t* d_xy = (int32_t*)c->d_cmp_stage;
   double* d_out = (double*)((char*)c->d_cmp_stage + (size_t)n * 8);
   int16_t* d_blk = (int16_t*)((char*)c->d_cmp_stage + (size_t)n * 16);
@@ -277,15 +273,7 @@ int gz_compare_block_pixels(gz_ctx* c, int n, const int32_t* block_xy, const uin
   TRY(ensure_block_mask(c));
   // staging: positions, pixels and results share one device block kept by the context
   const size_t need = (size_t)n * (8 + 8 + 192);
-  if (need > c->cmp_stage_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)pool_free(c->d_cmp_stage);
-    c->d_cmp_stage = nullptr;
-    c->cmp_stage_cap = 0;
-    const size_t cap = std::max<size_t>(need, 4096);
-    HIPCHK(c, pool_malloc(&c->d_cmp_stage, cap));
-    c->cmp_stage_cap = cap;
-  }
+  TRY(ensure_cmp_stage(c, need));
   int32_t* d_xy = (int32_t*)c->d_cmp_stage;
   double* d_out = (double*)((char*)c->d_cmp_stage + (size_t)n * 8);
   uint8_t* d_px = (uint8_t*)c->d_cmp_stage + (size_t)n * 16;

@@ -44,7 +44,8 @@ extern "C" {
 #define GZ_E_NO_DEVICE (-2)  /* no usable gfx950 device / HIP runtime failure at init */
 #define GZ_E_HIP (-3)        /* a HIP call failed; see gz_last_error */
 #define GZ_E_STATE (-4)      /* call sequence violated (e.g. compare before coefficients) */
-#define GZ_E_NOMEM (-5)
+#define GZ_E_NOMEM (-5)      /* out of device or page-locked memory: the context stays valid and holds nothing of the
+                                failed call's half-made buffers; the call may be repeated (after freeing memory) */
 
 typedef struct gz_ctx gz_ctx;
 

@@ -1,6 +1,7 @@
 // Phase B's two-phase calls (tests/test_phase_b_protocol.py has the table) as plain C calls, for a run of the C ABI's
 // host side under AddressSanitizer and UBSan with no interpreter in the process: the fused iteration as the search
-// loop drives it, a begin that supersedes a begin, a new frame between begin and end, one failed launch.
+// loop drives it, a begin that supersedes a begin, a new frame between begin and end, one failed launch, and two calls
+// that run out of memory in the middle of a group made on first use and are repeated on the same context.
 // Built by hand with the emulation of the kernels (tests/emu/hip_emu.h), not part of the suite (two minutes of g++):
 //   g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -DGZ_EMU
 //       -Itests/emu -Iinclude -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-unused-variable
@@ -18,6 +19,7 @@
 #include "guetzli_amd.h"
 
 extern "C" void gz_emu_fail_launch(long n);
+extern "C" void gz_emu_fail_alloc(long n);
 
 #define EXPECT(call, want)                                                                            \
   do {                                                                                                \
@@ -33,7 +35,7 @@ static const int W = 100, H = 84, NB = 13 * 11, LEVELS = 12;
 static const float TARGET = 0.971769f, PER_BLOCK = 2.0f;
 
 // A context as phase B finds it: a candidate, phase A's block search, max_block_error zeroed, a distance map.
-static gz_ctx* searched(uint64_t* candidates) {
+static gz_ctx* searched(uint64_t* candidates, bool reset = true) {
   std::vector<uint8_t> rgb((size_t)3 * W * H);
   for (int y = 0; y < H; ++y)
     for (int x = 0; x < W; ++x)
@@ -52,7 +54,7 @@ static gz_ctx* searched(uint64_t* candidates) {
   std::vector<float> errs(cap);
   EXPECT(gz_block_zeroing_orders_masked(c, 7, 3, 1, off.data(), idx.data(), errs.data(), cap), GZ_OK);
   *candidates = (uint64_t)off[NB];
-  EXPECT(gz_order_reset(c), GZ_OK);
+  if (reset) EXPECT(gz_order_reset(c), GZ_OK);
   float d = 0;
   EXPECT(gz_compare(c, &d, nullptr, nullptr), GZ_OK);
   return c;
@@ -122,6 +124,26 @@ int main() {
   EXPECT(gz_compare_end(c, &d), GZ_E_STATE);
   EXPECT(gz_order_exported(c, &exported), GZ_OK);
   if (levels != 0 || exported != 0) { fprintf(stderr, "a new frame left %d levels, %llu exported\n", levels, (unsigned long long)exported); return 1; }
+  gz_destroy(c);
+
+  // out of memory inside a group made on first use (the order's block arrays, the entropy coder's buffers): the call
+  // fails, the context stays valid, and the same call repeated makes the group in full
+  c = searched(&candidates, false);
+  uint64_t total2 = 0;
+  gz_emu_fail_alloc(2);
+  EXPECT(gz_order_build_auto(c, 1, 1, 1.0, 1, zero.data(), 0, 0.0f, &total, &btc, &below), GZ_E_NOMEM);
+  gz_emu_fail_alloc(-1);
+  EXPECT(gz_order_build_auto(c, 1, 1, 1.0, 1, zero.data(), 0, 0.0f, &total2, &btc, &below), GZ_OK);
+  if (total2 == 0 || total2 > candidates) { fprintf(stderr, "the repeated order has %llu entries\n", (unsigned long long)total2); return 1; }
+  int q[192];
+  for (int i = 0; i < 192; ++i) q[i] = 3;
+  std::vector<uint32_t> counts(1536), counts2(1536);
+  gz_emu_fail_alloc(1);
+  EXPECT(gz_jpeg_histograms(c, q, counts.data()), GZ_E_NOMEM);
+  gz_emu_fail_alloc(-1);
+  EXPECT(gz_jpeg_histograms(c, q, counts.data()), GZ_OK);
+  EXPECT(gz_jpeg_histograms(c, q, counts2.data()), GZ_OK);
+  if (counts != counts2 || counts[0] + counts[1] == 0) { fprintf(stderr, "the repeated histograms differ from the next ones\n"); return 1; }
   gz_destroy(c);
   printf("ok\n");
   return 0;

@@ -424,7 +424,26 @@ inline hipError_t hipHostFree(void* p) {
   return hipSuccess;
 }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
+// Copy fault injection, in the style of gz_emu_fail_launch: every asynchronous copy / fill is counted;
+// gz_emu_fail_copy(n) makes the (n + 1)-th one from now on return an error (once) and do nothing -- not enqueued, so
+// not in the enqueue log either.  (One thread: no lock.)
+namespace hipemu {
+struct CopyBook { long calls = 0, fail_at = -1; };
+inline CopyBook& copy_book() { static CopyBook b; return b; }
+inline bool copy_should_fail() {
+  CopyBook& b = copy_book();
+  if (b.calls++ != b.fail_at) return false;
+  b.fail_at = -1;
+  return true;
+}
+}  // namespace hipemu
+extern "C" __attribute__((used, visibility("default"))) inline void gz_emu_fail_copy(long n) {
+  hipemu::CopyBook& b = hipemu::copy_book();
+  b.fail_at = n < 0 ? -1 : b.calls + n;
+}
+extern "C" __attribute__((used, visibility("default"))) inline long gz_emu_copy_calls(void) { return hipemu::copy_book().calls; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t stream) {
+  if (hipemu::copy_should_fail()) return hipErrorInvalidValue;
   static const char* const kinds[] = {"h2d", "d2h", "d2d", "h2h", "default"};
   hipemu::log_enqueue(std::string("memcpy ") + kinds[kind] + " " + std::to_string(n), "s", stream, nullptr);
   memcpy(d, s, n);
@@ -432,6 +451,7 @@ inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind
 }
 inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t stream) {
+  if (hipemu::copy_should_fail()) return hipErrorInvalidValue;
   hipemu::log_enqueue("memset " + std::to_string(n), "s", stream, nullptr);
   memset(d, v, n);
   return hipSuccess;

@@ -13,6 +13,9 @@ same way, and the n-th one from now on can be made to fail.  Checked here:
     fails, and a caller that goes on gets a Compare that does not trust planes the failed call may have left stale
     (the context's claims, context.h), with the distance of a fresh context given the same coefficients -- or, after a
     failed downsample, a refusal to quantize a half-written original.
+  * every entry point that makes buffers on first use, with EVERY one of its allocations failing in turn, and the
+    first order, block search and scan with every asynchronous copy or fill failing: the call fails, the SAME context
+    repeats it with the clean call's results bit for bit, and gz_destroy leaves nothing allocated.
 (The emulation build allocates directly instead of through the product's pools, so "still allocated" is exact.)
 CPU only."""
 import ctypes as C
@@ -283,3 +286,194 @@ def test_downsample_launch_failures_leave_no_original(emu, L, planes):
         assert ctx.frame_layout()[0] == 1
         ctx.close()
     sweep_launches(emu, lambda: patch_ready(L, rgb, search=False)[0], call, after)
+
+
+# ---- a failed call is repeated on the same context: every group the context makes on first use is all-or-nothing and
+# counts as made only behind its initialisation (context.h, regrow), so the repeat finds nothing half-made
+def _eq(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_eq(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return a == b
+
+
+FIXED_CODES = (np.full((2, 3, 256), 8, np.uint8), np.tile(np.arange(256, dtype=np.uint16), (2, 3, 1)))   # 8 bits a symbol
+
+
+def quantized(L, rgb):
+    ctx = L.context(rgb, TARGET)
+    ctx.encode_rgb(download=False)
+    ctx.quantize(Q, download=False)
+    return ctx
+
+
+def searched(L, rgb):
+    """... and phase A's block search, and a distance map (max_block_error is zeroed with the arrays it lives in)."""
+    ctx = quantized(L, rgb)
+    ctx.cnt = np.diff(ctx.block_zeroing_orders()[0])
+    ctx.compare()
+    return ctx
+
+
+def zeros(ctx):
+    return np.zeros(ctx.search_blocks, np.int32)
+
+
+def ordered(L, rgb, histograms=False):
+    ctx = searched(L, rgb)
+    if histograms:
+        ctx.jpeg_histograms(Q)
+    ctx.total = ctx.order_build_auto(1, 1, 1.0, True, zeros(ctx))[0]
+    return ctx
+
+
+def scanned(L, rgb):
+    ctx = quantized(L, rgb)
+    ctx.jpeg_histograms(Q)
+    ctx.jpeg_scan(3, *FIXED_CODES)
+    return ctx
+
+
+def _scan(ctx):
+    return ctx.jpeg_scan(3, *FIXED_CODES), ctx.jpeg_scan_bytes()
+
+
+def _scan_keep(ctx):
+    ctx.jpeg_scan_keep()
+    return ctx.jpeg_scan_bytes(kept=True)
+
+
+def _compare_blocks(ctx):
+    xy = np.array([[0, 0], [1, 1], [1, 0]], np.int32)
+    co = ctx.get_coeffs()
+    return ctx.compare_blocks(xy, np.stack([co[:, y * ctx.bw + x] for x, y in xy]))
+
+
+def _fused(ctx):
+    ctx.order_build_auto_descend_begin(1, 1, 1.0, True, zeros(ctx), 2.0, 16, 12)
+    return ctx.order_build_auto_end(), ctx.order_descend_end(12)
+
+
+def _steps(ctx):
+    sel = np.flatnonzero(ctx.cnt > 0)[:1].astype(np.int32)   # one block of four: a minority, the patch path
+    ctx.apply_candidate_steps(1, sel, np.minimum(ctx.cnt[sel], 2).astype(np.int32))
+    return ctx.steps_histogram_delta(), ctx.get_coeffs()
+
+
+def _edits(ctx):
+    ctx.apply_coeff_edits(*edits_of(ctx, 6, 7))
+    return ctx.get_coeffs()
+
+
+def _mirror_fetch(ctx):
+    return ctx.order_fetch(0, ctx.total, ctx.order_host_mirror(ctx.total)).copy()
+
+
+# (name, the calls that bring a fresh context to the state the step needs, the step -> its results)
+LAZY_STEPS = [
+    ("gz_jpeg_histograms", quantized, lambda ctx: ctx.jpeg_histograms(Q)),
+    ("gz_jpeg_scan", lambda L, rgb: (lambda ctx: (ctx.jpeg_histograms(Q), ctx)[1])(quantized(L, rgb)), _scan),
+    ("gz_jpeg_scan_keep", scanned, _scan_keep),
+    ("gz_block_zeroing_orders", quantized, lambda ctx: ctx.block_zeroing_orders()),
+    ("gz_compare_blocks", quantized, _compare_blocks),
+    ("gz_order_build_auto", searched, lambda ctx: (lambda r: (r, ctx.order_fetch(0, r[0])))(ctx.order_build_auto(1, 1, 1.0, True, zeros(ctx)))),
+    ("gz_order_build_auto_descend_begin .. _end", searched, _fused),
+    ("gz_order_descend", ordered, lambda ctx: (ctx.order_descend(ctx.total // 2, 16, 3), ctx.order_fetch(0, ctx.total))),
+    ("gz_apply_candidate_steps + gz_steps_histogram_delta", lambda L, rgb: ordered(L, rgb, histograms=True), _steps),
+    ("gz_apply_coeff_edits", quantized, _edits),
+    ("gz_order_host_mirror + gz_order_fetch", ordered, _mirror_fetch),
+]
+
+
+def sweep_allocations(emu, L, rgb, name, setup, call, min_allocs=1):
+    """call(setup()) once cleanly: its results, the distance of a Compare behind it, its allocations counted.  Then for
+    EVERY allocation n of it, on a fresh context in the same state: allocation n fails -> GZ_E_NOMEM; the same call
+    repeated on the same context -> the clean call's results, bit for bit; a Compare -> the clean context's distance;
+    gz_destroy -> nothing left allocated."""
+    base = live(emu)
+    ctx = setup(L, rgb)
+    before = emu.gz_emu_alloc_calls()
+    exp = call(ctx)
+    n_allocs = emu.gz_emu_alloc_calls() - before
+    exp_dist = ctx.compare(want_distmap=False, want_block_max=False)[0]
+    ctx.close()
+    assert live(emu) == base, f"{name}: a clean call leaves allocations behind"
+    assert n_allocs >= min_allocs, (name, n_allocs)
+    for n in range(n_allocs):
+        ctx = setup(L, rgb)
+        emu.gz_emu_fail_alloc(n)
+        try:
+            with pytest.raises(GuetzliAmdError, match="GZ_E_NOMEM"):
+                call(ctx)
+        finally:
+            emu.gz_emu_fail_alloc(-1)
+        got = call(ctx)
+        assert _eq(got, exp), f"{name}: repeated after allocation {n} of {n_allocs} failed, the call gives other results"
+        assert bits_of(ctx.compare(want_distmap=False, want_block_max=False)[0]) == bits_of(exp_dist), (name, n)
+        ctx.close()
+        assert live(emu) == base, f"{name}: allocation {n} failing leaves {live(emu)} (device bytes, host bytes, blocks, events)"
+    return n_allocs
+
+
+def bits_of(x):
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def test_a_context_survives_every_lazy_allocation_failing(emu, L):
+    """The C ABI's caller may free memory and repeat a call that returned GZ_E_NOMEM.  Every allocation index of every
+    step is swept (nothing sampled): 16x16 is four blocks and an order of 557 entries."""
+    rgb = np.ascontiguousarray(images.crop(16, 16, 100, 60))
+    counts = {name: sweep_allocations(emu, L, rgb, name, setup, call) for name, setup, call in LAZY_STEPS}
+    # the groups made on first use are in there: the entropy coder's seven buffers and the landing area; the block mask,
+    # the probe arena and the search's seven; the order's block arrays, its counters and its four growing buffers
+    assert counts["gz_jpeg_histograms"] >= 8 and counts["gz_block_zeroing_orders"] >= 9, counts
+    assert counts["gz_order_build_auto"] >= 14 and counts["gz_order_descend"] >= 3, counts
+    # 4:2:0: the chroma samples (d_csamp) of the search with component mask 6, the 16x16 maxima (d_gmax) of its order
+    rgb = np.ascontiguousarray(images.crop(32, 32, 100, 60))
+
+    def downsampled(L, rgb):
+        ctx = L.context(rgb, TARGET)
+        ctx.encode_rgb(download=False)
+        ctx.downsample(download=False)
+        ctx.quantize(Q, download=False)
+        return ctx
+
+    def searched420(L, rgb):
+        ctx = downsampled(L, rgb)
+        ctx.block_zeroing_orders(comp_mask=6)
+        ctx.compare()
+        return ctx
+    n = sweep_allocations(emu, L, rgb, "4:2:0 gz_block_zeroing_orders_masked(6)", downsampled,
+                          lambda ctx: ctx.block_zeroing_orders(comp_mask=6))
+    assert n >= 10, n
+    n = sweep_allocations(emu, L, rgb, "4:2:0 gz_order_build_auto", searched420,
+                          lambda ctx: ctx.order_build_auto(1, 1, 1.0, True, zeros(ctx)))
+    assert n >= 15, n
+
+
+def test_initialisation_failures_leave_the_group_unmade(emu, L):
+    """A group's memset or table upload fails to enqueue: the call fails, and the repeat makes the group again -- its
+    results are the clean call's bit for bit (the emulation poisons fresh memory with 0xCD: a group that counted as made
+    without its initialisation shows in max_block_error, the ranking tables or the scan's look-back flags)."""
+    emu.gz_emu_fail_copy.argtypes = [C.c_long]
+    emu.gz_emu_copy_calls.restype = C.c_long
+    rgb = np.ascontiguousarray(images.crop(16, 16, 100, 60))
+    first_scan = LAZY_STEPS[1]
+    for name, setup, call in (LAZY_STEPS[5], LAZY_STEPS[3], first_scan):
+        ctx = setup(L, rgb)
+        before = emu.gz_emu_copy_calls()
+        exp = call(ctx)
+        n_copies = emu.gz_emu_copy_calls() - before
+        ctx.close()
+        assert n_copies >= 3, (name, n_copies)
+        for n in range(n_copies):   # (every asynchronous copy and fill of the call, the group's initialisation among them)
+            ctx = setup(L, rgb)
+            emu.gz_emu_fail_copy(n)
+            try:
+                with pytest.raises(GuetzliAmdError, match="GZ_E_HIP"):
+                    call(ctx)
+            finally:
+                emu.gz_emu_fail_copy(-1)
+            assert _eq(call(ctx), exp), f"{name}: repeated after copy {n} of {n_copies} failed, the call gives other results"
+            ctx.close()
