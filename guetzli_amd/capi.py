@@ -52,6 +52,8 @@ SIGNATURES = {
     "gz_set_orig_coeffs_420": (_I, [_P, _P]),
     "gz_downsample": (_I, [_P, _P]),
     "gz_downsample_planes": (_I, [_P, _P, _P, _P, _P]),
+    "gz_downsample_silver": (_I, [_P, _P, _P]),
+    "gz_probe_silver_yuv420": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gz_frame_layout": (_I, [_P, _P, _P, _P]),
     "gz_quantize": (_I, [_P, _P, _P]),
     "gz_set_coeffs": (_I, [_P, _P]),
@@ -227,8 +229,8 @@ class Library:
 
     def probe_math(self, op, a, b=None, c=None, p=(), outs=1, device=0):
         """gz_probe_math: op = GZ_MATH_* of include/guetzli_amd.h; float arrays (doubles for
-        GZ_MATH_INTERP_LUT512 = 15, int32 for GZ_MATH_QUANT_DIV = 16); returns [outs][n]."""
-        dt = np.float64 if op == 15 else np.int32 if op == 16 else np.float32
+        GZ_MATH_INTERP_LUT512 = 15 and GZ_MATH_POW_TO_FLOAT = 17, int32 for GZ_MATH_QUANT_DIV = 16); returns [outs][n]."""
+        dt = np.float64 if op in (15, 17) else np.int32 if op == 16 else np.float32
         a = np.ascontiguousarray(a, dt)
         b = None if b is None else np.ascontiguousarray(b, dt)
         c = None if c is None else np.ascontiguousarray(c, dt)
@@ -238,6 +240,19 @@ class Library:
         self.check(self.lib.gz_probe_math(device, op, n, _ptr(a), _ptr(b), _ptr(c),
                                           _ptr(pp) if pp.size else None, pp.size, _ptr(out)))
         return out
+
+    def probe_silver_yuv420(self, srgb, guard_log2=40, device=0):
+        """gz_probe_silver_yuv420: RGBToYUV420 of a packed sRGB image on the device -> (y, u, v, counters), float32 [h][w]
+        planes and (cell-passes evaluated, cell-passes redone on the host).  guard_log2: 40 as the encoder runs it,
+        -1 every cell through the host path, 64 no guard."""
+        rgb = np.ascontiguousarray(srgb, np.uint8)
+        h, w, ch = rgb.shape
+        assert ch == 3
+        y, u, v = (np.zeros((h, w), np.float32) for _ in range(3))
+        cnt = np.zeros(2, np.uint64)
+        self.check(self.lib.gz_probe_silver_yuv420(device, _ptr(rgb), w, h, int(guard_log2), _ptr(y), _ptr(u), _ptr(v),
+                                                   _ptr(cnt)))
+        return y, u, v, (int(cnt[0]), int(cnt[1]))
 
     def div2_sweep(self, numerators, stride=1, sample_every=1 << 20, device=0):
         """gz_probe_div2_sweep: (mismatches, sampled quotients [samples][len(numerators)])."""
@@ -369,6 +384,15 @@ class Context:
         self._chk(self.L.lib.gz_downsample_planes(self.handle, _ptr(pl[0]), _ptr(pl[1]), _ptr(pl[2]), _ptr(out)))
         self.cfac = 2
         return out
+
+    def downsample_silver(self, download=True):
+        """The whole use_silver_screen branch of OutputImage::Downsample on the device -> (coefficients of the 4:2:0
+        frame, (cell-passes evaluated, cell-passes redone on the host))."""
+        out = self._coeff_buf(2) if download else None
+        cnt = np.zeros(2, np.uint64)
+        self._chk(self.L.lib.gz_downsample_silver(self.handle, _ptr(out), _ptr(cnt)))
+        self.cfac = 2
+        return out, (int(cnt[0]), int(cnt[1]))
 
     def quantize(self, q=None, download=True):
         qq = None if q is None else np.ascontiguousarray(q, np.int32)

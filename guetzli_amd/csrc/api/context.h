@@ -282,7 +282,7 @@ struct gz_ctx {
   std::vector<Owned> owned;
   std::vector<hipEvent_t*> owned_events;
   // The groups made on first use, each made only through its mark here (regrow() below: set last)
-  struct Made { bool entropy = false, rank = false, order_blocks = false, part = false, descent = false, step_delta = false, scan_state[2] = {false, false}; } made;
+  struct Made { bool entropy = false, rank = false, order_blocks = false, part = false, descent = false, step_delta = false, scan_state[2] = {false, false}, silver = false; } made;
   int device = 0;
   int w = 0, h = 0, bw = 0, bh = 0, nb = 0, pitch = 0;
   size_t plane = 0;   // floats per plane
@@ -426,6 +426,8 @@ struct gz_ctx {
   // memory costs 27 us per round trip on this system, into pinned memory 15)
   void* h_res = nullptr; size_t h_res_cap = 0;
   void* d_cmp_stage = nullptr; size_t cmp_stage_cap = 0;   // gz_compare_blocks / _block_pixels staging
+  // gz_downsample_silver (made.silver): the list of cells for the host, GammaToLinear of a byte, the pinned + mapped staging
+  unsigned* d_silver_list = nullptr; float* d_silver_lut = nullptr; float* h_silver = nullptr;
   size_t search_total = 0;   // candidates phase A produced (bounds every global order)
   unsigned long long search_evaluations = 0;   // CompareBlock evaluations of the last block search
   float last_distance = 0.0f;

@@ -1,4 +1,4 @@
-// C ABI: context-free block transforms (gz_encode_rgb_only, double-precision DCT and its two users), the frame layout switch, OutputImage::Downsample (4:2:0).
+// C ABI: context-free block transforms (gz_encode_rgb_only, double-precision DCT and its two users), the frame layout switch, OutputImage::Downsample (4:2:0; use_silver_screen on the device: silver_run, gz_downsample_silver).
 // (part of the one translation unit gz_api.hip, which includes these files in order; split by
 // concern in round 5 -- no declaration here is visible outside libguetzli_amd.so but the C ABI)
 #pragma once
@@ -232,6 +232,165 @@ int gz_downsample_planes(gz_ctx* c, const float* y, const float* u, const float*
   if (coeffs_out)
     HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_orig, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_orig = true;
+  return GZ_OK;
+}
+
+
+// ------------------------------------------------ use_silver_screen on the device ----
+// RGBToYUV420 (preprocess_downsample.cc:452-476) by the kernels of gz_kernels_silver.h: the init pass and twenty
+// rounds, one launch each.  A cell whose device power could not be proven to round like libm's pow wrote nothing
+// and is on the device's list; behind every launch the listed cells are gathered into the pinned staging, a chunk
+// at a time, redone here with libm (gz_silver_ref.h: the same CellEval the kernels run) and scattered back before
+// the next launch is enqueued.  One wait per launch reads the list's length and its first chunk together.
+namespace {
+// GammaToLinear of a byte, by the host's libm: exact by construction
+const float* silver_lut() {
+  static const std::vector<float> lut = [] {
+    std::vector<float> v(256);
+    for (int i = 0; i < 256; ++i) v[i] = gz_silver::GammaToLinear(static_cast<float>(i));
+    return v;
+  }();
+  return lut.data();
+}
+// One gathered cell (kSilverIn floats, k_silver_gather's layout) -> kSilverOut floats for k_silver_patch.
+void silver_host_cell(bool init, const float* in, float* out) {
+  float rec[4][3], yrec[4], yuv[3];
+  memcpy(rec, in, sizeof(rec));
+  gz_silver::LibmPow pw;
+  gz_silver::CellEval(rec, (int)in[24], (int)in[25], pw, yrec, yuv);
+  if (init) {
+    for (int s = 0; s < 4; ++s) out[s] = yrec[s];
+    out[4] = yuv[0]; out[5] = yuv[1]; out[6] = yuv[2]; out[7] = 0.0f;
+  } else {
+    for (int s = 0; s < 4; ++s) out[s] = gz_silver::Update(in[12 + s], yrec[s], in[16 + s]);
+    out[4] = gz_silver::Update(in[20], yuv[1], in[22]);
+    out[5] = gz_silver::Update(in[21], yuv[2], in[23]);
+    out[6] = out[7] = 0.0f;
+  }
+}
+constexpr size_t kSilverStageBytes = sizeof(float) * (kSilverHeader + (size_t)kSilverChunk * (kSilverIn + kSilverOut));
+struct SilverRun {
+  hipStream_t stream;
+  SilverArgs a;
+  float* stage;            // pinned and mapped, kSilverStageBytes
+  float *out_u, *out_v;    // the chroma guesses box-upsampled to w x h (the luma plane is a.guess_y)
+};
+// counters (may be null): cell-passes evaluated (the init pass and the rounds), cell-passes redone on the host
+int silver_run(const SilverRun& r, uint64_t* counters, std::string* err) {
+#define SILVER_HIP(call)                                                             \
+  do {                                                                               \
+    const hipError_t e_ = (call);                                                    \
+    if (e_ != hipSuccess) {                                                          \
+      *err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
+      return e_ == hipErrorOutOfMemory ? GZ_E_NOMEM : GZ_E_HIP;                      \
+    }                                                                                \
+  } while (0)
+#define SILVER_KCHK()                                                                \
+  do {                                                                               \
+    const hipError_t e_ = hipGetLastError();                                         \
+    if (e_ != hipSuccess) {                                                          \
+      *err = std::string("kernel launch: ") + hipGetErrorString(e_);                 \
+      return GZ_E_HIP;                                                               \
+    }                                                                                \
+  } while (0)
+  const SilverArgs& a = r.a;
+  const unsigned cells = (unsigned)a.w2 * (unsigned)a.h2;
+  const dim3 grid(gz_div_up((int)cells, 256)), gather_grid(kSilverChunk / 256);
+  float* in = r.stage + kSilverHeader;
+  float* out = in + (size_t)kSilverChunk * kSilverIn;
+  uint64_t redone = 0;
+  for (int round = -1; round < kSilverRounds; ++round) {
+    const int from = round < 0 ? -1 : (round & 1);
+    SILVER_HIP(hipMemsetAsync(a.list, 0, sizeof(unsigned), r.stream));
+    if (round < 0) {
+      GZ_LAUNCH(k_silver_init, grid, dim3(256), r.stream, a);
+    } else {
+      GZ_LAUNCH(k_silver_iter, grid, dim3(256), r.stream, a, from);
+    }
+    SILVER_KCHK();
+    unsigned n = 0;
+    for (unsigned first = 0; first == 0 || first < n; first += kSilverChunk) {
+      GZ_LAUNCH(k_silver_gather, gather_grid, dim3(256), r.stream, a, from, first, r.stage);
+      SILVER_KCHK();
+      SILVER_HIP(hipStreamSynchronize(r.stream));   // (also: the patch of the chunk before has read `out`)
+      n = reinterpret_cast<const unsigned*>(r.stage)[0];
+      if (n > cells) { *err = "silver screen: more listed cells than cells"; return GZ_E_HIP; }
+      if (n == 0) break;
+      const unsigned m = std::min<unsigned>(kSilverChunk, n - first);
+      for (unsigned t = 0; t < m; ++t) silver_host_cell(round < 0, in + (size_t)t * kSilverIn, out + (size_t)t * kSilverOut);
+      GZ_LAUNCH(k_silver_patch, dim3(gz_div_up((int)m, 256)), dim3(256), r.stream, a, from, first, m, (const float*)out);
+      SILVER_KCHK();
+    }
+    redone += n;
+  }
+  const int last = kSilverRounds & 1;   // the half the last round wrote
+  GZ_LAUNCH(k_silver_upsample, dim3(gz_div_up(a.w, 256), a.h), dim3(256), r.stream, (const float*)a.guess_u[last],
+            (const float*)a.guess_v[last], a.w, a.h, a.w2, r.out_u, r.out_v);
+  SILVER_KCHK();
+  if (counters) {
+    counters[0] = (uint64_t)cells * (kSilverRounds + 1);
+    counters[1] = redone;
+  }
+  return GZ_OK;
+#undef SILVER_HIP
+#undef SILVER_KCHK
+}
+}  // namespace
+
+int gz_downsample_silver(gz_ctx* c, int16_t* coeffs_out, uint64_t counters[2]) {
+  DeviceScope ds_(c);
+  if (!c) return GZ_E_ARG;
+  if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample_silver needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
+  const int w = c->w, h = c->h, w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+  const size_t cells = (size_t)w2 * h2;
+  if (!c->made.silver) {
+    TRY(regrow(c, c->stream, nullptr, 0, {{(void**)&c->d_silver_list, sizeof(unsigned) * (cells + 1)},
+                                          {(void**)&c->d_silver_lut, sizeof(float) * 256},
+                                          {(void**)&c->h_silver, kSilverStageBytes, true}}));
+    HIPCHK(c, hipMemcpyAsync(c->d_silver_lut, silver_lut(), sizeof(float) * 256, hipMemcpyHostToDevice, c->stream));
+    c->made.silver = true;
+  }
+  c->have_orig = false;     // (d_orig is rewritten)
+  c->xyb_is_cand = false;   // (xyb[] takes the three planes; tmp[] and lf_raw[0] are scratch no claim covers)
+  // OutputImage::ToSRGB() of the unquantised image (output_image.cc:310): quantising by all ones is the identity, so the
+  // pixels come from d_orig as they are -- the candidate and its planes are not touched
+  TRY(stage_reconstruct(c, c->stream, c->d_orig, nullptr, c->d_srgb_out));
+  SilverRun r;
+  r.stream = c->stream;
+  r.a.w = w; r.a.h = h; r.a.w2 = w2; r.a.h2 = h2;
+  r.a.rgb = c->d_srgb_out;
+  r.a.lut = c->d_silver_lut;
+  r.a.guess_y = c->xyb[0];
+  r.out_u = c->xyb[1];
+  r.out_v = c->xyb[2];
+  r.a.y_target = c->tmp[0];
+  // (2 * cells <= w * h for every w, h >= 3: two quarter planes per scratch plane)
+  r.a.target_u = c->tmp[1]; r.a.target_v = c->tmp[1] + cells;
+  r.a.guess_u[0] = c->tmp[2]; r.a.guess_v[0] = c->tmp[2] + cells;
+  r.a.guess_u[1] = c->lf_raw[0]; r.a.guess_v[1] = c->lf_raw[0] + cells;
+  r.a.list = c->d_silver_list;
+  r.a.guard = kPowGuard;
+  r.a.list_all = 0;
+  r.stage = c->h_silver;
+  uint64_t cnt[2] = {0, 0};
+  if (const int rc = silver_run(r, cnt, &c->err)) return rc;
+  // output_image.cc:314-316: every component from its plane, as gz_downsample_planes
+  const int cbw = (w + 15) / 16, cbh = (h + 15) / 16, nbc = cbw * cbh;
+  GZ_LAUNCH(k_set_downsampled_coeffs, dim3(gz_div_up(c->nb, kBlocksPerWG)), dim3(256), c->stream,
+            (const float*)c->xyb[0], w, h, 1, 1, c->bw, c->nb, c->d_orig);
+  KCHK(c);
+  for (int i = 1; i < 3; ++i) {
+    int16_t* dst = c->d_orig + ((size_t)c->nb + (size_t)(i - 1) * nbc) * 64;
+    GZ_LAUNCH(k_set_downsampled_coeffs, dim3(gz_div_up(nbc, kBlocksPerWG)), dim3(256), c->stream,
+              (const float*)c->xyb[i], w, h, 2, 2, cbw, nbc, dst);
+    KCHK(c);
+  }
+  set_frame(c, 2);
+  if (coeffs_out)
+    HIPCHK(c, hipMemcpyAsync(coeffs_out, c->d_orig, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (counters) { counters[0] = cnt[0]; counters[1] = cnt[1]; }
   c->have_orig = true;
   return GZ_OK;
 }

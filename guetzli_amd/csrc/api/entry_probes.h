@@ -193,11 +193,12 @@ int gz_probe_math(int device, int op, int n, const void* a, const void* b, const
       {2, 1, 0, 1},    // GZ_MATH_DIFF_FROM_SUPS
       {1, 1, 512, 1},  // GZ_MATH_INTERP_LUT512 (a, out: double)
       {2, 1, 0, 1},    // GZ_MATH_QUANT_DIV (a, b, out: int32)
+      {1, 1, 2, 3},    // GZ_MATH_POW_TO_FLOAT (a, out: double)
   };
   const auto& o = kOps[op];
   if (np != o.np || (o.nin >= 2 && !b) || (o.nin >= 3 && !c)) return GZ_E_ARG;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
-  const size_t es = op == GZ_MATH_INTERP_LUT512 ? 8 : 4;
+  const size_t es = op == GZ_MATH_INTERP_LUT512 || op == GZ_MATH_POW_TO_FLOAT ? 8 : 4;
   const size_t in_bytes = es * (size_t)o.per_in * n, out_bytes = es * (size_t)o.outs * n;
   DevBuf da, db, dc, dp, dout;
   if (!da.alloc(in_bytes) || !db.alloc(in_bytes) || !dc.alloc(in_bytes) || !dp.alloc(sizeof(double) * 512) ||
@@ -213,6 +214,9 @@ int gz_probe_math(int device, int op, int n, const void* a, const void* b, const
   if (op == GZ_MATH_QUANT_DIV) {
     const int* pa = (const int*)da.p; const int* pq = (const int*)db.p; int* po = (int*)dout.p;
     GZ_LAUNCH(k_probe_quant_div, grid, dim3(256), (hipStream_t)0, pa, pq, po, n);
+  } else if (op == GZ_MATH_POW_TO_FLOAT) {
+    const double* pa = (const double*)da.p; double* po = (double*)dout.p;
+    GZ_LAUNCH(k_probe_pow, grid, dim3(256), (hipStream_t)0, pa, n, p[0], p[1], kPowGuard, po);
   } else {
     ProbeMathArgs g;
     memset(&g, 0, sizeof(g));
@@ -262,7 +266,60 @@ int gz_probe_div2_sweep(int device, const float* numerators, int nnum, unsigned 
   return GZ_OK;
 }
 
+// RGBToYUV420 (preprocess_downsample.cc:452-476) of a packed sRGB image by the device path of gz_downsample_silver,
+// without a context: the three w x h planes it returns.
+int gz_probe_silver_yuv420(int device, const uint8_t* srgb, int w, int h, int guard_log2, float* y, float* u, float* v,
+                           uint64_t counters[2]) {
+  if (!srgb || !y || !u || !v || w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16) || (size_t)w * h > ((size_t)1 << 30) ||
+      guard_log2 < -1 || guard_log2 > 64)
+    return GZ_E_ARG;
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  const int w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+  const size_t n = (size_t)w * h, cells = (size_t)w2 * h2;
+  struct HostBuf {   // scoped pinned allocation
+    void* p = nullptr;
+    ~HostBuf() { if (p) (void)hipHostFree(p); }
+  } stage;
+  DevBuf drgb, dlut, dplanes, dquarter, dlist;
+  // four full planes (y_target, guess_y, out_u, out_v), six quarter planes (targets, the guesses' two halves)
+  if (!drgb.alloc(3 * n) || !dlut.alloc(sizeof(float) * 256) || !dplanes.alloc(sizeof(float) * 4 * n) ||
+      !dquarter.alloc(sizeof(float) * 6 * cells) || !dlist.alloc(sizeof(unsigned) * (cells + 1)) ||
+      hipHostMalloc(&stage.p, kSilverStageBytes, kHostAllocFlags) != hipSuccess) {
+    (void)hipGetLastError();
+    return GZ_E_NOMEM;
+  }
+  if (hipMemcpy(drgb.p, srgb, 3 * n, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(dlut.p, silver_lut(), sizeof(float) * 256, hipMemcpyHostToDevice) != hipSuccess)
+    return GZ_E_HIP;
+  float* planes = (float*)dplanes.p;
+  float* quarter = (float*)dquarter.p;
+  SilverRun r;
+  r.stream = (hipStream_t)0;
+  r.a.w = w; r.a.h = h; r.a.w2 = w2; r.a.h2 = h2;
+  r.a.rgb = (const uint8_t*)drgb.p;
+  r.a.lut = (const float*)dlut.p;
+  r.a.y_target = planes; r.a.guess_y = planes + n; r.out_u = planes + 2 * n; r.out_v = planes + 3 * n;
+  r.a.target_u = quarter; r.a.target_v = quarter + cells;
+  r.a.guess_u[0] = quarter + 2 * cells; r.a.guess_v[0] = quarter + 3 * cells;
+  r.a.guess_u[1] = quarter + 4 * cells; r.a.guess_v[1] = quarter + 5 * cells;
+  r.a.list = (unsigned*)dlist.p;
+  r.a.guard = guard_log2 == 64 ? 0.0 : guard_log2 < 0 ? kPowGuard : ldexp(1.0, -guard_log2);
+  r.a.list_all = guard_log2 < 0 ? 1 : 0;
+  r.stage = (float*)stage.p;
+  std::string err;
+  if (const int rc = silver_run(r, counters, &err)) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return GZ_E_HIP;
+  if (hipMemcpy(y, r.a.guess_y, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(u, r.out_u, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(v, r.out_v, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess)
+    return GZ_E_HIP;
+  return GZ_OK;
+}
+
 #ifdef GZ_EMU
+// Emulation build only: the emulated device pow of gz_pow_to_float_guarded off by u double ulps (the device library's
+// pow is accurate to a few ulps, and not libm's: in the emulation it IS libm's, and the guard would have nothing to catch)
+__attribute__((used, visibility("default"))) void gz_emu_set_pow_ulps(int u) { gz::gz_emu_pow_ulps() = u; }
 // Emulation build only (test hook, in the style of gz_emu_fail_launch): the emulated reciprocal of
 // div2_shared off by u = -1, 0, +1 ulp -- v_rcp_f32 is accurate to 1 ulp, not correctly rounded.
 __attribute__((used, visibility("default"))) void gz_emu_set_rcp_ulps(int u) { gz::gz_emu_rcp_ulps() = u; }

@@ -32,6 +32,7 @@
 #include "gz_kernels_entropy.h"
 #include "gz_kernels_dctd.h"
 #include "gz_kernels_downsample.h"
+#include "gz_kernels_silver.h"
 #include "gz_kernels_order.h"
 #include "gz_kernels_rank.h"
 #include "gz_host_weights.h"

@@ -6,7 +6,8 @@
 // operand types, promotions and association.  gfx950 provides correctly rounded
 // f32/f64 + - * / sqrt and conversions, and denormals are preserved (HIP default).
 // All transcendental work (exp for blur taps, pow for the sRGB LUT, the mask LUTs) is
-// done on the host and uploaded.
+// done on the host and uploaded -- but for use_silver_screen's powers, which the device
+// evaluates itself together with a proof that libm's result rounds alike (gz_pow_to_float).
 #pragma once
 #include "gz_common.h"
 
@@ -280,6 +281,55 @@ GZ_DEVFN float malta_diff(float a, float b, const MaltaNorm nm) {
   if (diff < 0) impact = -impact;
   const float r = (float)((double)d + impact);
   return hit ? r : d;
+}
+
+// ---- float(scale * pow(base, expo)) with a proof that libm's pow rounds to the same float ----
+// RGBToYUV420 (use_silver_screen) depends on every float that static_cast<float>(pow(...)) gives,
+// and glibc's pow -- under one ulp, not correctly rounded -- is not the device library's.  The device
+// does not imitate it: it evaluates v = scale * p with its own p and reports whether any double
+// within relative G of v would convert to another float.  With the device's p within E_dev of the
+// true power, libm's within 2^-52 and the product's rounding 2^-53, every double either side can
+// hold lies in v * (1 +- (E_dev + 2^-51)): if that interval holds no float rounding boundary both
+// sides convert to the same float.  G = 2^-40 is 4096 double ulps, 256 times the 16 ulp OpenCL
+// allows a double pow (the test measures the device's); 2.4e-5 of uniform inputs come out ambiguous,
+// and the caller has those evaluated by the host's libm.  pow(0, y) = 0 and pow(1, y) = 1 are exact
+// in every libm and never ambiguous.  The conversions are IEEE (denormal floats included).
+#ifdef GZ_EMU
+// (in the emulation pow IS libm's: the hook moves p by that many double ulps before the guard, so
+// that the guard has something to catch)
+inline int& gz_emu_pow_ulps() {
+  static int v = 0;
+  return v;
+}
+#endif
+constexpr double kPowGuard = 0x1p-40;
+// guard: G (0: no guard, nothing is ambiguous); p_out (may be null): the device's p
+GZ_DEVFN float gz_pow_to_float_guarded(double base, double expo, double scale, double guard, bool* ambiguous,
+                                       double* p_out) {
+  double p;
+  bool exact = true;
+  if (base == 0.0) {
+    p = 0.0;
+  } else if (base == 1.0) {
+    p = 1.0;
+  } else {
+    exact = false;
+    p = pow(base, expo);
+#ifdef GZ_EMU
+    if (gz_emu_pow_ulps() != 0 && p > 0.0 && p * 0.0 == 0.0) {
+      long long bits = __builtin_bit_cast(long long, p);
+      bits += gz_emu_pow_ulps();
+      p = __builtin_bit_cast(double, bits);
+    }
+#endif
+  }
+  if (p_out) *p_out = p;
+  const double v = scale * p;
+  *ambiguous = !exact && (float)(v * (1.0 - guard)) != (float)(v * (1.0 + guard));
+  return (float)v;
+}
+GZ_DEVFN float gz_pow_to_float(double base, double expo, double scale, bool* ambiguous) {
+  return gz_pow_to_float_guarded(base, expo, scale, kPowGuard, ambiguous, nullptr);
 }
 
 // ---- L2Diff / L2DiffAsymmetric / SameNoiseLevels accumulations -------------------

@@ -10,6 +10,7 @@
 #include "png_reader.h"
 #include "processor.h"
 #include "reader_dump.h"
+#include "silver_screen.h"
 
 extern "C" {
 
@@ -144,6 +145,21 @@ long gzh_read_png(const uint8_t* data, long len, int* wh, uint8_t* out, long cap
   wh[1] = h;
   if ((long)rgb.size() <= cap) memcpy(out, rgb.data(), rgb.size());
   return (long)rgb.size();
+  GZH_GUARD_END
+}
+
+// SilverScreenYUV420 (silver_screen.h: RGBToYUV420 on the host, with libm): rgb w*h*3 -> y, u, v of w*h floats each.
+// Test hook: the yardstick of the device path (gz_downsample_silver, gz_probe_silver_yuv420).
+int gzh_silver_screen_yuv420(const uint8_t* rgb, int w, int h, float* y, float* u, float* v) {
+  GZH_GUARD_BEGIN
+  if (!rgb || !y || !u || !v || w <= 0 || h <= 0) return -1;
+  std::vector<float> py, pu, pv;
+  guetzli_amd::SilverScreenYUV420(rgb, w, h, &py, &pu, &pv);
+  const size_t n = (size_t)w * h;
+  memcpy(y, py.data(), n * sizeof(float));
+  memcpy(u, pu.data(), n * sizeof(float));
+  memcpy(v, pv.data(), n * sizeof(float));
+  return 0;
   GZH_GUARD_END
 }
 

@@ -7,7 +7,11 @@
 #include "encoder.h"
 #include "jpeg_reader.h"
 #include "parallel.h"
-#include "silver_screen.h"
+
+// A weak reference: the driver is also linked against stand-ins for the device library that implement the C ABI as
+// it was when they were written (the recorded-session replay of the tests).  Such a library still loads; asking it
+// for use_silver_screen fails below, loudly -- there is no host path behind this call.
+extern "C" int gz_downsample_silver(gz_ctx* ctx, int16_t* coeffs_out, uint64_t counters[2]) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -195,16 +199,15 @@ bool Encoder::Search(const QuantMatrix first_q, const Stopwatch& start, std::str
       if (!grey) {
         Stopwatch dw;
         if (params_.use_silver_screen) {
-          // output_image.cc:309-318: ToSRGB() of the unquantised image -> RGBToYUV420 (host:
-          // silver_screen.cc) -> all three components from the planes it returns
-          std::vector<uint8_t> srgb((size_t)3 * w_ * h_);
-          rc = gz_quantize(ctx_, nullptr, nullptr);
-          if (rc == GZ_OK) rc = gz_reconstruct(ctx_, srgb.data(), nullptr);
-          if (rc != GZ_OK) return Fail("gz_reconstruct", rc);
-          std::vector<float> py, pu, pv;
-          SilverScreenYUV420(srgb.data(), w_, h_, &py, &pu, &pv);
-          rc = gz_downsample_planes(ctx_, py.data(), pu.data(), pv.data(), sc_.orig.data());
-          if (rc != GZ_OK) return Fail("gz_downsample_planes", rc);
+          // output_image.cc:309-318: ToSRGB() of the unquantised image -> RGBToYUV420 -> all three components
+          // from the planes it returns, on the device (bit-identical to silver_screen.cc's host form: the cells
+          // whose power the device cannot prove to round like libm's are redone by the library's host code)
+          uint64_t cell_passes[2] = {0, 0};
+          if (!gz_downsample_silver) return Fail("gz_downsample_silver (not in this device library)", GZ_E_STATE);
+          rc = gz_downsample_silver(ctx_, sc_.orig.data(), cell_passes);
+          if (rc != GZ_OK) return Fail("gz_downsample_silver", rc);
+          stats_->counters["silver screen cell rounds"] = (int)std::min<uint64_t>(cell_passes[0], 0x7fffffff);
+          stats_->counters["silver screen cell rounds on host"] = (int)std::min<uint64_t>(cell_passes[1], 0x7fffffff);
         } else {
           rc = gz_downsample(ctx_, sc_.orig.data());
           if (rc != GZ_OK) return Fail("gz_downsample", rc);

@@ -4,19 +4,21 @@
 
 #include <algorithm>
 
+#include "../csrc/gz_silver_ref.h"
 #include "parallel.h"
 
 namespace guetzli_amd {
 
 namespace {
 
-// preprocess_downsample.cc:283-319 -- every expression with the reference's operand types
-inline float Clip(float v) { return std::max(0.0f, std::min(255.0f, v)); }
-inline float ToY(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b; }
-inline float ToU(float r, float g, float b) { return -0.16874f * r - 0.33126f * g + 0.5f * b + 128.0f; }
-inline float ToV(float r, float g, float b) { return 0.5f * r - 0.41869f * g - 0.08131f * b + 128.0f; }
-inline float GammaToLinear(float x) { return static_cast<float>(pow(x / 255.0f, 2.2)); }
-inline float LinearToGamma(float x) { return static_cast<float>(255.0 * pow(x, 1.0 / 2.2)); }
+// preprocess_downsample.cc:283-319: the per-sample functions live in csrc/gz_silver_ref.h, one copy for this file, the
+// device kernels and the device library's host path
+using gz_silver::Clip;
+using gz_silver::GammaToLinear;
+using gz_silver::LinearToGamma;
+using gz_silver::ToU;
+using gz_silver::ToV;
+using gz_silver::ToY;
 
 // Rows [0, n) in chunks on the worker pool (every stage below is independent per output row).
 template <class F>

@@ -1,10 +1,10 @@
 // Params::use_silver_screen: RGBToYUV420 of the reference (guetzli/preprocess_downsample.cc:
 // 283-476) -- the YUV 4:2:0 samples whose decoded image has the luma of the original when
 // averaged in LINEAR light, found by 20 fixed-point iterations through the decoder model.
-// Host code on purpose: the iteration is made of std::pow calls on arbitrary float arguments,
-// and bit-identical results need the same libm as the reference uses (glibc's pow); it runs
-// once per image, row-parallel on the worker pool.  Its three output planes go to the device
-// (gz_set_orig_from_planes_420), where SetDownsampledCoefficients makes coefficients of them.
+// The whole conversion on the host, with the same libm as the reference uses (glibc's pow), row-parallel on the
+// worker pool.  The encoder runs the conversion on the device (gz_downsample_silver, csrc/gz_kernels_silver.h), which
+// gives the same floats; this form is the yardstick of the tests (gzh_silver_screen_yuv420) and what a caller of
+// gz_downsample_planes may feed it.  The per-sample functions are shared with the device path: csrc/gz_silver_ref.h.
 #pragma once
 #include <stdint.h>
 

@@ -154,14 +154,26 @@ int gz_set_orig_coeffs_420(gz_ctx* ctx, const int16_t* coeffs);
  * receives the new original, nb + 2*nbc blocks.  The caller skips the call for a greyscale
  * image, as the reference does (:305-308). */
 int gz_downsample(gz_ctx* ctx, int16_t* coeffs_out);
-/* The use_silver_screen branch of OutputImage::Downsample (output_image.cc:309-318): y, u, v
- * are the three w x h planes RGBToYUV420 returned (preprocess_downsample.cc:452-476; host
- * work: it is twenty rounds of libm pow(), guetzli_amd/host/silver_screen.cc restates it on
- * OutputImage::ToSRGB() = gz_quantize(NULL) + gz_reconstruct of the 4:4:4 original).  All three
+/* The use_silver_screen branch of OutputImage::Downsample (output_image.cc:309-318) for a caller that
+ * has RGBToYUV420's planes already: y, u, v are the three w x h planes it returned
+ * (preprocess_downsample.cc:452-476) for OutputImage::ToSRGB() = gz_quantize(NULL) + gz_reconstruct of
+ * the 4:4:4 original -- from the reference's own function, or from guetzli_amd/host/silver_screen.cc,
+ * the host restatement (twenty rounds of libm pow()) the tests keep as their yardstick.  The encoder
+ * itself calls gz_downsample_silver below, which computes the planes on the device.  All three
  * components become SetDownsampledCoefficients of their plane -- luma by 1 x 1, chroma by
  * 2 x 2 -- and the context's frame 4:2:0, as after gz_downsample. */
 int gz_downsample_planes(gz_ctx* ctx, const float* y, const float* u, const float* v,
                          int16_t* coeffs_out);
+/* The whole use_silver_screen branch on the device: the candidate's pixels are those of the unquantised original
+ * (ToSRGB of CopyFromJpegData's image), RGBToYUV420 runs as kernels (csrc/gz_kernels_silver.h: an init pass and twenty
+ * rounds, one thread per 2 x 2 cell), and the three components become SetDownsampledCoefficients of its planes, as
+ * above.  Bit-identical to the host form: every float(pow()) of the reference is evaluated by the device's pow
+ * together with a proof that glibc's pow rounds to the same float (gz_pow_to_float, csrc/gz_math.h); the cells that
+ * hold an evaluation without that proof -- about 5 in 10^4 per pass -- are redone by this library's host code with
+ * libm and patched in before the next pass.  Preconditions, frame and error behaviour as gz_downsample_planes: a
+ * failed call leaves the 4:4:4 frame without an original.  counters (may be NULL): [0] = cell-passes evaluated
+ * (cells x 21), [1] = cell-passes redone on the host. */
+int gz_downsample_silver(gz_ctx* ctx, int16_t* coeffs_out, uint64_t counters[2]);
 /* Current frame: chroma subsampling factor (1 or 2), luma blocks, blocks per chroma
  * component.  Any pointer may be NULL. */
 int gz_frame_layout(gz_ctx* ctx, int* chroma_factor, int* luma_blocks, int* chroma_blocks);
@@ -530,16 +542,26 @@ int gz_probe_arith(int device, int op, const void* a, const void* b, const void*
  *   GZ_MATH_SAME_NOISE_PRE     a, b                            -                             1
  *   GZ_MATH_DIFF_FROM_SUPS     a = sup0, b = sup1              -                             1
  *   GZ_MATH_INTERP_LUT512      a = ix (n DOUBLES)              the table, 512 doubles        1 (double)
- *   GZ_MATH_QUANT_DIV          a, b = q >= 1 (n int32 each)    -                             1 (int32)  */
+ *   GZ_MATH_QUANT_DIV          a, b = q >= 1 (n int32 each)    -                             1 (int32)
+ *   GZ_MATH_POW_TO_FLOAT       a = base (n DOUBLES)            expo, scale                   3 (double): the device's
+ *                              pow(base, expo); gz_pow_to_float's float(scale * pow) as a double; 1.0 where that float
+ *                              is not proven to be libm's (G = 2^-40)  */
 enum {
   GZ_MATH_DIV2_SHARED = 0, GZ_MATH_MALTA_DIFF, GZ_MATH_MALTA_DIFF_PLAIN, GZ_MATH_GAMMA_POLY,
   GZ_MATH_OPSIN_PIXEL, GZ_MATH_MAXIMUM_CLAMP, GZ_MATH_REMOVE_RANGE, GZ_MATH_AMPLIFY_RANGE,
   GZ_MATH_SUPPRESS_X_BY_Y, GZ_MATH_SUPPRESS_BRIGHT, GZ_MATH_LF_TO_VALS, GZ_MATH_L2DIFF,
   GZ_MATH_L2DIFF_ASYM, GZ_MATH_SAME_NOISE_PRE, GZ_MATH_DIFF_FROM_SUPS, GZ_MATH_INTERP_LUT512,
-  GZ_MATH_QUANT_DIV, GZ_MATH_OP_COUNT
+  GZ_MATH_QUANT_DIV, GZ_MATH_POW_TO_FLOAT, GZ_MATH_OP_COUNT
 };
 int gz_probe_math(int device, int op, int n, const void* a, const void* b, const void* c,
                   const double* p, int np, void* out);
+/* RGBToYUV420 (preprocess_downsample.cc:452-476) of a packed sRGB image through the kernels and the host path of
+ * gz_downsample_silver, without a context: y, u, v receive its three w x h planes (u, v box-upsampled).  guard_log2:
+ * the guard of gz_pow_to_float is 2^-guard_log2 -- 40 in production; -1: every cell takes the host path (gather,
+ * libm, patch); 64: no guard, nothing takes it (the planes then differ from the reference's wherever the device's pow
+ * rounds to another float than libm's).  counters (may be NULL) as gz_downsample_silver's. */
+int gz_probe_silver_yuv420(int device, const uint8_t* srgb, int w, int h, int guard_log2, float* y, float* u, float* v,
+                           uint64_t counters[2]);
 /* div2_shared against the device's own IEEE division, on the device: for the nnum numerators (an
  * even number, at most 12: each pair shares its reciprocal) and every stride-th float denominator
  * of [2^-40, 2^40) -- 80 * 2^23 of them, stride 1: all -- the number of quotients that differ.
