@@ -114,6 +114,7 @@ SIGNATURES = {
     "gz_probe_arith": (_I, [_I, _I, _P, _P, _P, _P, _I]),
     "gz_probe_math": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "gz_probe_div2_sweep": (_I, [_I, _P, _I, C.c_uint, C.c_uint, _P, _P, C.c_size_t]),
+    "gz_probe_scan_offsets": (_I, [_I, _P, _I, _P, _I, C.c_uint, _P]),
     "gz_dct_double_blocks": (_I, [_I, _P, _I, _I]),
     "gz_component_to_float_pixels": (_I, [_I, _P, _I, _I, _P]),
     "gz_component_set_downsampled": (_I, [_I, _P, _I, _I, _I, _I, _P]),
@@ -253,6 +254,17 @@ class Library:
         self.check(self.lib.gz_probe_silver_yuv420(device, _ptr(rgb), w, h, int(guard_log2), _ptr(y), _ptr(u), _ptr(v),
                                                    _ptr(cnt)))
         return y, u, v, (int(cnt[0]), int(cnt[1]))
+
+    def probe_scan_offsets(self, values, lengths, start_epoch=0, device=0):
+        """gz_probe_scan_offsets: k_scan_offsets once per entry of `lengths` on a prefix of `values`, back to back on
+        one scratch -> a list of uint64 arrays off[0 .. lengths[i]]."""
+        v = np.ascontiguousarray(values, np.uint32)
+        ln = np.ascontiguousarray(lengths, np.int32)
+        out = np.zeros(int(ln.astype(np.int64).sum()) + ln.size, np.uint64)
+        self.check(self.lib.gz_probe_scan_offsets(device, _ptr(v), v.size, _ptr(ln), ln.size, int(start_epoch),
+                                                  _ptr(out)))
+        ends = np.cumsum(ln.astype(np.int64) + 1)
+        return [out[e - n - 1:e] for e, n in zip(ends, ln)]
 
     def div2_sweep(self, numerators, stride=1, sample_every=1 << 20, device=0):
         """gz_probe_div2_sweep: (mismatches, sampled quotients [samples][len(numerators)])."""

@@ -435,29 +435,43 @@ int stage_diffmap(gz_ctx* c, const ChainStreams& cs, const Psycho& p0, const Psy
   return GZ_OK;
 }
 
+// k_scan_offsets' scratch for max_tiles tiles, as one allocation (zero before its first launch: ticket 0, no epoch yet).
+inline size_t scan_state_bytes(int max_tiles) { return (size_t)max_tiles * (8 + 8 + 4) + 64; }
+inline ScanState scan_state_at(void* d_state, int max_tiles) {
+  ScanState st;
+  st.agg = (unsigned long long*)d_state;
+  st.incl = st.agg + max_tiles;
+  st.status = (unsigned*)(st.incl + max_tiles);
+  st.ticket = st.status + max_tiles;
+  return st;
+}
+// The epoch of the scratch's next launch on `stream`, *epoch being the one of its last launch (0: none yet).  The
+// flags keep 30 bits of it: where it would wrap, the scratch is cleared behind the launches before and the count starts
+// over at 1.
+inline hipError_t scan_next_epoch(unsigned* epoch, void* d_state, size_t bytes, hipStream_t stream) {
+  if (++*epoch >= 0x3fffffffu) {
+    const hipError_t e = hipMemsetAsync(d_state, 0, bytes, stream);
+    if (e != hipSuccess) return e;
+    *epoch = 1;
+  }
+  return hipSuccess;
+}
+
 // Exclusive 64-bit prefix sums of n 32-bit values on `stream` (which: 0 = the main stream's
 // scratch, 1 = the entropy stream's).
 int enqueue_scan_offsets(gz_ctx* c, int which, hipStream_t stream, const unsigned* d_bits, int n,
                          unsigned long long* d_off) {
   const int max_tiles = gz_div_up(c->nb, kScanTile) + 1;
-  const size_t bytes = (size_t)max_tiles * (8 + 8 + 4) + 64;
+  const size_t bytes = scan_state_bytes(max_tiles);
   if (!c->made.scan_state[which]) {
     TRY(regrow(c, stream, nullptr, 0, {{&c->d_scan_state[which], bytes}}));
     HIPCHK(c, hipMemsetAsync(c->d_scan_state[which], 0, bytes, stream));   // ticket 0, no epoch yet
     c->scan_epoch[which] = 0;
     c->made.scan_state[which] = true;
   }
-  char* base = (char*)c->d_scan_state[which];
-  ScanState st;
-  st.agg = (unsigned long long*)base;
-  st.incl = st.agg + max_tiles;
-  st.status = (unsigned*)(st.incl + max_tiles);
-  st.ticket = st.status + max_tiles;
-  unsigned ep = ++c->scan_epoch[which];
-  if (ep >= 0x3fffffffu) {   // the epoch field of the flags would wrap: start over
-    HIPCHK(c, hipMemsetAsync(c->d_scan_state[which], 0, bytes, stream));
-    c->scan_epoch[which] = ep = 1;
-  }
+  const ScanState st = scan_state_at(c->d_scan_state[which], max_tiles);
+  HIPCHK(c, scan_next_epoch(&c->scan_epoch[which], c->d_scan_state[which], bytes, stream));
+  const unsigned ep = c->scan_epoch[which];
   if (n > max_tiles * kScanTile) { c->err = "scan larger than its scratch"; return GZ_E_STATE; }
   GZ_LAUNCH(k_scan_offsets, dim3(std::max(1, gz_div_up(n, kScanTile))), dim3(256), stream, d_bits, n, d_off, st, ep);
   KCHK(c);

@@ -316,6 +316,48 @@ int gz_probe_silver_yuv420(int device, const uint8_t* srgb, int w, int h, int gu
   return GZ_OK;
 }
 
+// k_scan_offsets alone, without a context: one scratch sized for the largest of `lengths`, one launch per entry on the
+// first lengths[i] of `values`, back to back on one stream, the epochs following start_epoch by the rule
+// enqueue_scan_offsets follows (scan_next_epoch) -- nothing else clears the scratch between the launches.
+// out: every launch's off[0 .. lengths[i]], one after the other.
+int gz_probe_scan_offsets(int device, const uint32_t* values, int n_values, const int32_t* lengths, int n_lengths,
+                          uint32_t start_epoch, uint64_t* out) {
+  if (!values || !lengths || !out || n_values <= 0 || n_lengths <= 0 || n_lengths > 4096 || start_epoch >= 0x3fffffffu)
+    return GZ_E_ARG;
+  int max_len = 0;
+  size_t total = 0;
+  for (int i = 0; i < n_lengths; ++i) {
+    if (lengths[i] <= 0 || lengths[i] > n_values) return GZ_E_ARG;
+    max_len = std::max(max_len, (int)lengths[i]);
+    total += (size_t)lengths[i] + 1;
+  }
+  if (total > ((size_t)1 << 28)) return GZ_E_ARG;
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  const int max_tiles = gz_div_up(max_len, kScanTile) + 1;
+  const size_t bytes = scan_state_bytes(max_tiles);
+  DevBuf dv, dstate, doff;
+  if (!dv.alloc(sizeof(uint32_t) * n_values) || !dstate.alloc(bytes) || !doff.alloc(sizeof(unsigned long long) * total))
+    return GZ_E_NOMEM;
+  const hipStream_t stream = (hipStream_t)0;
+  if (hipMemcpy(dv.p, values, sizeof(uint32_t) * n_values, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemsetAsync(dstate.p, 0, bytes, stream) != hipSuccess)
+    return GZ_E_HIP;
+  const ScanState st = scan_state_at(dstate.p, max_tiles);
+  const unsigned* bits = (const unsigned*)dv.p;
+  unsigned long long* off = (unsigned long long*)doff.p;
+  unsigned epoch = start_epoch;
+  for (int i = 0; i < n_lengths; ++i) {
+    if (scan_next_epoch(&epoch, dstate.p, bytes, stream) != hipSuccess) return GZ_E_HIP;
+    const int n = lengths[i];
+    GZ_LAUNCH(k_scan_offsets, dim3(gz_div_up(n, kScanTile)), dim3(256), stream, bits, n, off, st, epoch);
+    if (hipGetLastError() != hipSuccess) return GZ_E_HIP;
+    off += (size_t)n + 1;
+  }
+  if (hipStreamSynchronize(stream) != hipSuccess) return GZ_E_HIP;
+  if (hipMemcpy(out, doff.p, sizeof(unsigned long long) * total, hipMemcpyDeviceToHost) != hipSuccess) return GZ_E_HIP;
+  return GZ_OK;
+}
+
 #ifdef GZ_EMU
 // Emulation build only: the emulated device pow of gz_pow_to_float_guarded off by u double ulps (the device library's
 // pow is accurate to a few ulps, and not libm's: in the emulation it IS libm's, and the guard would have nothing to catch)

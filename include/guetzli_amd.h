@@ -562,6 +562,14 @@ int gz_probe_math(int device, int op, int n, const void* a, const void* b, const
  * rounds to another float than libm's).  counters (may be NULL) as gz_downsample_silver's. */
 int gz_probe_silver_yuv420(int device, const uint8_t* srgb, int w, int h, int guard_log2, float* y, float* u, float* v,
                            uint64_t counters[2]);
+/* The exclusive prefix sums of the entropy coder and of phase B's order (k_scan_offsets, decoupled look-back over tiles
+ * of 2048 values) without a context: one launch per entry of `lengths` (1 <= lengths[i] <= n_values, n_lengths <= 4096)
+ * on the first lengths[i] of `values`, back to back on ONE scratch sized for the largest, its epochs continuing from
+ * start_epoch (< 0x3fffffff) as a context's do -- 0x3ffffffd: the second launch wraps the flags' epoch field, the scratch
+ * is cleared and the count starts over at 1.  out receives every launch's off[0 .. lengths[i]] (lengths[i] + 1 sums,
+ * 64-bit), one launch after the other. */
+int gz_probe_scan_offsets(int device, const uint32_t* values, int n_values, const int32_t* lengths, int n_lengths,
+                          uint32_t start_epoch, uint64_t* out);
 /* div2_shared against the device's own IEEE division, on the device: for the nnum numerators (an
  * even number, at most 12: each pair shares its reciprocal) and every stride-th float denominator
  * of [2^-40, 2^40) -- 80 * 2^23 of them, stride 1: all -- the number of quotients that differ.

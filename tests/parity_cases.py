@@ -375,10 +375,9 @@ def expected_jpeg_histograms(cq, q):
     return counts.astype(np.uint32)
 
 
-def case_jpeg_entropy(L, host, w, h, x0=0, y0=0, check_histograms=True):
-    """Device symbol statistics + device scan (gz_jpeg_histograms / gz_jpeg_scan) with the
-    host-built marker segments must reproduce the reference's WriteJpeg byte for byte."""
-    from checkers import ref
+def jpeg_entropy_inputs(w, h, x0=0, y0=0):
+    """The inputs of case_jpeg_entropy: (rgb, original coefficients, [(dequantised coefficients, q or None, is_grey)],
+    the wild case's array)."""
     rng = np.random.default_rng(RNG_SEED + 31 * w + h)
     rgb = images.crop(w, h, x0, y0) if max(w, h) <= 444 else images.tiled(w, h)
     co = oracle.encode_rgb(rgb)
@@ -400,6 +399,14 @@ def case_jpeg_entropy(L, host, w, h, x0=0, y0=0, check_histograms=True):
     grey = cases[1][0].copy()
     grey[1:] = 0
     cases.append((grey, qs[1], True))
+    return rgb, co, cases, wild
+
+
+def case_jpeg_entropy(L, host, w, h, x0=0, y0=0, check_histograms=True):
+    """Device symbol statistics + device scan (gz_jpeg_histograms / gz_jpeg_scan) with the
+    host-built marker segments must reproduce the reference's WriteJpeg byte for byte."""
+    from checkers import ref
+    rgb, co, cases, wild = jpeg_entropy_inputs(w, h, x0, y0)
     with L.context(rgb, 1.0) as ctx:
         for cq, q, is_grey in cases:
             qq = np.ones((3, 64), np.int32) if q is None else q
@@ -518,19 +525,24 @@ def case_block_search_masks444(L, w, h, chk, x0=0, y0=0, qs=3, lookahead=3, new_
     oc.close()
 
 
+def jpeg_entropy420_quants(w, h):
+    """The quantisers of case_jpeg_entropy420."""
+    rng = np.random.default_rng(RNG_SEED + 5 * w + h)
+    return [np.full((3, 64), 2, np.int32),
+            np.stack([rng.integers(1, 9, 64), rng.integers(1, 30, 64), rng.integers(1, 30, 64)]).astype(np.int32),
+            np.stack([np.full(64, 3), np.full(64, 4000), np.full(64, 4000)]).astype(np.int32)]   # chroma -> all zero
+
+
 def case_jpeg_entropy420(L, H, w, h, chk, x0=0, y0=0):
     """The device entropy coder on a 4:2:0 frame (MCUs of 2x2 luma + Cb + Cr blocks, padding
     blocks, DC prediction in scan order) + the host head == the reference's WriteJpeg."""
-    rng = np.random.default_rng(RNG_SEED + 5 * w + h)
     rgb = images.crop(w, h, x0, y0)
     co = chk.encode_rgb(rgb)
     orig = chk.downsample(co, w, h)
     with L.context(rgb, 1.0) as ctx:
         ctx.encode_rgb()
         ctx.downsample(download=False)
-        qs = [np.full((3, 64), 2, np.int32),
-              np.stack([rng.integers(1, 9, 64), rng.integers(1, 30, 64), rng.integers(1, 30, 64)]).astype(np.int32),
-              np.stack([np.full(64, 3), np.full(64, 4000), np.full(64, 4000)]).astype(np.int32)]   # chroma -> all zero
+        qs = jpeg_entropy420_quants(w, h)
         for q in qs:
             cq = ctx.quantize(q)
             exp = chk.write_jpeg420(orig, w, h, q)
@@ -993,3 +1005,150 @@ def case_probe_math_binding(L):
     den = den.astype(np.uint32).view(np.float32)
     assert sample.shape == (-(-(80 << 23) // stride), 2)
     assert_bits_equal(sample, num[None, :] / den[:, None], "div2_shared sweep samples")
+
+
+# ------------------------------------------- the scan coder on tests/entropy_domain.py --
+class ContextCache:
+    """One context per image size, kept for the cases that follow (their frames and scans reuse its buffers and its
+    prefix-scan scratch, as an encode's candidates do); close() at the end of the module."""
+
+    def __init__(self, L):
+        self.L, self.ctx = L, {}
+
+    def get(self, w, h):
+        if (w, h) not in self.ctx:
+            self.ctx[(w, h)] = self.L.context(np.zeros((h, w, 3), np.uint8), 1.0)
+        return self.ctx[(w, h)]
+
+    def close(self):
+        for c in self.ctx.values():
+            c.close()
+        self.ctx = {}
+
+
+def entropy_tables(host, case, kind, counts):
+    """(head or None, depth, code) of `kind`; the optimal ones from `counts`, the statistics of the library under test,
+    as the product builds them."""
+    import entropy_domain as ed
+    g = case.geom
+    if kind == "optimal":
+        return host.jpeg_head(counts, g.w, g.h, case.q, g.ncomp, g.factor)
+    depth, code = ed.tables(kind, case.symbols.hist)
+    return None, depth, code
+
+
+def check_entropy_case(ctx, host, case, kind):
+    """gz_jpeg_histograms (both kernels) and gz_jpeg_scan (one call, and begin / end) on one case of
+    tests/entropy_domain.py under one kind of code table against the reference coder; returns its result."""
+    import os
+    import entropy_domain as ed
+    g, s = case.geom, case.symbols
+    what = f"{case.name} {kind} {g.layout} {g.w}x{g.h}"
+    ctx.set_frame(g.factor)
+    ctx.set_coeffs(case.coeffs)
+    assert "GZ_HIST_GENERIC" not in os.environ
+    counts = ctx.jpeg_histograms(case.q, g.ncomp)
+    assert_bits_equal(counts, s.hist, f"statistics, templated kernel: {what}")
+    os.environ["GZ_HIST_GENERIC"] = "1"
+    try:
+        generic = ctx.jpeg_histograms(case.q, g.ncomp)
+    finally:
+        del os.environ["GZ_HIST_GENERIC"]
+    assert_bits_equal(generic, s.hist, f"statistics, run-time-geometry kernel: {what}")
+    head, depth, code = entropy_tables(host, case, kind, counts)
+    exp = ed.encode(s, depth, code)
+    cap = len(exp.stuffed) + 64
+    n = ctx.jpeg_scan(g.ncomp, depth, code)
+    scan = ctx.jpeg_scan_bytes(cap=cap)
+    assert ctx.jpeg_scan_bits() == (exp.total_bits, exp.stuffed_count), what
+    assert n == (exp.total_bits + 7) // 8 + exp.stuffed_count == len(scan), what
+    if scan != exp.stuffed:
+        got = np.frombuffer(scan, np.uint8)
+        want = np.frombuffer(exp.stuffed, np.uint8)
+        m = min(got.size, want.size)
+        at = int(np.argmax(got[:m] != want[:m])) if (got[:m] != want[:m]).any() else m
+        raise AssertionError(f"scan bytes differ from byte {at} of {want.size}: {what}")
+    ctx.jpeg_scan_begin(g.ncomp, depth, code)
+    assert ctx.jpeg_scan_end() == n, what
+    assert ctx.jpeg_scan_bytes(cap=cap) == scan, f"begin / end: {what}"
+    assert ctx.jpeg_scan_bits() == (exp.total_bits, exp.stuffed_count), what
+    if head is not None:
+        assert head + scan + b"\xff\xd9" == host.write_jpeg(case.coeffs, g.w, g.h, case.q, factor=g.factor), what
+    return exp
+
+
+def case_entropy_domain(contexts, host, family, kind, shapes):
+    import entropy_domain as ed
+    for layout, w, h in shapes:
+        check_entropy_case(contexts.get(w, h), host, ed.case(family, layout, w, h), kind)
+
+
+ENTROPY_KEEP_ORDER = (("dense", "444", "flat16"), ("phase/tiny", "420", "optimal"), ("quant/one", "444", "skewed"),
+                      ("sparse", "gray", "optimal"), ("dense", "420", "flat16"))
+
+
+def case_entropy_keep_across_scans(L, host, w=448, h=296):
+    """On ONE context: the longest scan (kept with gz_jpeg_scan_keep), right behind it a much shorter one (a quarter
+    of the MCUs: one tile of the prefix scan where there were two, a few hundred bytes where there were hundreds of
+    thousands), then long ones again, the unstaged 4:2:0 one among them.  Every scan is checked, and the kept bytes
+    are intact after each."""
+    import entropy_domain as ed
+    with L.context(np.zeros((h, w, 3), np.uint8), 1.0) as ctx:
+        kept = None
+        sizes = []
+        for family, layout, kind in ENTROPY_KEEP_ORDER:
+            exp = check_entropy_case(ctx, host, ed.case(family, layout, w, h), kind)
+            sizes.append(len(exp.stuffed))
+            if kept is None:
+                ctx.jpeg_scan_keep()
+                kept = exp.stuffed
+            assert ctx.jpeg_scan_bytes(kept=True, cap=len(kept) + 64) == kept, f"kept scan after {family} {layout} {kind}"
+        assert sizes[0] == max(sizes) and sizes[1] * 100 < sizes[0] and sizes[2] * 4 > sizes[0], sizes
+
+
+SCAN_PROBE_LENGTHS = (1, 7, 2047, 2048, 2049, 8 * 2048 + 3, 64 * 2048, 64 * 2048 + 1, 65 * 2048 + 1, 130 * 2048 + 77)
+
+
+def scan_probe_values(name, n):
+    rng = np.random.default_rng(RNG_SEED + 77)
+    if name == "random":
+        return rng.integers(0, 20001, n).astype(np.uint32)
+    if name == "zero":
+        return np.zeros(n, np.uint32)
+    assert name == "2^20-1"     # the total passes 2^32 (from 4097 values on), a tile's sum (2048 of them) stays below 2^31
+    return np.full(n, (1 << 20) - 1, np.uint32)
+
+
+def check_scan_probe(L, values, lengths, start_epoch=0):
+    got = L.probe_scan_offsets(values, lengths, start_epoch)
+    exp = np.concatenate([[0], np.cumsum(values.astype(np.uint64), dtype=np.uint64)])
+    assert len(got) == len(lengths)
+    for i, (g, n) in enumerate(zip(got, lengths)):
+        assert g.size == n + 1
+        if not np.array_equal(g, exp[:n + 1]):
+            at = int(np.argmax(g != exp[:n + 1]))
+            raise AssertionError(f"launch {i} (n = {n}, epoch after {start_epoch:#x}): off[{at}] = {int(g[at])}, "
+                                 f"expected {int(exp[at])}")
+
+
+def case_scan_probe(L, repeats=20, lengths=SCAN_PROBE_LENGTHS):
+    """k_scan_offsets alone (gz_probe_scan_offsets) against numpy.cumsum in uint64: every length of the list in
+    ascending order, then long -> short -> long on the same scratch (stale flags of tiles the shorter scan does not
+    have), then across the wrap of the flags' epoch field, then the long lengths `repeats` times.
+
+    Which predecessors already hold an inclusive prefix when a tile looks back depends on timing on the GPU, and the
+    emulation (workgroups one after the other, in ticket order) always finds it in the nearest one: the test cannot
+    choose the arm, it can only give the others the opportunity -- more than 64 and more than 128 tiles, many launches."""
+    lengths = list(lengths)
+    nmax = max(lengths)
+    for name in ("random", "zero", "2^20-1"):
+        v = scan_probe_values(name, nmax)
+        check_scan_probe(L, v, lengths)
+        check_scan_probe(L, v, [lengths[-1], lengths[0], lengths[-1], lengths[4], lengths[-2], lengths[1], lengths[-1]])
+        # 0x3ffffffe, then the wrap: cleared, 1, 2, 3 -- long and short across it
+        check_scan_probe(L, v, [lengths[-1], lengths[-2], lengths[-1], lengths[2], lengths[-1]], start_epoch=0x3ffffffd)
+    v = scan_probe_values("random", nmax)
+    long_ones = [n for n in lengths if n > 64 * 2048]
+    check_scan_probe(L, v, long_ones * repeats)
+    v = scan_probe_values("2^20-1", nmax)
+    check_scan_probe(L, v, long_ones * repeats)
