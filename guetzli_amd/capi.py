@@ -115,6 +115,9 @@ SIGNATURES = {
     "gz_probe_math": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "gz_probe_div2_sweep": (_I, [_I, _P, _I, C.c_uint, C.c_uint, _P, _P, C.c_size_t]),
     "gz_probe_scan_offsets": (_I, [_I, _P, _I, _P, _I, C.c_uint, _P]),
+    "gz_probe_set_block_max": (_I, [_P, _P]),
+    "gz_probe_set_search": (_I, [_P, _I, _P, _P, _P]),
+    "gz_probe_order_state": (_I, [_P, _P, _P]),
     "gz_dct_double_blocks": (_I, [_I, _P, _I, _I]),
     "gz_component_to_float_pixels": (_I, [_I, _P, _I, _I, _P]),
     "gz_component_set_downsampled": (_I, [_I, _P, _I, _I, _I, _I, _P]),
@@ -734,6 +737,31 @@ class Context:
         mdc = np.zeros((3, self.h, self.w), np.float32)
         self._chk(self.L.lib.gz_probe_mask(self.handle, _ptr(a), _ptr(b), _ptr(m), _ptr(mdc)))
         return m, mdc
+
+    # ---- phase B on chosen state (tests/order_domain.py) ----
+    def probe_set_block_max(self, block_max):
+        bm = np.ascontiguousarray(block_max, np.float32)
+        assert bm.size == self.nb
+        self._chk(self.L.lib.gz_probe_set_block_max(self.handle, _ptr(bm)))
+
+    def probe_set_search(self, offsets, idx, err, comp_mask=7):
+        """Candidates (CSR, as block_zeroing_orders returns them) in the place of a block search's."""
+        off = np.ascontiguousarray(offsets, np.int32)
+        ix = np.ascontiguousarray(idx, np.uint8)
+        er = np.ascontiguousarray(err, np.float32)
+        gn = self.nbc if (self.cfac == 2 and comp_mask == 6) else self.nb
+        assert off.size == gn + 1 and ix.size == er.size == int(off[-1])
+        ix = ix if ix.size else np.zeros(1, np.uint8)
+        er = er if er.size else np.zeros(1, np.float32)
+        self._chk(self.L.lib.gz_probe_set_search(self.handle, comp_mask, _ptr(off), _ptr(ix), _ptr(er)))
+        self.search_blocks = gn
+
+    def probe_order_state(self):
+        """(block weights, max_block_error) of the device, a pending order_advance made first."""
+        gn = getattr(self, "search_blocks", self.nb)
+        wgt, me = np.zeros(gn, np.float32), np.zeros(gn, np.float32)
+        self._chk(self.L.lib.gz_probe_order_state(self.handle, _ptr(wgt), _ptr(me)))
+        return wgt, me
 
 
 _default = None

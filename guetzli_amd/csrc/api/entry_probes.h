@@ -358,6 +358,58 @@ int gz_probe_scan_offsets(int device, const uint32_t* values, int n_values, cons
   return GZ_OK;
 }
 
+// ---- phase B on state the tests choose (tests/order_domain.py): the hooks put block maxima and candidates where a
+// gz_compare and a block search leave them, and read the device's weights and max_block_error back; they launch no
+// kernel of their own, everything under test runs through the production entry points.
+int gz_probe_set_block_max(gz_ctx* c, const float* block_max) {
+  DeviceScope ds_(c);
+  if (!c || !block_max) return GZ_E_ARG;
+  c->have_distmap = c->h_block_max_valid = false;
+  HIPCHK(c, hipMemcpyAsync(c->d_block_max, block_max, sizeof(float) * c->nb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_distmap = true;
+  return GZ_OK;
+}
+
+int gz_probe_set_search(gz_ctx* c, int comp_mask, const int32_t* offsets, const uint8_t* idx, const float* err) {
+  DeviceScope ds_(c);
+  if (!c || !offsets || !idx || !err || comp_mask < 1 || comp_mask > 7) return GZ_E_ARG;
+  int mode = 0;
+  TRY(search_mode_of(c, comp_mask, &mode));
+  const int gn = mode == 2 ? c->nbc : c->nb;
+  if (offsets[0] != 0) return GZ_E_ARG;
+  for (int b = 0; b < gn; ++b)
+    if (offsets[b + 1] < offsets[b] || offsets[b + 1] - offsets[b] > 192) return GZ_E_ARG;
+  TRY(search_grid_begin(c, comp_mask, mode));
+  // k_block_search's layout: a count per block, its indices and errors at a stride of 192
+  std::vector<int32_t> cnt(gn);
+  std::vector<uint8_t> widx((size_t)gn * 192, 0);
+  std::vector<float> werr((size_t)gn * 192, 0.0f);
+  for (int b = 0; b < gn; ++b) {
+    cnt[b] = offsets[b + 1] - offsets[b];
+    memcpy(widx.data() + (size_t)b * 192, idx + offsets[b], (size_t)cnt[b]);
+    memcpy(werr.data() + (size_t)b * 192, err + offsets[b], sizeof(float) * (size_t)cnt[b]);
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_out_cnt, cnt.data(), sizeof(int32_t) * gn, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_out_idx, widx.data(), (size_t)gn * 192, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_out_err, werr.data(), sizeof(float) * gn * 192, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  search_installed(c, (size_t)offsets[gn]);
+  return GZ_OK;
+}
+
+int gz_probe_order_state(gz_ctx* c, float* weight, float* max_err) {
+  DeviceScope ds_(c);
+  if (!c) return GZ_E_ARG;
+  if (!c->have_search || !c->made.order_blocks) { c->err = "gz_order_build* must precede gz_probe_order_state"; return GZ_E_STATE; }
+  TRY(flush_order_advance(c));
+  const size_t bytes = sizeof(float) * (size_t)c->sg_n;
+  if (weight) HIPCHK(c, hipMemcpyAsync(weight, c->d_weight, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (max_err) HIPCHK(c, hipMemcpyAsync(max_err, c->d_max_err, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GZ_OK;
+}
+
 #ifdef GZ_EMU
 // Emulation build only: the emulated device pow of gz_pow_to_float_guarded off by u double ulps (the device library's
 // pow is accurate to a few ulps, and not libm's: in the emulation it IS libm's, and the guard would have nothing to catch)

@@ -80,6 +80,47 @@ void rank_all(const int16_t* coeffs, const int16_t* orig, int nb, int new_model,
 }
 }  // namespace
 
+// ---- the state a block search leaves for phase B, apart from the candidates in d_out_cnt / d_out_idx / d_out_err:
+// shared by phase A (gz_block_zeroing_orders_masked) and the tests' gz_probe_set_search, which installs candidates of
+// its own in the same place.
+// SelectFrequencyMasking's grid (processor.cc:546-552) is that of the mask's last component.  mode: 0 a 4:4:4 frame,
+// 1 / 2 the luma / chroma grid of a 4:2:0 one.
+static int search_mode_of(gz_ctx* c, int comp_mask, int* mode) {
+  *mode = 0;
+  if (c->cfac == 2) {
+    if (comp_mask == 1) *mode = 1;
+    else if (comp_mask == 6) *mode = 2;
+    else { c->err = "a 4:2:0 frame is searched with component mask 1 or 6"; return GZ_E_ARG; }
+  }
+  return GZ_OK;
+}
+// Before the candidates are written: what worked on the old grid is void, the new grid, the arrays.
+static int search_grid_begin(gz_ctx* c, int comp_mask, int mode) {
+  c->pending.void_up_to(Pending::kOrder);   // a new search grid: a pending order of the old one is void, and its descent
+  TRY(flush_order_advance(c));   // (an update of max_block_error that is still due belongs to the old grid)
+  const int nb = c->nb;   // capacity of the per-block arrays: the luma grid
+  c->sg_w = mode == 2 ? c->cbw : c->bw;
+  c->sg_h = mode == 2 ? c->cbh : c->bh;
+  c->sg_n = mode == 2 ? c->nbc : c->nb;
+  c->sg_factor = mode == 2 ? 2 : 1;
+  c->sg_mask = comp_mask;
+  if (!c->made.rank) {
+    TRY(regrow(c, c->stream, nullptr, 0,
+               {{(void**)&c->d_rank_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_rank_idx, (size_t)nb * 192}, {(void**)&c->d_rank_tables, sizeof(float) * 384},
+                {(void**)&c->d_out_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_out_idx, (size_t)nb * 192},
+                {(void**)&c->d_out_err, sizeof(float) * nb * 192}, {(void**)&c->d_csr_off, sizeof(int32_t) * ((size_t)nb + 1)}}));
+    HIPCHK(c, hipMemcpyAsync(c->d_rank_tables, kOrderCsf, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_rank_tables + 192, kOrderBias, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
+    c->made.rank = true;
+  }
+  return GZ_OK;
+}
+// Behind them, once their number is known on the host (it bounds every global order).
+static void search_installed(gz_ctx* c, size_t total) {
+  c->have_search = true;
+  c->search_total = total;
+}
+
 extern "C" {
 
 int gz_rank_zeroing_candidates(const int16_t* coeffs, const int16_t* orig, int nb,
@@ -103,32 +144,12 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
   DeviceScope ds_(c);
   if (!c || !offsets || !idx || lookahead < 1 || cap < 0 || comp_mask < 1 || comp_mask > 7) return GZ_E_ARG;
   if (!c->have_cand || !c->have_orig) { c->err = "needs original and candidate coefficients"; return GZ_E_STATE; }
-  // SelectFrequencyMasking's grid (processor.cc:546-552) is that of the mask's last component
   int mode = 0;
-  if (c->cfac == 2) {
-    if (comp_mask == 1) mode = 1;
-    else if (comp_mask == 6) mode = 2;
-    else { c->err = "a 4:2:0 frame is searched with component mask 1 or 6"; return GZ_E_ARG; }
-  }
+  TRY(search_mode_of(c, comp_mask, &mode));
   TRY(ensure_block_mask(c));
-  c->pending.void_up_to(Pending::kOrder);   // a new search grid: a pending order of the old one is void, and its descent
-  TRY(flush_order_advance(c));   // (an update of max_block_error that is still due belongs to the old grid)
+  TRY(search_grid_begin(c, comp_mask, mode));
   const int nb = c->nb;   // capacity of the per-block arrays: the luma grid
-  const int gn = mode == 2 ? c->nbc : c->nb;
-  c->sg_w = mode == 2 ? c->cbw : c->bw;
-  c->sg_h = mode == 2 ? c->cbh : c->bh;
-  c->sg_n = gn;
-  c->sg_factor = mode == 2 ? 2 : 1;
-  c->sg_mask = comp_mask;
-  if (!c->made.rank) {
-    TRY(regrow(c, c->stream, nullptr, 0,
-               {{(void**)&c->d_rank_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_rank_idx, (size_t)nb * 192}, {(void**)&c->d_rank_tables, sizeof(float) * 384},
-                {(void**)&c->d_out_cnt, sizeof(int32_t) * nb}, {(void**)&c->d_out_idx, (size_t)nb * 192},
-                {(void**)&c->d_out_err, sizeof(float) * nb * 192}, {(void**)&c->d_csr_off, sizeof(int32_t) * ((size_t)nb + 1)}}));
-    HIPCHK(c, hipMemcpyAsync(c->d_rank_tables, kOrderCsf, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_rank_tables + 192, kOrderBias, sizeof(float) * 192, hipMemcpyHostToDevice, c->stream));
-    c->made.rank = true;
-  }
+  const int gn = c->sg_n;
   {  // input_order of every block, ranked on the device with std::sort's permutation
     RankArgs r;
     r.coeffs = c->d_cand; r.orig = c->d_orig;
@@ -168,8 +189,6 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
   else if (mode == 1) GZ_LAUNCH(k_block_search<1>, dim3(gn), dim3(64), c->stream, a);
   else GZ_LAUNCH(k_block_search<2>, dim3(gn), dim3(256), c->stream, a);
   KCHK(c);
-  c->have_search = true;
-  c->search_total = 0;   // set below, once the offsets are on the host
   // The CSR arrays are made on the device (offsets = scan of the counts, indices packed into the
   // ranked lists' buffer, which the search is done with): the host copies what the caller takes.
   GZ_LAUNCH(k_csr_offsets, dim3(1), dim3(1024), c->stream, (const int32_t*)c->d_out_cnt, gn, c->d_csr_off);
@@ -182,7 +201,7 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
   HIPCHK(c, hipMemcpyAsync(offsets, c->d_csr_off, sizeof(int32_t) * ((size_t)gn + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const long total = offsets[gn];
-  c->search_total = (size_t)total;
+  search_installed(c, (size_t)total);
   // evaluations: step s of a block with n candidates compares min(lookahead, n - s) of them (summed in
   // closed form), on every 8x8 block of its area that lies inside the image
   c->search_evaluations = 0;

@@ -570,6 +570,17 @@ int gz_probe_silver_yuv420(int device, const uint8_t* srgb, int w, int h, int gu
  * 64-bit), one launch after the other. */
 int gz_probe_scan_offsets(int device, const uint32_t* values, int n_values, const int32_t* lengths, int n_lengths,
                           uint32_t start_epoch, uint64_t* out);
+/* Phase B on state of the caller's choosing (tests/order_domain.py).  None of the three launches a kernel.
+ * gz_probe_set_block_max: the nb per-8x8-block maxima of a distance map, as if a gz_compare had left them.
+ * gz_probe_set_search: the candidates of a block search as gz_block_zeroing_orders_masked returns them (CSR: offsets of
+ * the mask's search grid on the current frame, at most 192 entries per block), put where that call leaves them for the
+ * orders, steps and descents that follow; a pending order or descent is void, as after a search.
+ * gz_probe_order_state: the device's block weights and max_block_error (search-grid blocks each; either may be NULL);
+ * an update of gz_order_advance that is still due is made first, so a test of the update that rides on the next
+ * gz_order_build_auto reads AFTER that build. */
+int gz_probe_set_block_max(gz_ctx* ctx, const float* block_max);
+int gz_probe_set_search(gz_ctx* ctx, int comp_mask, const int32_t* offsets, const uint8_t* idx, const float* err);
+int gz_probe_order_state(gz_ctx* ctx, float* weight, float* max_err);
 /* div2_shared against the device's own IEEE division, on the device: for the nnum numerators (an
  * even number, at most 12: each pair shares its reciprocal) and every stride-th float denominator
  * of [2^-40, 2^40) -- 80 * 2^23 of them, stride 1: all -- the number of quotients that differ.

@@ -176,11 +176,15 @@ def case_block_search(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
     oc.close()
 
 
-def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
+def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769, census=None):
     """Phase B's global candidate order on the device (processor.cc:622-663): the construction
     from the reference's definition, the device-side block weights
     (ComputeBlockErrorAdjustmentWeights, pinned through the oracle) and max_block_error
-    bookkeeping, and single-coefficient edits."""
+    bookkeeping, and single-coefficient edits.  The restatements of tests/order_domain.py are pinned
+    here on the way: on these arrays they give what the oracle and the loops below give (census: the
+    arms this photograph takes, counted by them)."""
+    import order_domain as od
+    g = od.Grid(w, h)
     rng = np.random.default_rng(RNG_SEED + 3 * w + h)
     rgb = images.crop(w, h, x0, y0) if max(w, h) <= 444 else images.tiled(w, h)
     oc = oracle.comparator(rgb, target)
@@ -198,6 +202,8 @@ def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
             for radius in (1, 2, 4):
                 zero = np.zeros_like(dm)
                 wgt = oc.block_weights(direction, radius, 1.0, dm if use_dm else zero)
+                assert_bits_equal(od.weights_of(g, bmax, target, direction, radius, 1.0, use_dm, census), wgt,
+                                  "order_domain.weights_of")
                 # the reference's construction loop
                 exp = []
                 btc = 0
@@ -214,9 +220,12 @@ def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
                         btc += at > 0
                     exp.extend((b, v) for v in vals.astype(np.float32))
                 limit = np.float32(0.75) * np.float32(target)
+                mb, mv, mbtc, mbelow = od.build_order(off, err, next_cand, max_err, wgt, direction, float(limit), census)
+                assert mbtc == btc and mb.tolist() == [b for b, _ in exp], "order_domain.build_order"
+                assert_bits_equal(mv, np.array([v for _, v in exp], np.float32), "order_domain.build_order")
                 total, got_btc, below = ctx.order_build_auto(direction, radius, 1.0, use_dm,
                                                              next_cand, limit=float(limit))
-                assert total == len(exp) and got_btc == btc, (total, len(exp), got_btc, btc)
+                assert total == len(exp) and got_btc == btc and below == mbelow, (total, len(exp), got_btc, btc)
                 got = ctx.order_fetch(0, total)
                 if total:
                     eb = np.array([b for b, _ in exp], np.int32)
@@ -237,6 +246,8 @@ def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
             ctx.order_build_auto(direction, 4, 1.0, use_dm, next_cand)
             ctx.order_advance(float(thr), direction)
             wgt = oc.block_weights(direction, 4, 1.0, dm if use_dm else np.zeros_like(dm))
+            assert_bits_equal(od.advance(max_err, wgt, thr, direction),
+                              (max_err + (wgt * thr) * np.float32(direction)).astype(np.float32), "order_domain.advance")
             max_err = (max_err + (wgt * thr) * np.float32(direction)).astype(np.float32)
         # whole-block steps (processor.cc:704-736): zero / restore the next candidates
         def quantize(raw, q):
@@ -267,8 +278,13 @@ def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
                         precious = abs(int(ob[k])) >= (4 if hf < 60 else 8)
                     if not precious:
                         exp[c, b, k] = newval
-            ctx.order_build_auto(direction, 1, 1.0, True, next_cand)   # uploads next_cand
             qs_all = np.full((3, 64), qs, np.int32)
+            assert_bits_equal(od.apply_steps(g, co, orig, qs_all, off, idx, next_cand, direction, sel, counts[sel],
+                                             census).reshape(exp.shape), exp, "order_domain.apply_steps")
+            assert_bits_equal(od.hist_delta(g, co, exp, qs_all, census), od.ac_hist(g, exp, qs_all) - od.ac_hist(g, co, qs_all),
+                              "order_domain.hist_delta")
+            exp_delta = od.hist_delta(g, co, exp, qs_all)
+            ctx.order_build_auto(direction, 1, 1.0, True, next_cand)   # uploads next_cand
             before = ctx.jpeg_histograms(qs_all)                        # also: the symbols' quantiser
             ctx.apply_candidate_steps(direction, sel, counts[sel])
             delta = ctx.steps_histogram_delta()
@@ -278,6 +294,7 @@ def case_global_order(L, w, h, x0=300, y0=150, qs=3, target=0.971769):
             after = ctx.jpeg_histograms(qs_all)
             assert_bits_equal(delta, after[1].astype(np.int64) - before[1].astype(np.int64),
                               f"steps_histogram_delta direction {direction}")
+            assert_bits_equal(delta, exp_delta, f"steps_histogram_delta == order_domain.hist_delta, direction {direction}")
         cq = co
         # single-coefficient edits == block scatter
         pos = rng.choice(3 * nb * 64, size=min(500, nb), replace=False).astype(np.int32)
@@ -566,10 +583,12 @@ def case_jpeg_entropy420(L, H, w, h, chk, x0=0, y0=0):
             assert got == exp, (len(got), len(exp), ncomp)
 
 
-def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
+def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769, census=None):
     """Phase B's order on the chroma grid of a 4:2:0 frame: device-side weights over 16x16
     areas, the construction loop, whole-block steps on components 1 and 2 with their
-    statistics change."""
+    statistics change.  (order_domain's restatements pinned on the way, as in case_global_order.)"""
+    import order_domain as od
+    g = od.Grid(w, h, "420", 6)
     rng = np.random.default_rng(RNG_SEED + 13 * w + h)
     rgb = images.crop(w, h, x0, y0)
     oc = chk.comparator(rgb, target)
@@ -579,7 +598,7 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
         q = np.full((3, 64), qs, np.int32)
         cq = ctx.quantize(q)
         off, idx, err = ctx.block_zeroing_orders(comp_mask=6)
-        dist, dm, _ = ctx.compare()
+        dist, dm, bmax = ctx.compare()
         gn = ctx.nbc
         cnt = np.diff(off)
         max_err = np.zeros(gn, np.float32)
@@ -588,6 +607,8 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
             next_cand = (rng.integers(0, 1000, gn) % (cnt + 1)).astype(np.int32)
             for radius in (1, 2):
                 wgt = oc.block_weights_factor(direction, radius, 1.0, 2, dm)
+                assert_bits_equal(od.weights_of(g, bmax, target, direction, radius, 1.0, True, census), wgt,
+                                  "order_domain.weights_of (factor 2)")
                 exp = []
                 btc = 0
                 for b in range(gn):
@@ -602,6 +623,9 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
                         vals = (max_err[b] - e[:at][::-1]) / wgt[b]
                         btc += at > 0
                     exp.extend((b, v) for v in vals.astype(np.float32))
+                mb, mv, mbtc, _ = od.build_order(off, err, next_cand, max_err, wgt, direction, None, census)
+                assert mbtc == btc and mb.tolist() == [b for b, _ in exp], "order_domain.build_order"
+                assert_bits_equal(mv, np.array([v for _, v in exp], np.float32), "order_domain.build_order")
                 total, got_btc, _ = ctx.order_build_auto(direction, radius, 1.0, True, next_cand)
                 assert total == len(exp) and got_btc == btc, (total, len(exp), got_btc, btc)
                 got = ctx.order_fetch(0, total)
@@ -636,6 +660,10 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
                         precious = abs(int(ob[k])) >= (4 if hf < 60 else 8)
                     if not precious:
                         exp[coff[c] + b, k] = newval
+            assert_bits_equal(od.apply_steps(g, co, orig, q, off, idx, next_cand, direction, sel, counts[sel], census), exp,
+                              "order_domain.apply_steps (4:2:0)")
+            exp_delta = od.hist_delta(g, co, exp, q, census)
+            assert_bits_equal(exp_delta, od.ac_hist(g, exp, q) - od.ac_hist(g, co, q), "order_domain.hist_delta (4:2:0)")
             ctx.order_build_auto(direction, 1, 1.0, True, next_cand)
             before = ctx.jpeg_histograms(q)
             ctx.apply_candidate_steps(direction, sel, counts[sel])
@@ -645,6 +673,7 @@ def case_global_order420(L, w, h, chk, x0=0, y0=0, qs=3, target=0.971769):
             after = ctx.jpeg_histograms(q)
             assert_bits_equal(delta, after[1].astype(np.int64) - before[1].astype(np.int64),
                               f"steps_histogram_delta (4:2:0) direction {direction}")
+            assert_bits_equal(delta, exp_delta, f"steps_histogram_delta == order_domain.hist_delta (4:2:0), direction {direction}")
     oc.close()
 
 
@@ -1152,3 +1181,273 @@ def case_scan_probe(L, repeats=20, lengths=SCAN_PROBE_LENGTHS):
     check_scan_probe(L, v, long_ones * repeats)
     v = scan_probe_values("2^20-1", nmax)
     check_scan_probe(L, v, long_ones * repeats)
+
+
+# ------------------------------------------------ phase B on tests/order_domain.py --
+class TargetContexts:
+    """One context per (size, target, tag), kept for the cases that follow; close() at the end of the module."""
+
+    def __init__(self, L):
+        self.L, self.ctx = L, {}
+
+    def get(self, w, h, target, tag=""):
+        key = (w, h, float(target), tag)
+        if key not in self.ctx:
+            self.ctx[key] = self.L.context(np.zeros((h, w, 3), np.uint8), target)
+        return self.ctx[key]
+
+    def close(self):
+        for c in self.ctx.values():
+            c.close()
+        self.ctx = {}
+
+
+def _order_frame(ctx, g):
+    factor = 2 if g.layout == "420" else 1
+    if ctx.cfac != factor or getattr(ctx, "_od_frame", None) != factor:
+        ctx.set_frame(factor)
+        ctx._od_frame, ctx._od_search = factor, None
+
+
+def _install_search(ctx, g, key, off, idx, err):
+    """gz_probe_set_search, once for the cases that share `key` on this context."""
+    _order_frame(ctx, g)
+    if key is None or getattr(ctx, "_od_search", None) != (g.mask, key):
+        ctx.probe_set_search(off, idx, err, comp_mask=g.mask)
+        ctx._od_search = (g.mask, key)
+
+
+def _unit_search(ctx, g):
+    """One candidate of error 1 per block: an order holds the blocks of non-zero weight, their weights in its vals."""
+    off = np.arange(g.gn + 1, dtype=np.int32)
+    _install_search(ctx, g, "unit", off, np.ones(g.gn, np.uint8), np.ones(g.gn, np.float32))
+    return off, np.ones(g.gn, np.float32)
+
+
+def _check_order(ctx, got_counts, exp, what, permuted=False):
+    """(total, blocks_to_change, below) and the entries of the context's order against build_order's."""
+    eb, ev, btc, below = exp
+    assert got_counts == (eb.size, btc, below), (what, got_counts, (eb.size, btc, below))
+    got = ctx.order_fetch(0, eb.size)
+    if permuted:       # behind a descent: the same entries, rearranged
+        key = lambda b, v: np.lexsort((b, v.view(np.uint32)))
+        i, j = key(got["block"], got["val"]), key(eb, ev)
+        assert_bits_equal(got["block"][i], eb[j], what + ": blocks (as a set)")
+        assert_bits_equal(got["val"][i], ev[j], what + ": vals (as a set)")
+    else:
+        assert_bits_equal(got["block"], eb, what + ": blocks")
+        assert_bits_equal(got["val"], ev, what + ": vals")
+    return got
+
+
+def check_weight_case(ctx, case, host_form=False):
+    """k_block_max_group / k_weights_flag / k_weights_gather through gz_order_build_auto at every radius, direction
+    and target_mul: the device's weights bit for bit, and the order they select."""
+    import order_domain as od
+    g = case.g
+    off, err = _unit_search(ctx, g)
+    ctx.probe_set_block_max(case.bmax8)
+    for direction in (1, -1):
+        nc = np.zeros(g.gn, np.int32) if direction > 0 else np.ones(g.gn, np.int32)
+        for r in od.RADII:
+            for mul in od.MULS:
+                what = f"{case.family} {g.name} target {case.target} direction {direction} r {r} mul {mul}"
+                exp = case.reference(direction, r, mul)
+                counts = ctx.order_build_auto(direction, r, mul, case.use_distmap, nc, limit=0.5)
+                wgt, me = ctx.probe_order_state()
+                assert_bits_equal(wgt, exp, "weights: " + what)
+                _check_order(ctx, counts, od.build_order(off, err, nc, me, exp, direction, 0.5), what)
+                if host_form:
+                    f = ctx.block_weights_factor(direction, r, mul, g.factor, case.use_distmap)
+                    assert_bits_equal(f, exp, "gz_block_weights_factor: " + what)
+
+
+def case_order_weights(contexts, family, grid_index, target, host_form=False):
+    import order_domain as od
+    g = od.WEIGHT_GRIDS[grid_index]
+    ctx = contexts.get(g.w, g.h, target)
+    ctx.order_reset()
+    for case in od.weight_cases(family, g, target):
+        check_weight_case(ctx, case, host_form)
+
+
+def check_order_case(ctx, case):
+    """One input through gz_order_build (host weights), gz_order_build_auto, _begin / _end and the fused
+    _descend_begin: the same entries from all four."""
+    import order_domain as od
+    g = case.g
+    what = f"{case.family} {g.name} direction {case.direction}"
+    _install_search(ctx, g, None, case.off, case.idx, case.err)
+    ctx.probe_set_block_max(case.bmax8)
+    wgt = case.weights()
+    exp = case.reference()
+    lim = case.limit
+    args = (case.direction, case.r, case.mul, True, case.next_cand)
+    _check_order(ctx, ctx.order_build(case.direction, case.next_cand, case.max_err, wgt, limit=lim), exp,
+                 what + ": gz_order_build")
+    _check_order(ctx, ctx.order_build_auto(*args, limit=lim), exp, what + ": gz_order_build_auto")
+    dw, dme = ctx.probe_order_state()
+    assert_bits_equal(dw, wgt, what + ": device weights")
+    assert_bits_equal(dme, case.max_err, what + ": max_block_error")
+    ctx.order_build_auto_begin(*args, limit=lim)
+    _check_order(ctx, ctx.order_build_auto_end(), exp, what + ": _begin / _end")
+    per_block = 2.0 if case.direction > 0 else 0.2
+    ctx.order_build_auto_descend_begin(*args, per_block, 16, 12, limit=lim)
+    counts = ctx.order_build_auto_end()
+    log, last = ctx.order_descend_end()
+    got = _check_order(ctx, counts, exp, what + ": _descend_begin", permuted=True)
+    n = exp[0].size
+    if n > 16:
+        assert len(log) > 0 and last == od.derived_last(per_block, exp[2], n), (what, last, exp[2], n)
+        for lo, hi, cut in log.astype(np.int64):     # each cut parts its range
+            assert lo < cut <= hi and (cut == hi or got["val"][lo:cut].max() <= got["val"][cut:hi].min()), (what, lo, hi, cut)
+    else:
+        assert len(log) == 0 and last == 0, what
+
+
+def case_order_build(contexts, family):
+    import order_domain as od
+    for case in od.order_cases(family):
+        check_order_case(contexts.get(case.g.w, case.g.h, case.target), case)
+
+
+def case_order_advance(contexts, family):
+    """gz_order_advance: the update rides on the next gz_order_build_auto's k_weights_gather with the weights that
+    kernel replaces, once; two in a row; dropped by gz_order_build."""
+    import order_domain as od
+    g = od.grid_of_blocks(17, 13)
+    target = od.TARGETS[0]
+    ctx = contexts.get(g.w, g.h, target)
+    off, err = _unit_search(ctx, g)
+    A = np.full((g.bh, g.bw), 0.25 * target, np.float32)
+    A[3, 4] = A[9, 12] = 3 * target
+    B = np.full((g.bh, g.bw), 0.25 * target, np.float32)
+    B[6, 8] = 3 * target
+    ones = np.ones(g.gn, np.int32)
+    wA = od.weights_of(g, A, target, -1, 2, 1.0)
+    wB1, wB2 = (od.weights_of(g, B, target, -1, r, 1.0) for r in (1, 2))
+    assert (wA != wB2).any() and (wB1 != wB2).any()
+    thr, thr2 = np.float32(0.3125 + 1e-3), np.float32(0.07)
+
+    def start():
+        ctx.order_reset()
+        ctx.probe_set_block_max(A)
+        ctx.order_build_auto(-1, 2, 1.0, True, ones)
+        w, me = ctx.probe_order_state()
+        assert_bits_equal(w, wA, "weights before the advance")
+        assert not me.any()
+        return me
+
+    def state_is(w, me, what):
+        gw, gme = ctx.probe_order_state()
+        assert_bits_equal(gw, w, family + ": weights " + what)
+        assert_bits_equal(gme, me, family + ": max_block_error " + what)
+    me = start()
+    if family == "advance/fused":
+        ctx.order_advance(float(thr), -1)
+        ctx.probe_set_block_max(B)
+        counts = ctx.order_build_auto(-1, 2, 1.0, True, ones)
+        me = od.advance(me, wA, thr, -1)
+        _check_order(ctx, counts, od.build_order(off, err, ones, me, wB2, -1), family)     # (read AFTER the build)
+        state_is(wB2, me, "after the build that carries the advance")
+    elif family == "advance/escalate":
+        gy, gx = np.mgrid[0:g.bh, 0:g.bw]
+        ring2 = (np.maximum(abs(gy - 6), abs(gx - 8)) == 2).reshape(-1)
+        nc = ring2.astype(np.int32)                     # applied candidates only at distance 2 of the hot block
+        ctx.order_advance(float(thr), -1)
+        ctx.probe_set_block_max(B)
+        assert ctx.order_build_auto(-1, 1, 1.0, True, nc)[0] == 0          # radius 1: an empty order
+        counts = ctx.order_build_auto(-1, 2, 1.0, True, nc)                # radius 2
+        me = od.advance(me, wA, thr, -1)                                   # once, with the OLD weights
+        exp = od.build_order(off, err, nc, me, wB2, -1)
+        assert exp[0].size == ring2.sum() > 0
+        _check_order(ctx, counts, exp, family)
+        state_is(wB2, me, "after the escalation")
+    elif family == "advance/twice":
+        ctx.order_advance(float(thr), -1)
+        ctx.order_advance(float(thr2), 1)
+        ctx.probe_set_block_max(B)
+        counts = ctx.order_build_auto(-1, 2, 1.0, True, ones)
+        me = od.advance(od.advance(me, wA, thr, -1), wA, thr2, 1)
+        _check_order(ctx, counts, od.build_order(off, err, ones, me, wB2, -1), family)
+        state_is(wB2, me, "after two advances")
+        ctx.order_advance(float(thr2), -1)                                 # ... and read without a build: made first
+        state_is(wB2, od.advance(me, wB2, thr2, -1), "flushed by the read")
+    elif family == "advance/replaced":
+        ctx.order_advance(float(thr), -1)
+        rng = np.random.default_rng(5)
+        hw = rng.choice(np.array([0, 1, 0.5, 1 / 3], np.float32), g.gn)
+        hme = rng.random(g.gn).astype(np.float32)
+        counts = ctx.order_build(-1, ones, hme, hw)
+        _check_order(ctx, (counts[0], counts[1], 0), od.build_order(off, err, ones, hme, hw, -1), family)
+        state_is(hw, hme, "after gz_order_build replaced the state")
+    else:
+        raise KeyError(family)
+
+
+def check_step_case(ctx, case):
+    """gz_apply_candidate_steps + gz_steps_histogram_delta (k_apply_steps_hist / k_steps_hist_sum), or k_apply_steps on
+    a context that has no statistics quantiser: coefficients and the AC statistics change, call by call."""
+    g = case.g
+    _order_frame(ctx, g)
+    ctx._od_search = None
+    (ctx.set_orig_coeffs_420 if g.layout == "420" else ctx.set_orig_coeffs)(case.layout(case.orig))
+    ctx._od_frame = ctx.cfac
+    ctx.quantize(case.q, download=False)                 # the steps' quantiser
+    ctx.set_coeffs(case.layout(case.cand))
+    ctx.probe_set_search(case.off, case.idx, np.zeros(case.idx.size, np.float32), comp_mask=g.mask)
+    if case.with_statistics:
+        ctx.jpeg_histograms(case.q)                      # the symbols' quantiser
+    zero_w, zero_e = np.zeros(g.gn, np.float32), np.zeros(g.gn, np.float32)
+    for i, ((direction, next_cand, blocks, counts, read), (exp, exp_delta)) in enumerate(zip(case.calls, case.reference())):
+        what = f"{case.family} {g.name} call {i} direction {direction} n {len(blocks)}"
+        ctx.order_build(direction, next_cand, zero_e, zero_w)        # uploads next_cand (an empty order)
+        ctx.apply_candidate_steps(direction, blocks, counts)
+        if read and case.with_statistics:
+            assert_bits_equal(ctx.steps_histogram_delta(), exp_delta, "statistics change: " + what)
+        assert_bits_equal(ctx.get_coeffs().reshape(-1, 64), exp, "coefficients: " + what)
+
+
+def case_order_steps(L, contexts, family):
+    import order_domain as od
+    for case in od.step_cases(family):
+        g = case.g
+        if case.with_statistics:
+            check_step_case(contexts.get(g.w, g.h, 1.0, "steps"), case)
+        else:       # k_apply_steps: a context no gz_jpeg_histograms has given a statistics quantiser
+            with L.context(np.zeros((g.h, g.w, 3), np.uint8), 1.0) as ctx:
+                check_step_case(ctx, case)
+
+
+def case_order_descent(contexts, per_block, big, short=False, log_every=1, every=1):
+    """The position gz_order_descend_begin derives on the device == the reference's, and its cut log == that of
+    gz_order_descend with that position on a second context that never derived one."""
+    import order_domain as od
+    g = od.Grid(*od.BIG) if big else od.grid_of_blocks(17, 13)
+    a, b = contexts.get(g.w, g.h, 1.0, "descent"), contexts.get(g.w, g.h, 1.0, "descent/plain")
+    search = od.descent_search(g)
+    for c in (a, b):
+        _install_search(c, g, "descent", *search)
+    values = od.btc_values(per_block, g.gn)
+    if big:
+        values = [v for v in values if v > 221]
+    if short:
+        values = [v for v in values if v <= 60 or v % 7 == 0]
+    values = values[::every]       # (the emulation: a sample of the large context's values)
+    for i, btc in enumerate(values):
+        nc = od.descent_next_cand(g, btc, short)
+        n = btc * (1 if short else od.DESCENT_CNT)
+        a.order_build_auto_begin(1, 1, 1.0, False, nc)
+        a.order_descend_begin(per_block, 16, 12)
+        total, got_btc, _ = a.order_build_auto_end()
+        log, last = a.order_descend_end()
+        assert (total, got_btc) == (n, btc), (per_block, btc, total, got_btc)
+        if n <= 16:
+            assert len(log) == 0 and last == 0, (per_block, btc)
+            continue
+        assert len(log) > 0 and last == od.derived_last(per_block, btc, n), (per_block, btc, n, last)
+        if i % log_every == 0:
+            b.order_build_auto(1, 1, 1.0, False, nc)
+            log2 = b.order_descend(last, 16, 12)
+            assert_bits_equal(log, log2, f"cut log, per_block {per_block} blocks_to_change {btc}")
+            assert_bits_equal(a.order_fetch(0, n), b.order_fetch(0, n), f"order after the descent, {per_block} {btc}")

@@ -132,6 +132,9 @@ def test_new_entry_points_reject_bad_arguments(lib_path):
     assert lib.gz_probe_rank_sort(0, None, None, 1, None) == -1
     assert lib.gz_probe_scan_offsets(0, None, 1, None, 1, 0, None) == -1
     assert lib.gz_probe_scan_offsets(0, z.ctypes.data, 1, z.ctypes.data, 1, 0x3fffffff, u64.ctypes.data) == -1
+    assert lib.gz_probe_set_block_max(None, z.ctypes.data) == -1
+    assert lib.gz_probe_set_search(None, 7, z.ctypes.data, z.ctypes.data, z.ctypes.data) == -1
+    assert lib.gz_probe_order_state(None, z.ctypes.data, z.ctypes.data) == -1
     assert lib.gz_trim_pool() == 0          # nothing cached: nothing to release, no device needed
     assert lib.gz_order_build(None, 1, z.ctypes.data, z.ctypes.data, z.ctypes.data, 0, 0.0,
                               u64.ctypes.data, z.ctypes.data, None) == -1
