@@ -30,6 +30,23 @@ class GzConfig(C.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+
+GZ_DT_U8, GZ_DT_F32, GZ_DT_F16, GZ_DT_BF16 = 0, 1, 2, 3
+
+
+class GzDeviceImage(C.Structure):
+    """gz_device_image of include/guetzli_amd.h: a strided w x h x 3 image in device memory."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_y", C.c_int64), ("stride_x", C.c_int64),
+                ("stride_c", C.c_int64), ("producer_stream", _P)]
+
+
+def device_image(ptr, dtype, strides, stream=0):
+    """A GzDeviceImage: ptr = device address of element (0, 0, 0), dtype = GZ_DT_*, strides = (y, x, c) in elements,
+    stream = the hipStream_t whose work produced the data (0: none to wait for)."""
+    sy, sx, sc = (int(v) for v in strides)
+    return GzDeviceImage(C.sizeof(GzDeviceImage), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None)
+
+
 # name -> (restype, argtypes); mirrors include/guetzli_amd.h one to one
 SIGNATURES = {
     "gz_abi_version": (_I, []),
@@ -44,6 +61,9 @@ SIGNATURES = {
     "gz_create": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
     "gz_destroy": (None, [_P]),
     "gz_set_rgb": (_I, [_P, _P]),
+    "gz_create_from_device": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
+    "gz_set_rgb_device": (_I, [_P, _P]),
+    "gz_pack_rgb_device": (_I, [_I, _P, _I, _I, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -282,6 +302,16 @@ class Library:
     def context(self, rgb, target, device=0):
         return Context(self, rgb, target, device)
 
+    def context_from_device(self, image, w, h, target, device=0):
+        """gz_create_from_device: a context whose original is the device-resident `image` (device_image(...))."""
+        return Context.from_device(self, image, w, h, target, device)
+
+    def pack_rgb_device(self, image, w, h, device=0):
+        """gz_pack_rgb_device: the ingest kernel's bytes of `image` (device_image(...)) -> uint8 [h][w][3]."""
+        out = np.zeros((h, w, 3), np.uint8)
+        self.check(self.lib.gz_pack_rgb_device(device, C.byref(image), w, h, _ptr(out)))
+        return out
+
 
 class Context:
     """One (image, GPU) context == one guetzli::ButteraugliComparator + OutputImage."""
@@ -289,8 +319,31 @@ class Context:
     def __init__(self, library, rgb, target, device=0):
         self.L = library
         self.rgb = np.ascontiguousarray(rgb, np.uint8)
-        self.h, self.w, ch = self.rgb.shape
+        h, w, ch = self.rgb.shape
         assert ch == 3
+        self._set_geometry(w, h)
+        err = C.c_int(0)
+        self.handle = library.lib.gz_create(device, self.w, self.h, _ptr(self.rgb),
+                                            float(target), C.byref(err))
+        if not self.handle:
+            library.check(err.value or -3)
+
+    @classmethod
+    def from_device(cls, library, image, w, h, target, device=0):
+        """gz_create_from_device: the original is the device-resident `image` (device_image(...)).  The pixels stay
+        where they are: such a context has rgb = None (as one whose original set_rgb_device replaced)."""
+        self = cls.__new__(cls)
+        self.L = library
+        self.rgb = None
+        self._set_geometry(w, h)
+        err = C.c_int(0)
+        self.handle = library.lib.gz_create_from_device(device, w, h, C.byref(image), float(target), C.byref(err))
+        if not self.handle:
+            library.check(err.value or -3)
+        return self
+
+    def _set_geometry(self, w, h):
+        self.w, self.h = w, h
         self.bw, self.bh = (self.w + 7) // 8, (self.h + 7) // 8
         self.nb = self.bw * self.bh
         # the frame: 4:4:4 (coefficient arrays [3][nb][64]) until downsample() /
@@ -298,11 +351,6 @@ class Context:
         self.cfac = 1
         self.cbw, self.cbh = (self.w + 15) // 16, (self.h + 15) // 16
         self.nbc = self.cbw * self.cbh
-        err = C.c_int(0)
-        self.handle = library.lib.gz_create(device, self.w, self.h, _ptr(self.rgb),
-                                            float(target), C.byref(err))
-        if not self.handle:
-            library.check(err.value or -3)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -345,6 +393,11 @@ class Context:
         assert rgb.shape == (self.h, self.w, 3)
         self.rgb = rgb
         self._chk(self.L.lib.gz_set_rgb(self.handle, _ptr(rgb)))
+
+    def set_rgb_device(self, image):
+        """gz_set_rgb_device: the original replaced by the device-resident `image` (device_image(...), w x h)."""
+        self.rgb = None
+        self._chk(self.L.lib.gz_set_rgb_device(self.handle, C.byref(image)))
 
     def synchronize(self):
         self._chk(self.L.lib.gz_synchronize(self.handle))

@@ -314,6 +314,7 @@ struct gz_ctx {
   // gz_compare_begin has put on the main stream: both only read the candidate coefficients
   hipStream_t entropy_stream = nullptr;
   hipEvent_t ev_candidate = nullptr;   // main stream: the candidate is in place
+  hipEvent_t ev_ingest = nullptr;      // gz_set_rgb_device: the producer's stream has written the source (made on first use)
   std::string err;
 
   uint8_t* d_rgb = nullptr;

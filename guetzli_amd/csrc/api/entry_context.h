@@ -118,19 +118,109 @@ const char* gz_strerror(int code) {
 
 const char* gz_last_error(const gz_ctx* ctx) { return ctx ? ctx->err.c_str() : ""; }
 
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, float target, int* err);
+// ---- device-resident input (gz_kernels_ingest.h) ----
+static size_t ingest_elem_size(int dtype) { return dtype == GZ_DT_U8 ? 1 : dtype == GZ_DT_F32 ? 4 : 2; }
+// The arguments alone: no device call (the library answers these without a GPU).
+static int check_device_image(const gz_device_image* img, int w, int h) {
+  if (!img || img->struct_size != (int)sizeof(gz_device_image) || !img->data) return GZ_E_ARG;
+  if (img->dtype < GZ_DT_U8 || img->dtype > GZ_DT_BF16) return GZ_E_ARG;
+  if (img->stride_y < 0 || img->stride_x < 0 || img->stride_c < 0) return GZ_E_ARG;
+  if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) return GZ_E_ARG;
+  // the last element's offset (h-1) sy + (w-1) sx + 2 sc in 62 bits: every term is bounded before it is formed
+  const uint64_t lim = (1ull << 62) - 1;
+  const uint64_t sy = (uint64_t)img->stride_y, sx = (uint64_t)img->stride_x, sc = (uint64_t)img->stride_c;
+  if ((h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1)) || sc > lim / 2) return GZ_E_ARG;
+  const uint64_t ty = sy * (uint64_t)(h - 1), tx = sx * (uint64_t)(w - 1), tc = sc * 2;   // each <= lim < 2^62
+  if (ty + tx > lim || ty + tx + tc > lim) return GZ_E_ARG;
+  return GZ_OK;
+}
+// Where the memory lives: it must be readable by `device` (the current one).  An ordinary host pointer, memory of
+// another GPU or an extent that leaves its allocation is an argument error here, not a fault in the kernel.
+static int check_device_pointer(int device, const gz_device_image* img, int w, int h, std::string* why) {
+#ifndef GZ_EMU
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, img->data) != hipSuccess) {
+    (void)hipGetLastError();
+    if (why) *why = "gz_device_image.data is not memory the HIP runtime knows (a host pointer?)";
+    return GZ_E_ARG;
+  }
+  const bool readable = (at.type == hipMemoryTypeDevice && at.device == device) || at.type == hipMemoryTypeManaged ||
+                        (at.type == hipMemoryTypeHost && at.devicePointer == img->data);
+  if (!readable) {
+    if (why) *why = at.type == hipMemoryTypeDevice ? "gz_device_image.data lives on device " + std::to_string(at.device) + ", the context on " + std::to_string(device)
+                                                   : std::string("gz_device_image.data is not device-readable memory (a host pointer?)");
+    return GZ_E_ARG;
+  }
+  if (at.type == hipMemoryTypeDevice) {
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)img->data) == hipSuccess) {
+      const uint64_t last = (uint64_t)img->stride_y * (uint64_t)(h - 1) + (uint64_t)img->stride_x * (uint64_t)(w - 1) + (uint64_t)img->stride_c * 2;
+      const uint64_t room = (uint64_t)((const char*)base + size - (const char*)img->data) / ingest_elem_size(img->dtype);
+      if (last >= room) {
+        if (why) *why = "gz_device_image: the strides lead outside the allocation that holds data";
+        return GZ_E_ARG;
+      }
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+#else
+  (void)device; (void)img; (void)w; (void)h; (void)why;
+#endif
+  return GZ_OK;
+}
+// The ingest kernel on `stream`: img (w x h) -> rgb [h][w][3] and, with lin != nullptr, the three linear planes.
+static void launch_ingest(hipStream_t stream, const gz_device_image* img, int w, int h, uint8_t* rgb, const float* lut,
+                          float* lin, int pitch, size_t pstride) {
+  const size_t elem = ingest_elem_size(img->dtype);
+  const long long sy = img->stride_y, sx = img->stride_x, sc = img->stride_c;
+  const int wide = ingest_wide_mode(img->data, elem, sy, sx, sc);
+  const int per_lane = (int)(16 / elem);
+  const dim3 grid((unsigned)(((size_t)gz_div_up(w, per_lane) * h + 255) / 256)), block(256);
+  switch (img->dtype) {
+    case GZ_DT_U8:
+      GZ_LAUNCH((k_ingest_rgb<uint8_t>), grid, block, stream, (const uint8_t*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
+      break;
+    case GZ_DT_F32:
+      GZ_LAUNCH((k_ingest_rgb<float>), grid, block, stream, (const float*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
+      break;
+    case GZ_DT_F16:
+      GZ_LAUNCH((k_ingest_rgb<ingest_f16>), grid, block, stream, (const ingest_f16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
+      break;
+    default:
+      GZ_LAUNCH((k_ingest_rgb<ingest_bf16>), grid, block, stream, (const ingest_bf16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
+      break;
+  }
+}
+
+static int set_rgb_device(gz_ctx* c, const gz_device_image* img);
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_image* img, float target, int* err);
 gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
   int prev = -1;
   if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  gz_ctx* c = create_context(device, w, h, rgb, target, err);
+  gz_ctx* c = create_context(device, w, h, rgb, nullptr, target, err);
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
   return c;
 }
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
+gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) {
+  if (check_device_image(img, w, h) != GZ_OK) {   // (before any device call)
+    if (err) *err = GZ_E_ARG;
+    return nullptr;
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  gz_ctx* c = create_context(device, w, h, nullptr, img, target, err);
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+  return c;
+}
+// The original from host pixels (rgb) or from a device-resident image (img, checked by the caller): one of the two.
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_image* img, float target, int* err) {
   int dummy;
   if (!err) err = &dummy;
   *err = GZ_OK;
-  if (!rgb || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
+  if ((!rgb && !img) || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
   // coefficient positions (3 x blocks x 64) and candidate offsets (blocks x 189) are 32-bit
   // on both sides of the ABI: 11.18 M blocks = 715 MPix is the largest image (tested: 268 MPix)
   if ((uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8) * 192u > 0x7fffffffull) { *err = GZ_E_ARG; return nullptr; }
@@ -140,6 +230,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, floa
     *err = GZ_E_NO_DEVICE;
     return nullptr;
   }
+  if (img && check_device_pointer(device, img, w, h, nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
   gz_ctx* c = new gz_ctx;
   c->device = device;
   c->w = w; c->h = h;
@@ -221,11 +312,26 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, floa
     if (c->blur[b].r != kBlurSpecs[b].r) return fail(GZ_E_STATE);
   }
   {
-    const int rc = gz_set_rgb(c, rgb);
+    const int rc = img ? set_rgb_device(c, img) : gz_set_rgb(c, rgb);
     if (rc != GZ_OK) return fail(rc);
   }
 #undef CHK0
   return c;
+}
+
+// What follows the original's arrival in d_rgb and lin[], from the host or from the device:
+// pi0_ = SeparateFrequencies(OpsinDynamicsImage(LinearRgb(rgb))), the original's half of every Compare's DiffPrecompute,
+// and the wait for all of it.
+static int original_from_lin(gz_ctx* c) {
+  TRY(stage_opsin(c, c->stream));
+  TRY(stage_separate(c, chain_streams(c, false), &c->pi0));
+  {
+    MaskIn in0[2];
+    mask_in_psycho(c->pi0, in0);
+    TRY(stage_mask_sup(c, c->stream, in0, c->sup0));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GZ_OK;
 }
 
 int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
@@ -234,20 +340,33 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   c->lin_is_cand = c->xyb_is_cand = false;   // (lin[] takes the original)
   c->have_block_mask = c->have_distmap = false;   // (StartBlockComparisons' mask and the map belong to the old one)
   HIPCHK(c, hipMemcpyAsync(c->d_rgb, rgb, (size_t)3 * c->w * c->h, hipMemcpyHostToDevice, c->stream));
-  // pi0_ = SeparateFrequencies(OpsinDynamicsImage(LinearRgb(rgb)))
   dim3 grid(gz_div_up(c->w, 256), c->h);
   GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), c->stream, c->d_rgb, c->w, c->h, c->pitch,
             c->plane, c->d_srgb_lut, c->lin[0]);
   KCHK(c);
-  TRY(stage_opsin(c, c->stream));
-  TRY(stage_separate(c, chain_streams(c, false), &c->pi0));
-  {  // the original's half of every Compare's DiffPrecompute
-    MaskIn in0[2];
-    mask_in_psycho(c->pi0, in0);
-    TRY(stage_mask_sup(c, c->stream, in0, c->sup0));
+  return original_from_lin(c);
+}
+
+// (the context's device is current, img has passed check_device_image and check_device_pointer)
+static int set_rgb_device(gz_ctx* c, const gz_device_image* img) {
+  c->lin_is_cand = c->xyb_is_cand = false;
+  c->have_block_mask = c->have_distmap = false;
+  if (img->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
+    if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
+    HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)img->producer_stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GZ_OK;
+  launch_ingest(c->stream, img, c->w, c->h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+  KCHK(c);
+  return original_from_lin(c);   // (its synchronise: the source is read when the call returns)
+}
+
+int gz_set_rgb_device(gz_ctx* c, const gz_device_image* img) {
+  if (!c) return GZ_E_ARG;
+  if (check_device_image(img, c->w, c->h) != GZ_OK) return GZ_E_ARG;
+  DeviceScope ds_(c);
+  if (const int rc = check_device_pointer(c->device, img, c->w, c->h, &c->err)) return rc;
+  return set_rgb_device(c, img);
 }
 
 void gz_destroy(gz_ctx* c) {

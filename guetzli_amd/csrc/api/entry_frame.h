@@ -43,6 +43,27 @@ int gz_encode_rgb_only(int device, const uint8_t* rgb, int w, int h, int16_t* co
   return GZ_OK;
 }
 
+int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out) {
+  if (!host_rgb_out || check_device_image(img, w, h) != GZ_OK) return GZ_E_ARG;
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  if (check_device_pointer(device, img, w, h, nullptr) != GZ_OK) return GZ_E_ARG;
+  DevBuf drgb;
+  if (!drgb.alloc((size_t)3 * w * h)) return GZ_E_NOMEM;
+  hipEvent_t ev = nullptr;
+  if (img->producer_stream) {   // the null stream below waits for the producer on the device
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return GZ_E_HIP;
+    const bool ok = hipEventRecord(ev, (hipStream_t)img->producer_stream) == hipSuccess &&
+                    hipStreamWaitEvent((hipStream_t)0, ev, 0) == hipSuccess;
+    if (!ok) { (void)hipEventDestroy(ev); return GZ_E_HIP; }
+  }
+  launch_ingest((hipStream_t)0, img, w, h, (uint8_t*)drgb.p, nullptr, nullptr, w, 0);
+  const bool launched = hipGetLastError() == hipSuccess;
+  // (a blocking copy on the null stream: behind the kernel, and complete when it returns)
+  const bool copied = launched && hipMemcpy(host_rgb_out, drgb.p, (size_t)3 * w * h, hipMemcpyDeviceToHost) == hipSuccess;
+  if (ev) (void)hipEventDestroy(ev);
+  return copied ? GZ_OK : GZ_E_HIP;
+}
+
 int gz_dct_double_blocks(int device, double* blocks, int n, int inverse) {
   if (!blocks || n <= 0) return GZ_E_ARG;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;

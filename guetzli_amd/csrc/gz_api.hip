@@ -35,6 +35,7 @@
 #include "gz_kernels_silver.h"
 #include "gz_kernels_order.h"
 #include "gz_kernels_rank.h"
+#include "gz_kernels_ingest.h"
 #include "gz_host_weights.h"
 #include "order_tables_generated.h"   // host-side csf/bias of order.inc
 

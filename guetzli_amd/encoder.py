@@ -7,6 +7,8 @@ import os
 
 import numpy as np
 
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, device_image
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
 
@@ -45,6 +47,9 @@ class HostLibrary:
         self.lib.gzh_process_params.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_double,
                                                 C.c_float, C.c_void_p, C.c_void_p, C.c_long,
                                                 C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+        self.lib.gzh_process_device.restype = C.c_long
+        self.lib.gzh_process_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_void_p,
+                                                C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long]
         self.lib.gzh_write_jpeg_factor.restype = C.c_long
         self.lib.gzh_write_jpeg_factor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_int, C.c_void_p, C.c_long]
@@ -64,8 +69,10 @@ class HostLibrary:
 
     def _process(self, data, w, h, quality, target, device, clear_metadata, try_420, force_420,
                  use_silver_screen, lookahead, new_model, want_trace):
-        """gzh_process_params with a buffer that grows to what the library asks for."""
+        """gzh_process_params -- or, for a capi.GzDeviceImage, gzh_process_device -- with a buffer that grows to
+        what the library asks for."""
         is_jpeg = isinstance(data, (bytes, bytearray))
+        on_device = not is_jpeg and not isinstance(data, np.ndarray)
         buf = np.frombuffer(data, np.uint8) if is_jpeg else data
         if is_jpeg:
             # from the frame header's dimensions (a heavily compressed input re-encoded at a high
@@ -82,10 +89,13 @@ class HostLibrary:
         tm = C.create_string_buffer(1 << 12)
         for _ in range(2):
             out = np.empty(cap, np.uint8)
-            n = self.lib.gzh_process_params(buf.ctypes.data, len(data) if is_jpeg else -1, w, h,
-                                            -1.0 if target is not None else float(quality),
-                                            float(target or 0.0), ip, out.ctypes.data, cap,
-                                            tr, len(tr) if tr else 0, tm, len(tm))
+            qt = (-1.0 if target is not None else float(quality), float(target or 0.0))
+            if on_device:
+                n = self.lib.gzh_process_device(C.addressof(data), w, h, *qt, ip, out.ctypes.data, cap,
+                                                tr, len(tr) if tr else 0, tm, len(tm))
+            else:
+                n = self.lib.gzh_process_params(buf.ctypes.data, len(data) if is_jpeg else -1, w, h, *qt, ip,
+                                                out.ctypes.data, cap, tr, len(tr) if tr else 0, tm, len(tm))
             if n < 0:
                 raise RuntimeError("guetzli_amd.Process failed (see stderr)" if n == -1 else
                                    "guetzli_amd.Process raised a C++ exception (see stderr)")
@@ -114,6 +124,18 @@ class HostLibrary:
         h, w, ch = rgb.shape
         assert ch == 3
         return self._process(rgb, w, h, quality, target, device, True, try_420, force_420,
+                             use_silver_screen, lookahead, new_model, want_trace)
+
+    def process_device(self, ptr, w, h, dtype, strides, stream=0, quality=95.0, target=None, device=0,
+                       want_trace=False, try_420=False, force_420=False, use_silver_screen=False, lookahead=3,
+                       new_model=True):
+        """guetzli_amd::Process(params, stats, DeviceImage, w, h, &out): the raw form.  ptr = address, in the memory of
+        GPU `device`, of element (0, 0, 0) of a w x h x 3 image; dtype = "uint8" | "float32" | "float16" | "bfloat16"
+        (or a GZ_DT_* code); strides = (y, x, c) in elements, each >= 0; stream = the hipStream_t whose work produced
+        the data (0: nothing to wait for).  Floats are [0, 1]: byte = rint(clamp(x * 255, 0, 255)).  Returns what
+        process() returns."""
+        image = device_image(ptr, DTYPE_CODES.get(dtype, dtype), strides, stream)
+        return self._process(image, w, h, quality, target, device, True, try_420, force_420,
                              use_silver_screen, lookahead, new_model, want_trace)
 
     def read_png(self, data):
@@ -187,8 +209,124 @@ def load_host():
     return _default
 
 
-def process(rgb, quality=95.0, **kw):
-    return load_host().process(rgb, quality=quality, **kw)
+DTYPE_CODES = {"uint8": GZ_DT_U8, "float32": GZ_DT_F32, "float16": GZ_DT_F16, "bfloat16": GZ_DT_BF16}
+
+
+def is_device_resident(x):
+    """A torch tensor on a GPU, or any object that exports __cuda_array_interface__."""
+    return bool(getattr(x, "is_cuda", False)) or hasattr(x, "__cuda_array_interface__")
+
+
+def _layout_strides(shape, strides, layout):
+    """(w, h, (stride_y, stride_x, stride_c)) of an image of `shape` with element `strides`: 2-D is grey (the one
+    value for all three channels), 3-D is "HWC" or "CHW" -- layout=None takes whichever of the first / last
+    dimension is 3 and refuses a shape where both are."""
+    if len(shape) == 2:
+        (h, w), (sy, sx) = shape, strides
+        return w, h, (sy, sx, 0)
+    if len(shape) != 3:
+        raise ValueError(f"an image has 2 or 3 dimensions, not {len(shape)}")
+    if layout is None:
+        first, last = shape[0] == 3, shape[2] == 3
+        if first and last:
+            raise ValueError(f"shape {tuple(shape)} is ambiguous: say layout='HWC' or layout='CHW'")
+        if not first and not last:
+            raise ValueError(f"shape {tuple(shape)}: neither the first nor the last dimension is 3")
+        layout = "CHW" if first else "HWC"
+    if layout == "HWC":
+        (h, w, ch), (sy, sx, sc) = shape, strides
+    elif layout == "CHW":
+        (ch, h, w), (sc, sy, sx) = shape, strides
+    else:
+        raise ValueError(f"layout {layout!r}: 'HWC', 'CHW' or None")
+    if ch != 3:
+        raise ValueError(f"shape {tuple(shape)} has {ch} channels in layout {layout}, not 3")
+    return w, h, (sy, sx, sc)
+
+
+def _device_source(x, layout, device):
+    """(ptr, w, h, dtype name, element strides, producer stream, device ordinal) of a device-resident image."""
+    if getattr(x, "is_cuda", False):   # a torch tensor
+        import torch
+        name = str(x.dtype).replace("torch.", "")
+        if name not in DTYPE_CODES:
+            raise TypeError(f"dtype {x.dtype}: uint8, float32, float16 or bfloat16")
+        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        if device is not None and device != ordinal:
+            raise ValueError(f"the tensor lives on device {ordinal}, device={device} was asked for")
+        w, h, strides = _layout_strides(tuple(x.shape), tuple(x.stride()), layout)
+        return x.data_ptr(), w, h, name, strides, torch.cuda.current_stream(x.device).cuda_stream, ordinal
+    cai = x.__cuda_array_interface__
+    dt = np.dtype(cai["typestr"])
+    if dt.name not in DTYPE_CODES:   # (numpy has no bfloat16: such arrays come as torch tensors)
+        raise TypeError(f"dtype {dt}: uint8, float32 or float16")
+    shape = tuple(cai["shape"])
+    if cai.get("strides") is None:
+        byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
+    else:
+        byte_strides = tuple(cai["strides"])
+    if any(b % dt.itemsize for b in byte_strides):
+        raise ValueError("strides that are no multiple of the element size")
+    w, h, strides = _layout_strides(shape, tuple(b // dt.itemsize for b in byte_strides), layout)
+    # the interface's stream: None / absent = nothing to wait for; 1 = the legacy default stream, with which the
+    # context's (blocking) streams synchronise by themselves: nothing to hand over; 2 = the per-thread default stream,
+    # which orders itself against nobody: handed over as it is -- it is hipStreamPerThread's handle too, and it names the
+    # stream of the thread that makes the call (process_many, whose calls run on other threads, refuses it)
+    stream = cai.get("stream") or 0
+    if stream == 1:
+        stream = 0
+    return cai["data"][0], w, h, dt.name, strides, stream, 0 if device is None else device
+
+
+PER_THREAD_STREAM = 2   # hipStreamPerThread: the default stream of whichever thread uses the handle
+
+
+class _Job:
+    """One encode whose thread-dependent part is done: run(**params) -> (jpeg_bytes, info) on any thread."""
+
+    def __init__(self, run, producer=0, keep=None):
+        self.run, self.producer, self.keep = run, producer, keep   # keep: the object that owns the device memory
+
+
+def _prepared(rgb, layout, device, stream):
+    """What of an encode must happen in the CALLER's thread -- torch's current stream is a property of the thread."""
+    if not is_device_resident(rgb):
+        if layout not in (None, "HWC"):
+            raise ValueError("host pixels are [h][w][3]")
+        if stream is not None:
+            raise ValueError("stream= goes with device-resident pixels")
+        return _Job(lambda **kw: load_host().process(rgb, device=0 if device is None else device, **kw))
+    ptr, w, h, dtype, strides, producer, ordinal = _device_source(rgb, layout, device)
+    if stream is not None:
+        producer = int(stream)
+    if any(s < 0 for s in strides):
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    return _Job(lambda **kw: load_host().process_device(ptr, w, h, dtype, strides, stream=producer, device=ordinal, **kw),
+                producer, rgb)
+
+
+def process(rgb, quality=95.0, layout=None, device=None, stream=None, **kw):
+    """guetzli::Process of an image -> (jpeg_bytes, info).  `rgb` on the host: anything numpy turns into uint8
+    [h][w][3].  `rgb` on the GPU -- a torch tensor with is_cuda, or an object with __cuda_array_interface__ -- is
+    encoded where it is: uint8, or float32 / float16 / bfloat16 in [0, 1]; "HWC" or "CHW" (layout=None: whichever of
+    the first / last dimension is 3), any strides >= 0, 2-D = grey; on the tensor's device (an explicit device= must
+    agree), behind the work enqueued so far on the producer's stream: the calling thread's current torch stream on
+    that device, the interface's `stream` entry, or stream= (a hipStream_t handle; 0: nothing to wait for)."""
+    return _prepared(rgb, layout, device, stream).run(quality=quality, **kw)
+
+
+def process_many(batch, workers=4, layout=None, device=None, stream=None, **kw):
+    """A batch of images with `workers` of them in flight on one GPU (batch.encode_concurrent): a 4-D tensor
+    [N,3,H,W] / [N,H,W,3] or a list of images, each as process() takes them.  Returns [(jpeg_bytes, info)] in order.
+    The encodes run on worker threads, but every image's producer stream is the one process() would have taken in
+    the CALLING thread, here and now: a batch made under `with torch.cuda.stream(s)` is encoded behind s.  (A
+    __cuda_array_interface__ stream of 2, the per-thread default stream, is refused: it names another stream there.)"""
+    from .batch import encode_concurrent
+    jobs = [_prepared(batch[i], layout, device, stream) for i in range(len(batch))]
+    if any(j.producer == PER_THREAD_STREAM for j in jobs):
+        raise ValueError("a per-thread default stream cannot be waited for from the worker threads: synchronise it and "
+                         "say stream=0, or encode with process()")
+    return encode_concurrent(jobs, lambda job: job.run(**kw), workers=workers)
 
 
 def read_png(data):

@@ -160,6 +160,7 @@ class Encoder {
   Encoder(const Params& p, ProcessStats* s);
   ~Encoder();
   bool Run(const std::vector<uint8_t>& rgb, int w, int h, std::string* out);
+  bool RunDevice(const DeviceImage& image, int w, int h, std::string* out);
   bool RunJpeg(const std::string& jpeg_data, std::string* out);
 
  private:
@@ -171,6 +172,8 @@ class Encoder {
   void SetGeometry(int w, int h, int factor);
   void SetFrame(int factor);
   bool WriteTooSmall(const Frame& f, std::string* out);
+  bool RunTooSmall(const uint8_t* rgb, int w, int h, std::string* out);   // w or h < 32, from host pixels
+  bool RunFromContext(const Stopwatch& start, std::string* out);          // ctx_ holds the original's pixels
   int CodeRefreshThreads() const;
   bool Search(const QuantMatrix first_q, const Stopwatch& start, std::string* out);   // ProcessJpegData from :826 on
   const char* FrameStr() const { return fac_ == 2 ? "f112222" : "f111111"; }   // OutputImage::FrameTypeStr

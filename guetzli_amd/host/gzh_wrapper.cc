@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <exception>
 
+#include "../../include/guetzli_amd.h"
 #include "jpeg_reader.h"
 #include "jpeg_writer.h"
 #include "parallel.h"
@@ -35,14 +36,7 @@ static void CopyText(const std::string& s, char* dst, long cap) {
   dst[n] = 0;
 }
 
-// guetzli::Process with every field of Params.  jpeg_len < 0: `data` is packed RGB of w x h,
-// otherwise JPEG bytes.  quality < 0: `target` is the butteraugli target directly.
-// iparams: device, clear_metadata, try_420, force_420, use_silver_screen,
-// zeroing_greedy_lookahead, new_zeroing_model.
-long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double quality,
-                        float target, const int* iparams, uint8_t* out, long cap, char* trace,
-                        long trace_cap, char* timers, long timers_cap) {
-  GZH_GUARD_BEGIN
+static guetzli_amd::Params ParamsFrom(double quality, float target, const int* iparams) {
   guetzli_amd::Params params;
   params.butteraugli_target =
       quality >= 0 ? (float)guetzli_amd::ButteraugliScoreForQuality(quality) : target;
@@ -53,20 +47,12 @@ long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double
   params.use_silver_screen = iparams[4] != 0;
   params.zeroing_greedy_lookahead = iparams[5];
   params.new_zeroing_model = iparams[6] != 0;
-  guetzli_amd::ProcessStats stats;
-  std::string dbg;
-  if (trace) stats.debug_output = &dbg;
-  std::string jpg;
-  bool ok;
-  if (jpeg_len < 0) {
-    static thread_local std::vector<uint8_t> v;   // Process takes a vector, as the reference's does
-    v.assign(data, data + (size_t)3 * w * h);
-    ok = guetzli_amd::Process(params, &stats, v, w, h, &jpg);
-  } else {
-    std::string in((const char*)data, (size_t)jpeg_len);
-    ok = guetzli_amd::Process(params, &stats, in, &jpg);
-  }
-  if (!ok) return -1;
+  return params;
+}
+
+// What a finished Process hands back: the JPEG if it fits, the trace, the timers and counters as "k=v;#k=n;".
+static long Deliver(const std::string& jpg, const std::string& dbg, const guetzli_amd::ProcessStats& stats,
+                    uint8_t* out, long cap, char* trace, long trace_cap, char* timers, long timers_cap) {
   if ((long)jpg.size() <= cap) memcpy(out, jpg.data(), jpg.size());
   CopyText(dbg, trace, trace_cap);
   if (timers && timers_cap > 0) {
@@ -84,6 +70,57 @@ long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double
     CopyText(t, timers, timers_cap);
   }
   return (long)jpg.size();
+}
+
+// guetzli::Process with every field of Params.  jpeg_len < 0: `data` is packed RGB of w x h,
+// otherwise JPEG bytes.  quality < 0: `target` is the butteraugli target directly.
+// iparams: device, clear_metadata, try_420, force_420, use_silver_screen,
+// zeroing_greedy_lookahead, new_zeroing_model.
+long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double quality,
+                        float target, const int* iparams, uint8_t* out, long cap, char* trace,
+                        long trace_cap, char* timers, long timers_cap) {
+  GZH_GUARD_BEGIN
+  const guetzli_amd::Params params = ParamsFrom(quality, target, iparams);
+  guetzli_amd::ProcessStats stats;
+  std::string dbg;
+  if (trace) stats.debug_output = &dbg;
+  std::string jpg;
+  bool ok;
+  if (jpeg_len < 0) {
+    static thread_local std::vector<uint8_t> v;   // Process takes a vector, as the reference's does
+    v.assign(data, data + (size_t)3 * w * h);
+    ok = guetzli_amd::Process(params, &stats, v, w, h, &jpg);
+  } else {
+    std::string in((const char*)data, (size_t)jpeg_len);
+    ok = guetzli_amd::Process(params, &stats, in, &jpg);
+  }
+  if (!ok) return -1;
+  return Deliver(jpg, dbg, stats, out, cap, trace, trace_cap, timers, timers_cap);
+  GZH_GUARD_END
+}
+
+// Process(params, stats, DeviceImage, w, h, &out): `image` is a gz_device_image (include/guetzli_amd.h) on GPU
+// iparams[0]; the other arguments as gzh_process_params'.
+long gzh_process_device(const gz_device_image* image, int w, int h, double quality, float target,
+                        const int* iparams, uint8_t* out, long cap, char* trace, long trace_cap,
+                        char* timers, long timers_cap) {
+  GZH_GUARD_BEGIN
+  if (!image || image->struct_size != (int)sizeof(gz_device_image)) {
+    fprintf(stderr, "guetzli_amd: gzh_process_device: not a gz_device_image of this library\n");
+    return -1;
+  }
+  const guetzli_amd::Params params = ParamsFrom(quality, target, iparams);
+  guetzli_amd::DeviceImage im;
+  im.dtype = image->dtype;
+  im.data = image->data;
+  im.stride_y = image->stride_y; im.stride_x = image->stride_x; im.stride_c = image->stride_c;
+  im.producer_stream = image->producer_stream;
+  guetzli_amd::ProcessStats stats;
+  std::string dbg;
+  if (trace) stats.debug_output = &dbg;
+  std::string jpg;
+  if (!guetzli_amd::Process(params, &stats, im, w, h, &jpg)) return -1;
+  return Deliver(jpg, dbg, stats, out, cap, trace, trace_cap, timers, timers_cap);
   GZH_GUARD_END
 }
 

@@ -12,6 +12,9 @@
 // it was when they were written (the recorded-session replay of the tests).  Such a library still loads; asking it
 // for use_silver_screen fails below, loudly -- there is no host path behind this call.
 extern "C" int gz_downsample_silver(gz_ctx* ctx, int16_t* coeffs_out, uint64_t counters[2]) __attribute__((weak));
+// ... and so do the device-input entries: a stand-in without them refuses a DeviceImage, it has nowhere to read one from.
+extern "C" gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) __attribute__((weak));
+extern "C" int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -391,31 +394,18 @@ bool Encoder::RunJpeg(const std::string& data, std::string* out) {
   return Search(q_in_, start, out);
 }
 
-bool Encoder::Run(const std::vector<uint8_t>& rgb, int w, int h, std::string* out) {
-  const Stopwatch start;
-  if (TargetRefused()) return false;
-  if (w < 0 || w >= 1 << 16 || h < 0 || h >= 1 << 16 || rgb.size() != (size_t)3 * w * h) {
-    fprintf(stderr, "Could not create jpg data from rgb pixels\n");   // EncodeRGBToJpeg failed
-    return false;
-  }
-  SetGeometry(w, h, 1);
-  if (w < 32 || h < 32) {
-    // no butteraugli (processor.cc:832-838, :940): the reference emits
-    // the unquantised JPEG of EncodeRGBToJpeg; the forward transform runs on the device.
-    if (w < 1 || h < 1) {
-      fprintf(stderr, "Could not create jpg data from rgb pixels\n");
-      return false;
-    }
-    sc_.orig.resize((size_t)3 * nb_ * 64);
-    const int rc0 = gz_encode_rgb_only(params_.device, rgb.data(), w, h, sc_.orig.data());
-    if (rc0 != GZ_OK) return Fail("gz_encode_rgb_only", rc0);
-    Frame f;
-    FrameFromOriginal(sc_.orig.data(), w, h, &f);
-    return WriteTooSmall(f, out);
-  }
-  int err = 0;
-  ctx_ = gz_create(params_.device, w, h, rgb.data(), params_.butteraugli_target, &err);
-  if (!ctx_) return Fail("gz_create", err);
+// no butteraugli (processor.cc:832-838, :940): the reference emits
+// the unquantised JPEG of EncodeRGBToJpeg; the forward transform runs on the device.
+bool Encoder::RunTooSmall(const uint8_t* rgb, int w, int h, std::string* out) {
+  sc_.orig.resize((size_t)3 * nb_ * 64);
+  const int rc0 = gz_encode_rgb_only(params_.device, rgb, w, h, sc_.orig.data());
+  if (rc0 != GZ_OK) return Fail("gz_encode_rgb_only", rc0);
+  Frame f;
+  FrameFromOriginal(sc_.orig.data(), w, h, &f);
+  return WriteTooSmall(f, out);
+}
+
+bool Encoder::RunFromContext(const Stopwatch& start, std::string* out) {
   sc_.orig.resize((size_t)3 * nb_ * 64);
   sc_.img.resize(sc_.orig.size());
   int rc = gz_encode_rgb(ctx_, sc_.orig.data());
@@ -425,12 +415,69 @@ bool Encoder::Run(const std::vector<uint8_t>& rgb, int w, int h, std::string* ou
   return Search(ones, start, out);
 }
 
+bool Encoder::Run(const std::vector<uint8_t>& rgb, int w, int h, std::string* out) {
+  const Stopwatch start;
+  if (TargetRefused()) return false;
+  if (w < 0 || w >= 1 << 16 || h < 0 || h >= 1 << 16 || rgb.size() != (size_t)3 * w * h) {
+    fprintf(stderr, "Could not create jpg data from rgb pixels\n");   // EncodeRGBToJpeg failed
+    return false;
+  }
+  SetGeometry(w, h, 1);
+  if (w < 32 || h < 32) {
+    if (w < 1 || h < 1) {
+      fprintf(stderr, "Could not create jpg data from rgb pixels\n");
+      return false;
+    }
+    return RunTooSmall(rgb.data(), w, h, out);
+  }
+  int err = 0;
+  ctx_ = gz_create(params_.device, w, h, rgb.data(), params_.butteraugli_target, &err);
+  if (!ctx_) return Fail("gz_create", err);
+  return RunFromContext(start, out);
+}
+
+bool Encoder::RunDevice(const DeviceImage& image, int w, int h, std::string* out) {
+  const Stopwatch start;
+  if (TargetRefused()) return false;
+  if (w < 1 || w >= 1 << 16 || h < 1 || h >= 1 << 16 || image.data == nullptr) {
+    fprintf(stderr, "Could not create jpg data from rgb pixels\n");
+    return false;
+  }
+  if (!gz_create_from_device || !gz_pack_rgb_device) return Fail("device-resident input (not in this device library)", GZ_E_STATE);
+  gz_device_image img;
+  memset(&img, 0, sizeof(img));
+  img.struct_size = (int)sizeof(img);
+  img.dtype = image.dtype;
+  img.data = image.data;
+  img.stride_y = image.stride_y; img.stride_x = image.stride_x; img.stride_c = image.stride_c;
+  img.producer_stream = image.producer_stream;
+  SetGeometry(w, h, 1);
+  if (w < 32 || h < 32) {   // too small for a context: the kernel's bytes come to the host, the rest is Run's
+    std::vector<uint8_t> rgb((size_t)3 * w * h);
+    const int rc0 = gz_pack_rgb_device(params_.device, &img, w, h, rgb.data());
+    if (rc0 != GZ_OK) return Fail("gz_pack_rgb_device", rc0);
+    return RunTooSmall(rgb.data(), w, h, out);
+  }
+  int err = 0;
+  ctx_ = gz_create_from_device(params_.device, w, h, &img, params_.butteraugli_target, &err);
+  if (!ctx_) return Fail("gz_create_from_device", err);
+  return RunFromContext(start, out);
+}
+
 bool Process(const Params& params, ProcessStats* stats, const std::vector<uint8_t>& rgb, int w,
              int h, std::string* out) {
   ProcessStats dummy;
   if (stats == nullptr) stats = &dummy;
   Encoder enc(params, stats);
   return enc.Run(rgb, w, h, out);
+}
+
+bool Process(const Params& params, ProcessStats* stats, const DeviceImage& image, int w, int h,
+             std::string* out) {
+  ProcessStats dummy;
+  if (stats == nullptr) stats = &dummy;
+  Encoder enc(params, stats);
+  return enc.RunDevice(image, w, h, out);
 }
 
 bool Process(const Params& params, ProcessStats* stats, const std::string& jpeg_data,

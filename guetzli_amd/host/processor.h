@@ -46,6 +46,16 @@ struct ProcessStats {                 // guetzli::ProcessStats, stats.h:34-41
   std::map<std::string, double> timers;
 };
 
+// gz_device_image of include/guetzli_amd.h: a w x h x 3 image that already lives in the memory of GPU
+// Params::device.  Element (y, x, c) is data[y*stride_y + x*stride_x + c*stride_c], strides in elements, >= 0.
+struct DeviceImage {
+  enum Dtype { kU8 = 0, kF32 = 1, kF16 = 2, kBF16 = 3 };   // GZ_DT_*
+  int dtype = kU8;
+  const void* data = nullptr;         // device address of element (0, 0, 0)
+  int64_t stride_y = 0, stride_x = 0, stride_c = 0;
+  void* producer_stream = nullptr;    // hipStream_t whose work writes the data; nullptr: none to wait for
+};
+
 double ButteraugliScoreForQuality(double quality);                       // quality.cc:78-85
 double ScoreJPEG(double butteraugli_distance, int size, double target);  // score.cc:23-41
 
@@ -53,6 +63,12 @@ double ScoreJPEG(double butteraugli_distance, int size, double target);  // scor
 // (packed 8-bit sRGB, w*h*3).  Returns false (message on stderr) on failure.
 bool Process(const Params& params, ProcessStats* stats, const std::vector<uint8_t>& rgb,
              int w, int h, std::string* out);
+
+// The same from pixels on the GPU (floats: [0, 1] -> rint(x * 255), clamped; include/guetzli_amd.h has the rule):
+// nothing goes through host memory but, for w or h < 32, the bytes of the tiny image itself.  Same refusals and
+// messages as above; memory that GPU params.device cannot read is a failure, not a fault.
+bool Process(const Params& params, ProcessStats* stats, const DeviceImage& image, int w, int h,
+             std::string* out);
 
 // The same from an existing JPEG (guetzli::Process(params, stats, jpeg_data, &out),
 // processor.h:39-41): the input is parsed on the host (jpeg_reader.h), its coefficients become

@@ -50,7 +50,10 @@ extern "C" {
 typedef struct gz_ctx gz_ctx;
 
 /* Library / device ------------------------------------------------------------ */
-int gz_abi_version(void);                 /* currently 6 (5 without the two experiment fields of gz_config) */
+int gz_abi_version(void);                 /* currently 6 (5 without the two experiment fields of gz_config); the
+                                             device-input entries (gz_device_image, gz_create_from_device,
+                                             gz_set_rgb_device, gz_pack_rgb_device) were ADDED to version 6: no
+                                             existing declaration, struct or call sequence changed, so the number stays */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -118,6 +121,43 @@ void gz_destroy(gz_ctx* ctx);
  * DecodeJpegToRGB(jpg) (jpeg_data_decoder.cc:45-54) -- an IDCT of the input's coefficients
  * that the context itself computes (gz_set_orig_coeffs, gz_quantize(NULL), gz_reconstruct). */
 int gz_set_rgb(gz_ctx* ctx, const uint8_t* rgb);
+
+/* Device-resident input ----------------------------------------------------------
+ * The original as a strided image that already lives in DEVICE memory (a decoder's, a resize's or a model's
+ * output): element (y, x, c) of the w x h x 3 image is data[y*stride_y + x*stride_x + c*stride_c], strides in
+ * ELEMENTS, each >= 0 -- HWC, CHW, cropped views (a row pitch larger than the row), grey broadcast over the
+ * channels (stride_c = 0), any element alignment of the base.  One kernel converts it to the context's packed 8-bit
+ * image and its linear planes; nothing goes through host memory.
+ * Byte of an element: integers pass through.  A float x becomes rint(clamp(float32(x) * 255.0f, 0, 255)) -- one f32
+ * multiplication, NaN -> 0, below 0 (and -inf) -> 0, above 255 (and +inf) -> 255, round to nearest with ties to
+ * even -- so k/255 stored in any of the three float types comes back as k.
+ * Stream contract: producer_stream is the hipStream_t whose already enqueued work writes the data; the call records
+ * an event there and makes the context's stream wait for it (no host synchronisation of the producer).  NULL: there
+ * is nothing to wait for -- the data is complete, or its producer is the legacy default stream, with which the
+ * context's (blocking) streams synchronise by themselves.  The source is fully read when the call returns.
+ * The memory must be readable by the context's device (device memory of that device, managed memory, or page-locked
+ * host memory mapped at the same address): anything else -- an ordinary host pointer -- is GZ_E_ARG, not a fault. */
+#define GZ_DT_U8 0
+#define GZ_DT_F32 1
+#define GZ_DT_F16 2
+#define GZ_DT_BF16 3
+typedef struct gz_device_image {
+  int struct_size;            /* sizeof(gz_device_image) */
+  int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 */
+  const void* data;           /* device address of element (0,0,0) */
+  int64_t stride_y, stride_x, stride_c;   /* elements, >= 0 */
+  void* producer_stream;      /* hipStream_t whose work produced the data; NULL = none to wait for */
+} gz_device_image;
+/* gz_create with the ingest kernel in place of the upload: same limits on w and h, same ownership (all or nothing).
+ * GZ_E_ARG (before any device call): NULL img or data, a wrong struct_size, an unknown dtype, a negative stride, an
+ * extent whose last element offset does not fit 62 bits. */
+gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err);
+/* gz_set_rgb from such an image (the context's w and h). */
+int gz_set_rgb_device(gz_ctx* ctx, const gz_device_image* img);
+/* The conversion alone, without a context: img (w x h, 0 < w, h < 65536) -> host_rgb_out, packed uint8 w*h*3.  For
+ * images too small for a context (w or h < 32: gz_encode_rgb_only takes the bytes from there). */
+int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out);
+
 int gz_synchronize(gz_ctx* ctx);
 /* Run subsequent work of this context on an externally owned hipStream_t (e.g. torch's
  * current stream, so that torch.cuda.Event timing sees the kernels).  NULL restores the
