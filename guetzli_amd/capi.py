@@ -32,6 +32,7 @@ class GzConfig(C.Structure):
 
 
 GZ_DT_U8, GZ_DT_F32, GZ_DT_F16, GZ_DT_BF16 = 0, 1, 2, 3
+GZ_DT_U16 = 4   # gz_device_pixels only
 
 
 class GzDeviceImage(C.Structure):
@@ -45,6 +46,20 @@ def device_image(ptr, dtype, strides, stream=0):
     stream = the hipStream_t whose work produced the data (0: none to wait for)."""
     sy, sx, sc = (int(v) for v in strides)
     return GzDeviceImage(C.sizeof(GzDeviceImage), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None)
+
+
+class GzDevicePixels(C.Structure):
+    """gz_device_pixels of include/guetzli_amd.h: gz_device_image with GZ_DT_U16, an alpha pointer and a background."""
+    _fields_ = GzDeviceImage._fields_ + [("alpha", _P), ("background", C.c_uint8 * 4)]
+
+
+def device_pixels(ptr, dtype, strides, stream=0, alpha=0, background=(0, 0, 0)):
+    """A GzDevicePixels: as device_image, and alpha = device address of the alpha sample of pixel (0, 0) (0: opaque),
+    background = the bytes (r, g, b) the pixels are blended over."""
+    sy, sx, sc = (int(v) for v in strides)
+    r, g, b = (int(v) for v in background)
+    return GzDevicePixels(C.sizeof(GzDevicePixels), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None,
+                          int(alpha) or None, (C.c_uint8 * 4)(r, g, b, 0))
 
 
 # name -> (restype, argtypes); mirrors include/guetzli_amd.h one to one
@@ -64,6 +79,9 @@ SIGNATURES = {
     "gz_create_from_device": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
     "gz_set_rgb_device": (_I, [_P, _P]),
     "gz_pack_rgb_device": (_I, [_I, _P, _I, _I, _P]),
+    "gz_create_from_device_pixels": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
+    "gz_set_rgb_device_pixels": (_I, [_P, _P]),
+    "gz_pack_rgb_device_pixels": (_I, [_I, _P, _I, _I, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -307,9 +325,11 @@ class Library:
         return Context.from_device(self, image, w, h, target, device)
 
     def pack_rgb_device(self, image, w, h, device=0):
-        """gz_pack_rgb_device: the ingest kernel's bytes of `image` (device_image(...)) -> uint8 [h][w][3]."""
+        """gz_pack_rgb_device / gz_pack_rgb_device_pixels: the ingest kernel's bytes of `image` (device_image(...) /
+        device_pixels(...)) -> uint8 [h][w][3]."""
         out = np.zeros((h, w, 3), np.uint8)
-        self.check(self.lib.gz_pack_rgb_device(device, C.byref(image), w, h, _ptr(out)))
+        entry = self.lib.gz_pack_rgb_device_pixels if isinstance(image, GzDevicePixels) else self.lib.gz_pack_rgb_device
+        self.check(entry(device, C.byref(image), w, h, _ptr(out)))
         return out
 
 
@@ -330,14 +350,16 @@ class Context:
 
     @classmethod
     def from_device(cls, library, image, w, h, target, device=0):
-        """gz_create_from_device: the original is the device-resident `image` (device_image(...)).  The pixels stay
-        where they are: such a context has rgb = None (as one whose original set_rgb_device replaced)."""
+        """gz_create_from_device / gz_create_from_device_pixels: the original is the device-resident `image`
+        (device_image(...) / device_pixels(...)).  The pixels stay where they are: such a context has rgb = None (as
+        one whose original set_rgb_device replaced)."""
         self = cls.__new__(cls)
         self.L = library
         self.rgb = None
         self._set_geometry(w, h)
         err = C.c_int(0)
-        self.handle = library.lib.gz_create_from_device(device, w, h, C.byref(image), float(target), C.byref(err))
+        entry = library.lib.gz_create_from_device_pixels if isinstance(image, GzDevicePixels) else library.lib.gz_create_from_device
+        self.handle = entry(device, w, h, C.byref(image), float(target), C.byref(err))
         if not self.handle:
             library.check(err.value or -3)
         return self
@@ -395,9 +417,11 @@ class Context:
         self._chk(self.L.lib.gz_set_rgb(self.handle, _ptr(rgb)))
 
     def set_rgb_device(self, image):
-        """gz_set_rgb_device: the original replaced by the device-resident `image` (device_image(...), w x h)."""
+        """gz_set_rgb_device / gz_set_rgb_device_pixels: the original replaced by the device-resident `image`
+        (device_image(...) / device_pixels(...), w x h)."""
         self.rgb = None
-        self._chk(self.L.lib.gz_set_rgb_device(self.handle, C.byref(image)))
+        entry = self.L.lib.gz_set_rgb_device_pixels if isinstance(image, GzDevicePixels) else self.L.lib.gz_set_rgb_device
+        self._chk(entry(self.handle, C.byref(image)))
 
     def synchronize(self):
         self._chk(self.L.lib.gz_synchronize(self.handle))

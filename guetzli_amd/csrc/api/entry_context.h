@@ -121,12 +121,13 @@ const char* gz_last_error(const gz_ctx* ctx) { return ctx ? ctx->err.c_str() : "
 // ---- device-resident input (gz_kernels_ingest.h) ----
 static size_t ingest_elem_size(int dtype) { return dtype == GZ_DT_U8 ? 1 : dtype == GZ_DT_F32 ? 4 : 2; }
 // The arguments alone: no device call (the library answers these without a GPU).
-static int check_device_image(const gz_device_image* img, int w, int h) {
-  if (!img || img->struct_size != (int)sizeof(gz_device_image) || !img->data) return GZ_E_ARG;
-  if (img->dtype < GZ_DT_U8 || img->dtype > GZ_DT_BF16) return GZ_E_ARG;
+static int check_device_pixels(const gz_device_pixels* img, int w, int h) {
+  if (!img || img->struct_size != (int)sizeof(gz_device_pixels) || !img->data) return GZ_E_ARG;
+  if (img->dtype < GZ_DT_U8 || img->dtype > GZ_DT_U16) return GZ_E_ARG;
   if (img->stride_y < 0 || img->stride_x < 0 || img->stride_c < 0) return GZ_E_ARG;
   if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) return GZ_E_ARG;
   // the last element's offset (h-1) sy + (w-1) sx + 2 sc in 62 bits: every term is bounded before it is formed
+  // (alpha's last offset is (h-1) sy + (w-1) sx, the ty + tx below)
   const uint64_t lim = (1ull << 62) - 1;
   const uint64_t sy = (uint64_t)img->stride_y, sx = (uint64_t)img->stride_x, sc = (uint64_t)img->stride_c;
   if ((h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1)) || sc > lim / 2) return GZ_E_ARG;
@@ -134,32 +135,45 @@ static int check_device_image(const gz_device_image* img, int w, int h) {
   if (ty + tx > lim || ty + tx + tc > lim) return GZ_E_ARG;
   return GZ_OK;
 }
+// gz_device_image is gz_device_pixels without alpha: what the three older entries accept stays what it was (their
+// struct_size, no GZ_DT_U16), the rest is the code behind the newer ones.
+static int pixels_of_image(const gz_device_image* img, gz_device_pixels* px) {
+  if (!img || img->struct_size != (int)sizeof(gz_device_image) || img->dtype > GZ_DT_BF16) return GZ_E_ARG;
+  memset(px, 0, sizeof(*px));
+  px->struct_size = (int)sizeof(*px);
+  px->dtype = img->dtype;
+  px->data = img->data;
+  px->stride_y = img->stride_y; px->stride_x = img->stride_x; px->stride_c = img->stride_c;
+  px->producer_stream = img->producer_stream;
+  return GZ_OK;
+}
 // Where the memory lives: it must be readable by `device` (the current one).  An ordinary host pointer, memory of
 // another GPU or an extent that leaves its allocation is an argument error here, not a fault in the kernel.
-static int check_device_pointer(int device, const gz_device_image* img, int w, int h, std::string* why) {
+// `last` = the offset of the last element read from p, `what` = "data" or "alpha".
+static int check_device_range(int device, const void* p, uint64_t last, size_t elem, const char* what, std::string* why) {
 #ifndef GZ_EMU
+  const std::string name = std::string("device image: ") + what;
   hipPointerAttribute_t at;
   memset(&at, 0, sizeof(at));
-  if (hipPointerGetAttributes(&at, img->data) != hipSuccess) {
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
     (void)hipGetLastError();
-    if (why) *why = "gz_device_image.data is not memory the HIP runtime knows (a host pointer?)";
+    if (why) *why = name + " is not memory the HIP runtime knows (a host pointer?)";
     return GZ_E_ARG;
   }
   const bool readable = (at.type == hipMemoryTypeDevice && at.device == device) || at.type == hipMemoryTypeManaged ||
-                        (at.type == hipMemoryTypeHost && at.devicePointer == img->data);
+                        (at.type == hipMemoryTypeHost && at.devicePointer == p);
   if (!readable) {
-    if (why) *why = at.type == hipMemoryTypeDevice ? "gz_device_image.data lives on device " + std::to_string(at.device) + ", the context on " + std::to_string(device)
-                                                   : std::string("gz_device_image.data is not device-readable memory (a host pointer?)");
+    if (why) *why = at.type == hipMemoryTypeDevice ? name + " lives on device " + std::to_string(at.device) + ", the context on " + std::to_string(device)
+                                                   : name + " is not device-readable memory (a host pointer?)";
     return GZ_E_ARG;
   }
   if (at.type == hipMemoryTypeDevice) {
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)img->data) == hipSuccess) {
-      const uint64_t last = (uint64_t)img->stride_y * (uint64_t)(h - 1) + (uint64_t)img->stride_x * (uint64_t)(w - 1) + (uint64_t)img->stride_c * 2;
-      const uint64_t room = (uint64_t)((const char*)base + size - (const char*)img->data) / ingest_elem_size(img->dtype);
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
+      const uint64_t room = (uint64_t)((const char*)base + size - (const char*)p) / elem;
       if (last >= room) {
-        if (why) *why = "gz_device_image: the strides lead outside the allocation that holds data";
+        if (why) *why = name + ": the strides lead outside the allocation that holds it";
         return GZ_E_ARG;
       }
     } else {
@@ -167,18 +181,36 @@ static int check_device_pointer(int device, const gz_device_image* img, int w, i
     }
   }
 #else
-  (void)device; (void)img; (void)w; (void)h; (void)why;
+  (void)device; (void)p; (void)last; (void)elem; (void)what; (void)why;
 #endif
   return GZ_OK;
 }
+static int check_device_pointer(int device, const gz_device_pixels* img, int w, int h, std::string* why) {
+  const size_t elem = ingest_elem_size(img->dtype);
+  const uint64_t plane = (uint64_t)img->stride_y * (uint64_t)(h - 1) + (uint64_t)img->stride_x * (uint64_t)(w - 1);
+  if (const int rc = check_device_range(device, img->data, plane + (uint64_t)img->stride_c * 2, elem, "data", why)) return rc;
+  return img->alpha ? check_device_range(device, img->alpha, plane, elem, "alpha", why) : GZ_OK;
+}
 // The ingest kernel on `stream`: img (w x h) -> rgb [h][w][3] and, with lin != nullptr, the three linear planes.
-static void launch_ingest(hipStream_t stream, const gz_device_image* img, int w, int h, uint8_t* rgb, const float* lut,
+// Opaque pixels take k_ingest_rgb, pixels with alpha k_ingest_rgba: same grid, one launch either way.
+static void launch_ingest(hipStream_t stream, const gz_device_pixels* img, int w, int h, uint8_t* rgb, const float* lut,
                           float* lin, int pitch, size_t pstride) {
   const size_t elem = ingest_elem_size(img->dtype);
   const long long sy = img->stride_y, sx = img->stride_x, sc = img->stride_c;
-  const int wide = ingest_wide_mode(img->data, elem, sy, sx, sc);
   const int per_lane = (int)(16 / elem);
   const dim3 grid((unsigned)(((size_t)gz_div_up(w, per_lane) * h + 255) / 256)), block(256);
+  if (img->alpha) {
+    const unsigned bg = (unsigned)img->background[0] | ((unsigned)img->background[1] << 8) | ((unsigned)img->background[2] << 16);
+    switch (img->dtype) {
+      case GZ_DT_U8: launch_ingest_rgba(stream, grid, block, (const uint8_t*)img->data, (const uint8_t*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+      case GZ_DT_F32: launch_ingest_rgba(stream, grid, block, (const float*)img->data, (const float*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+      case GZ_DT_F16: launch_ingest_rgba(stream, grid, block, (const ingest_f16*)img->data, (const ingest_f16*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+      case GZ_DT_BF16: launch_ingest_rgba(stream, grid, block, (const ingest_bf16*)img->data, (const ingest_bf16*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+      default: launch_ingest_rgba(stream, grid, block, (const uint16_t*)img->data, (const uint16_t*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+    }
+    return;
+  }
+  const int wide = ingest_wide_mode(img->data, elem, sy, sx, sc);
   switch (img->dtype) {
     case GZ_DT_U8:
       GZ_LAUNCH((k_ingest_rgb<uint8_t>), grid, block, stream, (const uint8_t*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
@@ -189,14 +221,17 @@ static void launch_ingest(hipStream_t stream, const gz_device_image* img, int w,
     case GZ_DT_F16:
       GZ_LAUNCH((k_ingest_rgb<ingest_f16>), grid, block, stream, (const ingest_f16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
       break;
-    default:
+    case GZ_DT_BF16:
       GZ_LAUNCH((k_ingest_rgb<ingest_bf16>), grid, block, stream, (const ingest_bf16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
+      break;
+    default:
+      GZ_LAUNCH((k_ingest_rgb<uint16_t>), grid, block, stream, (const uint16_t*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
       break;
   }
 }
 
-static int set_rgb_device(gz_ctx* c, const gz_device_image* img);
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_image* img, float target, int* err);
+static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img);
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err);
 gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
   int prev = -1;
   if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
@@ -204,8 +239,8 @@ gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, in
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
   return c;
 }
-gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) {
-  if (check_device_image(img, w, h) != GZ_OK) {   // (before any device call)
+gz_ctx* gz_create_from_device_pixels(int device, int w, int h, const gz_device_pixels* img, float target, int* err) {
+  if (check_device_pixels(img, w, h) != GZ_OK) {   // (before any device call)
     if (err) *err = GZ_E_ARG;
     return nullptr;
   }
@@ -215,8 +250,16 @@ gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* i
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
   return c;
 }
+gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) {
+  gz_device_pixels px;
+  if (pixels_of_image(img, &px) != GZ_OK) {
+    if (err) *err = GZ_E_ARG;
+    return nullptr;
+  }
+  return gz_create_from_device_pixels(device, w, h, &px, target, err);
+}
 // The original from host pixels (rgb) or from a device-resident image (img, checked by the caller): one of the two.
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_image* img, float target, int* err) {
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err) {
   int dummy;
   if (!err) err = &dummy;
   *err = GZ_OK;
@@ -347,8 +390,8 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   return original_from_lin(c);
 }
 
-// (the context's device is current, img has passed check_device_image and check_device_pointer)
-static int set_rgb_device(gz_ctx* c, const gz_device_image* img) {
+// (the context's device is current, img has passed check_device_pixels and check_device_pointer)
+static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img) {
   c->lin_is_cand = c->xyb_is_cand = false;
   c->have_block_mask = c->have_distmap = false;
   if (img->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
@@ -361,12 +404,17 @@ static int set_rgb_device(gz_ctx* c, const gz_device_image* img) {
   return original_from_lin(c);   // (its synchronise: the source is read when the call returns)
 }
 
-int gz_set_rgb_device(gz_ctx* c, const gz_device_image* img) {
+int gz_set_rgb_device_pixels(gz_ctx* c, const gz_device_pixels* img) {
   if (!c) return GZ_E_ARG;
-  if (check_device_image(img, c->w, c->h) != GZ_OK) return GZ_E_ARG;
+  if (check_device_pixels(img, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   DeviceScope ds_(c);
   if (const int rc = check_device_pointer(c->device, img, c->w, c->h, &c->err)) return rc;
   return set_rgb_device(c, img);
+}
+int gz_set_rgb_device(gz_ctx* c, const gz_device_image* img) {
+  gz_device_pixels px;
+  if (!c || pixels_of_image(img, &px) != GZ_OK) return GZ_E_ARG;
+  return gz_set_rgb_device_pixels(c, &px);
 }
 
 void gz_destroy(gz_ctx* c) {

@@ -43,8 +43,8 @@ int gz_encode_rgb_only(int device, const uint8_t* rgb, int w, int h, int16_t* co
   return GZ_OK;
 }
 
-int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out) {
-  if (!host_rgb_out || check_device_image(img, w, h) != GZ_OK) return GZ_E_ARG;
+int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, int h, uint8_t* host_rgb_out) {
+  if (!host_rgb_out || check_device_pixels(img, w, h) != GZ_OK) return GZ_E_ARG;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
   if (check_device_pointer(device, img, w, h, nullptr) != GZ_OK) return GZ_E_ARG;
   DevBuf drgb;
@@ -62,6 +62,11 @@ int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uin
   const bool copied = launched && hipMemcpy(host_rgb_out, drgb.p, (size_t)3 * w * h, hipMemcpyDeviceToHost) == hipSuccess;
   if (ev) (void)hipEventDestroy(ev);
   return copied ? GZ_OK : GZ_E_HIP;
+}
+int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out) {
+  gz_device_pixels px;
+  if (pixels_of_image(img, &px) != GZ_OK) return GZ_E_ARG;
+  return gz_pack_rgb_device_pixels(device, &px, w, h, host_rgb_out);
 }
 
 int gz_dct_double_blocks(int device, double* blocks, int n, int inverse) {

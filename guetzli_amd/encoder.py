@@ -3,11 +3,12 @@ guetzli_amd.process(rgb, quality=95) == guetzli::Process(params, stats, rgb, w, 
 with the numeric hot path on the MI355X.  No CPU fallback: the host library links the
 gfx950 C-ABI library and fails if no GPU is usable."""
 import ctypes as C
+import operator
 import os
 
 import numpy as np
 
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, device_image
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -50,6 +51,8 @@ class HostLibrary:
         self.lib.gzh_process_device.restype = C.c_long
         self.lib.gzh_process_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_void_p,
                                                 C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+        self.lib.gzh_process_device_pixels.restype = C.c_long
+        self.lib.gzh_process_device_pixels.argtypes = self.lib.gzh_process_device.argtypes
         self.lib.gzh_write_jpeg_factor.restype = C.c_long
         self.lib.gzh_write_jpeg_factor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                    C.c_int, C.c_void_p, C.c_long]
@@ -69,8 +72,8 @@ class HostLibrary:
 
     def _process(self, data, w, h, quality, target, device, clear_metadata, try_420, force_420,
                  use_silver_screen, lookahead, new_model, want_trace):
-        """gzh_process_params -- or, for a capi.GzDeviceImage, gzh_process_device -- with a buffer that grows to
-        what the library asks for."""
+        """gzh_process_params -- or, for a capi.GzDevicePixels / GzDeviceImage, gzh_process_device_pixels /
+        gzh_process_device -- with a buffer that grows to what the library asks for."""
         is_jpeg = isinstance(data, (bytes, bytearray))
         on_device = not is_jpeg and not isinstance(data, np.ndarray)
         buf = np.frombuffer(data, np.uint8) if is_jpeg else data
@@ -91,8 +94,8 @@ class HostLibrary:
             out = np.empty(cap, np.uint8)
             qt = (-1.0 if target is not None else float(quality), float(target or 0.0))
             if on_device:
-                n = self.lib.gzh_process_device(C.addressof(data), w, h, *qt, ip, out.ctypes.data, cap,
-                                                tr, len(tr) if tr else 0, tm, len(tm))
+                entry = self.lib.gzh_process_device_pixels if isinstance(data, GzDevicePixels) else self.lib.gzh_process_device
+                n = entry(C.addressof(data), w, h, *qt, ip, out.ctypes.data, cap, tr, len(tr) if tr else 0, tm, len(tm))
             else:
                 n = self.lib.gzh_process_params(buf.ctypes.data, len(data) if is_jpeg else -1, w, h, *qt, ip,
                                                 out.ctypes.data, cap, tr, len(tr) if tr else 0, tm, len(tm))
@@ -128,13 +131,19 @@ class HostLibrary:
 
     def process_device(self, ptr, w, h, dtype, strides, stream=0, quality=95.0, target=None, device=0,
                        want_trace=False, try_420=False, force_420=False, use_silver_screen=False, lookahead=3,
-                       new_model=True):
+                       new_model=True, alpha_offset=None, background=None):
         """guetzli_amd::Process(params, stats, DeviceImage, w, h, &out): the raw form.  ptr = address, in the memory of
         GPU `device`, of element (0, 0, 0) of a w x h x 3 image; dtype = "uint8" | "float32" | "float16" | "bfloat16"
-        (or a GZ_DT_* code); strides = (y, x, c) in elements, each >= 0; stream = the hipStream_t whose work produced
-        the data (0: nothing to wait for).  Floats are [0, 1]: byte = rint(clamp(x * 255, 0, 255)).  Returns what
-        process() returns."""
-        image = device_image(ptr, DTYPE_CODES.get(dtype, dtype), strides, stream)
+        | "uint16" (or a GZ_DT_* code); strides = (y, x, c) in elements, each >= 0; stream = the hipStream_t whose work
+        produced the data (0: nothing to wait for).  Floats are [0, 1]: byte = rint(clamp(x * 255, 0, 255)); uint16:
+        the high byte.  alpha_offset = where, in elements from ptr, the alpha sample of pixel (0, 0) sits (it moves
+        with the y and x strides; None: opaque), background = the bytes (r, g, b) such pixels are blended over:
+        (v * a + bg * (255 - a) + 128) // 255.  Returns what process() returns."""
+        code = DTYPE_CODES.get(dtype, dtype)
+        alpha = 0 if alpha_offset is None else int(ptr) + int(alpha_offset) * ITEMSIZE[code]
+        if alpha_offset is not None and not alpha:
+            raise ValueError("an alpha sample at address 0")
+        image = device_pixels(ptr, code, strides, stream, alpha, _background(background) or (0, 0, 0))
         return self._process(image, w, h, quality, target, device, True, try_420, force_420,
                              use_silver_screen, lookahead, new_model, want_trace)
 
@@ -209,7 +218,34 @@ def load_host():
     return _default
 
 
-DTYPE_CODES = {"uint8": GZ_DT_U8, "float32": GZ_DT_F32, "float16": GZ_DT_F16, "bfloat16": GZ_DT_BF16}
+DTYPE_CODES = {"uint8": GZ_DT_U8, "float32": GZ_DT_F32, "float16": GZ_DT_F16, "bfloat16": GZ_DT_BF16, "uint16": GZ_DT_U16}
+ITEMSIZE = {GZ_DT_U8: 1, GZ_DT_F32: 4, GZ_DT_F16: 2, GZ_DT_BF16: 2, GZ_DT_U16: 2}
+
+
+def _background(background):
+    """None, or the bytes (r, g, b) of background=: three ints 0..255, or one int for a grey background."""
+    if background is None:
+        return None
+    try:
+        if isinstance(background, (bool, str, bytes)):
+            raise TypeError
+        vals = [operator.index(background)] * 3 if not hasattr(background, "__len__") else [operator.index(v) for v in background]
+    except TypeError:
+        raise ValueError(f"background={background!r}: three ints 0..255, or one for a grey background") from None
+    if len(vals) != 3 or any(isinstance(v, bool) or not 0 <= v <= 255 for v in vals):
+        raise ValueError(f"background={background!r}: three ints 0..255, or one for a grey background")
+    return tuple(vals)
+
+
+def blend_on_background(pixels, background):
+    """The PNG front end's blend (BlendOnBlack at background 0) of uint8 [h][w][2] grey + alpha or [h][w][4] RGBA ->
+    uint8 [h][w][3]: (v * a + bg * (255 - a) + 128) // 255, an integer division."""
+    px = np.asarray(pixels, np.uint8).astype(np.uint32)
+    v, a = px[..., :-1], px[..., -1:]
+    if v.shape[-1] == 1:
+        v = np.repeat(v, 3, axis=-1)
+    bg = np.array(background, np.uint32)
+    return ((v * a + bg * (255 - a) + 128) // 255).astype(np.uint8)
 
 
 def is_device_resident(x):
@@ -217,21 +253,30 @@ def is_device_resident(x):
     return bool(getattr(x, "is_cuda", False)) or hasattr(x, "__cuda_array_interface__")
 
 
-def _layout_strides(shape, strides, layout):
-    """(w, h, (stride_y, stride_x, stride_c)) of an image of `shape` with element `strides`: 2-D is grey (the one
-    value for all three channels), 3-D is "HWC" or "CHW" -- layout=None takes whichever of the first / last
-    dimension is 3 and refuses a shape where both are."""
+def _layout_strides(shape, strides, layout, background=None):
+    """(w, h, (stride_y, stride_x, stride_c), alpha offset or None) of an image of `shape` with element `strides`:
+    2-D is grey (the one value for all three channels), 3-D is "HWC" or "CHW" with 3 channels, 1 (grey) or -- only
+    with background= -- 2 (grey + alpha) or 4 (RGBA).  layout=None takes whichever of the first / last dimension is
+    3 and refuses a shape where both are; where neither is, whichever is 1 (with background=: 1, 2 or 4), by the same
+    rule."""
     if len(shape) == 2:
         (h, w), (sy, sx) = shape, strides
-        return w, h, (sy, sx, 0)
+        return w, h, (sy, sx, 0), None
     if len(shape) != 3:
         raise ValueError(f"an image has 2 or 3 dimensions, not {len(shape)}")
+    need_background = f"shape {tuple(shape)}: pixels with alpha are blended only over a background that is named: background=(r, g, b)"
     if layout is None:
         first, last = shape[0] == 3, shape[2] == 3
+        if not first and not last:
+            counts = (1,) if background is None else (1, 2, 4)
+            first, last = shape[0] in counts, shape[2] in counts
+            if not first and not last:
+                if background is None and (shape[0] in (2, 4) or shape[2] in (2, 4)):
+                    raise ValueError(need_background)
+                raise ValueError(f"shape {tuple(shape)}: neither the first nor the last dimension is 3"
+                                 + (", 1, 2 or 4" if background is not None else " or 1"))
         if first and last:
             raise ValueError(f"shape {tuple(shape)} is ambiguous: say layout='HWC' or layout='CHW'")
-        if not first and not last:
-            raise ValueError(f"shape {tuple(shape)}: neither the first nor the last dimension is 3")
         layout = "CHW" if first else "HWC"
     if layout == "HWC":
         (h, w, ch), (sy, sx, sc) = shape, strides
@@ -239,27 +284,30 @@ def _layout_strides(shape, strides, layout):
         (ch, h, w), (sc, sy, sx) = shape, strides
     else:
         raise ValueError(f"layout {layout!r}: 'HWC', 'CHW' or None")
-    if ch != 3:
-        raise ValueError(f"shape {tuple(shape)} has {ch} channels in layout {layout}, not 3")
-    return w, h, (sy, sx, sc)
+    if ch in (2, 4) and background is None:
+        raise ValueError(need_background)
+    if ch not in (1, 2, 3, 4):
+        raise ValueError(f"shape {tuple(shape)} has {ch} channels in layout {layout}, not 1, 2, 3 or 4")
+    alpha = (ch - 1) * sc if ch in (2, 4) else None   # the last channel
+    return w, h, (sy, sx, sc if ch >= 3 else 0), alpha
 
 
-def _device_source(x, layout, device):
-    """(ptr, w, h, dtype name, element strides, producer stream, device ordinal) of a device-resident image."""
+def _device_source(x, layout, device, background=None):
+    """(ptr, w, h, dtype name, element strides, producer stream, device ordinal, alpha offset) of a device-resident image."""
     if getattr(x, "is_cuda", False):   # a torch tensor
         import torch
         name = str(x.dtype).replace("torch.", "")
         if name not in DTYPE_CODES:
-            raise TypeError(f"dtype {x.dtype}: uint8, float32, float16 or bfloat16")
+            raise TypeError(f"dtype {x.dtype}: uint8, uint16, float32, float16 or bfloat16")
         ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
         if device is not None and device != ordinal:
             raise ValueError(f"the tensor lives on device {ordinal}, device={device} was asked for")
-        w, h, strides = _layout_strides(tuple(x.shape), tuple(x.stride()), layout)
-        return x.data_ptr(), w, h, name, strides, torch.cuda.current_stream(x.device).cuda_stream, ordinal
+        w, h, strides, alpha = _layout_strides(tuple(x.shape), tuple(x.stride()), layout, background)
+        return x.data_ptr(), w, h, name, strides, torch.cuda.current_stream(x.device).cuda_stream, ordinal, alpha
     cai = x.__cuda_array_interface__
     dt = np.dtype(cai["typestr"])
     if dt.name not in DTYPE_CODES:   # (numpy has no bfloat16: such arrays come as torch tensors)
-        raise TypeError(f"dtype {dt}: uint8, float32 or float16")
+        raise TypeError(f"dtype {dt}: uint8, uint16, float32 or float16")
     shape = tuple(cai["shape"])
     if cai.get("strides") is None:
         byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
@@ -267,7 +315,7 @@ def _device_source(x, layout, device):
         byte_strides = tuple(cai["strides"])
     if any(b % dt.itemsize for b in byte_strides):
         raise ValueError("strides that are no multiple of the element size")
-    w, h, strides = _layout_strides(shape, tuple(b // dt.itemsize for b in byte_strides), layout)
+    w, h, strides, alpha = _layout_strides(shape, tuple(b // dt.itemsize for b in byte_strides), layout, background)
     # the interface's stream: None / absent = nothing to wait for; 1 = the legacy default stream, with which the
     # context's (blocking) streams synchronise by themselves: nothing to hand over; 2 = the per-thread default stream,
     # which orders itself against nobody: handed over as it is -- it is hipStreamPerThread's handle too, and it names the
@@ -275,7 +323,7 @@ def _device_source(x, layout, device):
     stream = cai.get("stream") or 0
     if stream == 1:
         stream = 0
-    return cai["data"][0], w, h, dt.name, strides, stream, 0 if device is None else device
+    return cai["data"][0], w, h, dt.name, strides, stream, 0 if device is None else device, alpha
 
 
 PER_THREAD_STREAM = 2   # hipStreamPerThread: the default stream of whichever thread uses the handle
@@ -288,41 +336,56 @@ class _Job:
         self.run, self.producer, self.keep = run, producer, keep   # keep: the object that owns the device memory
 
 
-def _prepared(rgb, layout, device, stream):
+def _prepared(rgb, layout, device, stream, background=None):
     """What of an encode must happen in the CALLER's thread -- torch's current stream is a property of the thread."""
+    background = _background(background)
     if not is_device_resident(rgb):
         if layout not in (None, "HWC"):
             raise ValueError("host pixels are [h][w][3]")
         if stream is not None:
             raise ValueError("stream= goes with device-resident pixels")
+        if background is not None:   # uint8 [h][w][2] / [h][w][4]: blended here, by the device path's rule
+            px = np.asarray(rgb)
+            if px.dtype == np.uint8 and px.ndim == 3 and px.shape[2] in (2, 4):
+                rgb = blend_on_background(px, background)
         return _Job(lambda **kw: load_host().process(rgb, device=0 if device is None else device, **kw))
-    ptr, w, h, dtype, strides, producer, ordinal = _device_source(rgb, layout, device)
+    ptr, w, h, dtype, strides, producer, ordinal, alpha = _device_source(rgb, layout, device, background)
     if stream is not None:
         producer = int(stream)
-    if any(s < 0 for s in strides):
+    if any(s < 0 for s in strides) or (alpha or 0) < 0:
         raise ValueError("negative strides (a flipped view): make it contiguous first")
-    return _Job(lambda **kw: load_host().process_device(ptr, w, h, dtype, strides, stream=producer, device=ordinal, **kw),
+    blend = {} if alpha is None else {"alpha_offset": alpha, "background": background}
+    return _Job(lambda **kw: load_host().process_device(ptr, w, h, dtype, strides, stream=producer, device=ordinal, **blend, **kw),
                 producer, rgb)
 
 
-def process(rgb, quality=95.0, layout=None, device=None, stream=None, **kw):
+def process(rgb, quality=95.0, layout=None, device=None, stream=None, background=None, **kw):
     """guetzli::Process of an image -> (jpeg_bytes, info).  `rgb` on the host: anything numpy turns into uint8
     [h][w][3].  `rgb` on the GPU -- a torch tensor with is_cuda, or an object with __cuda_array_interface__ -- is
-    encoded where it is: uint8, or float32 / float16 / bfloat16 in [0, 1]; "HWC" or "CHW" (layout=None: whichever of
-    the first / last dimension is 3), any strides >= 0, 2-D = grey; on the tensor's device (an explicit device= must
-    agree), behind the work enqueued so far on the producer's stream: the calling thread's current torch stream on
-    that device, the interface's `stream` entry, or stream= (a hipStream_t handle; 0: nothing to wait for)."""
-    return _prepared(rgb, layout, device, stream).run(quality=quality, **kw)
+    encoded where it is: uint8, uint16 (the high byte counts, as a 16-bit PNG is read), or float32 / float16 /
+    bfloat16 in [0, 1]; "HWC" or "CHW" (layout=None: whichever of the first / last dimension is 3 -- where neither
+    is, whichever is 1, or with background= 1, 2 or 4), any strides >= 0, 2-D or one channel = grey; on the tensor's
+    device (an explicit device= must agree), behind the work enqueued so far on the producer's stream: the calling
+    thread's current torch stream on that device, the interface's `stream` entry, or stream= (a hipStream_t handle;
+    0: nothing to wait for).
+    background=(r, g, b), or one int for a grey one, each 0..255: pixels with alpha -- 2 channels (grey + alpha) or 4
+    (RGBA, not premultiplied), the alpha of the colours' dtype and last -- are blended over it as the PNG front end
+    blends over black, on bytes: (v * a + bg * (255 - a) + 128) // 255.  The raw samples of a PNG as a GPU tensor, with
+    background=0, give the JPEG process_png gives.  Without background= such shapes are refused: nothing is blended
+    silently.  With an opaque image it has no effect.  A uint8 host array [h][w][2] or [h][w][4] is blended by the same
+    rule in numpy."""
+    return _prepared(rgb, layout, device, stream, background).run(quality=quality, **kw)
 
 
-def process_many(batch, workers=4, layout=None, device=None, stream=None, **kw):
+def process_many(batch, workers=4, layout=None, device=None, stream=None, background=None, **kw):
     """A batch of images with `workers` of them in flight on one GPU (batch.encode_concurrent): a 4-D tensor
-    [N,3,H,W] / [N,H,W,3] or a list of images, each as process() takes them.  Returns [(jpeg_bytes, info)] in order.
+    [N,C,H,W] / [N,H,W,C] or a list of images, each as process() takes them (background= included).  Returns
+    [(jpeg_bytes, info)] in order.
     The encodes run on worker threads, but every image's producer stream is the one process() would have taken in
     the CALLING thread, here and now: a batch made under `with torch.cuda.stream(s)` is encoded behind s.  (A
     __cuda_array_interface__ stream of 2, the per-thread default stream, is refused: it names another stream there.)"""
     from .batch import encode_concurrent
-    jobs = [_prepared(batch[i], layout, device, stream) for i in range(len(batch))]
+    jobs = [_prepared(batch[i], layout, device, stream, background) for i in range(len(batch))]
     if any(j.producer == PER_THREAD_STREAM for j in jobs):
         raise ValueError("a per-thread default stream cannot be waited for from the worker threads: synchronise it and "
                          "say stream=0, or encode with process()")

@@ -99,14 +99,14 @@ long gzh_process_params(const uint8_t* data, long jpeg_len, int w, int h, double
   GZH_GUARD_END
 }
 
-// Process(params, stats, DeviceImage, w, h, &out): `image` is a gz_device_image (include/guetzli_amd.h) on GPU
+// Process(params, stats, DeviceImage, w, h, &out): `image` is a gz_device_pixels (include/guetzli_amd.h) on GPU
 // iparams[0]; the other arguments as gzh_process_params'.
-long gzh_process_device(const gz_device_image* image, int w, int h, double quality, float target,
-                        const int* iparams, uint8_t* out, long cap, char* trace, long trace_cap,
-                        char* timers, long timers_cap) {
+long gzh_process_device_pixels(const gz_device_pixels* image, int w, int h, double quality, float target,
+                               const int* iparams, uint8_t* out, long cap, char* trace, long trace_cap,
+                               char* timers, long timers_cap) {
   GZH_GUARD_BEGIN
-  if (!image || image->struct_size != (int)sizeof(gz_device_image)) {
-    fprintf(stderr, "guetzli_amd: gzh_process_device: not a gz_device_image of this library\n");
+  if (!image || image->struct_size != (int)sizeof(gz_device_pixels)) {
+    fprintf(stderr, "guetzli_amd: gzh_process_device_pixels: not a gz_device_pixels of this library\n");
     return -1;
   }
   const guetzli_amd::Params params = ParamsFrom(quality, target, iparams);
@@ -115,6 +115,8 @@ long gzh_process_device(const gz_device_image* image, int w, int h, double quali
   im.data = image->data;
   im.stride_y = image->stride_y; im.stride_x = image->stride_x; im.stride_c = image->stride_c;
   im.producer_stream = image->producer_stream;
+  im.alpha = image->alpha;
+  memcpy(im.background, image->background, 3);
   guetzli_amd::ProcessStats stats;
   std::string dbg;
   if (trace) stats.debug_output = &dbg;
@@ -122,6 +124,24 @@ long gzh_process_device(const gz_device_image* image, int w, int h, double quali
   if (!guetzli_amd::Process(params, &stats, im, w, h, &jpg)) return -1;
   return Deliver(jpg, dbg, stats, out, cap, trace, trace_cap, timers, timers_cap);
   GZH_GUARD_END
+}
+
+// The same for a gz_device_image: opaque pixels.
+long gzh_process_device(const gz_device_image* image, int w, int h, double quality, float target,
+                        const int* iparams, uint8_t* out, long cap, char* trace, long trace_cap,
+                        char* timers, long timers_cap) {
+  if (!image || image->struct_size != (int)sizeof(gz_device_image)) {
+    fprintf(stderr, "guetzli_amd: gzh_process_device: not a gz_device_image of this library\n");
+    return -1;
+  }
+  gz_device_pixels px;
+  memset(&px, 0, sizeof(px));
+  px.struct_size = (int)sizeof(px);
+  px.dtype = image->dtype;
+  px.data = image->data;
+  px.stride_y = image->stride_y; px.stride_x = image->stride_x; px.stride_c = image->stride_c;
+  px.producer_stream = image->producer_stream;
+  return gzh_process_device_pixels(&px, w, h, quality, target, iparams, out, cap, trace, trace_cap, timers, timers_cap);
 }
 
 long gzh_process(const uint8_t* rgb, int w, int h, double quality, float target, int device,

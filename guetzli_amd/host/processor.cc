@@ -13,8 +13,8 @@
 // for use_silver_screen fails below, loudly -- there is no host path behind this call.
 extern "C" int gz_downsample_silver(gz_ctx* ctx, int16_t* coeffs_out, uint64_t counters[2]) __attribute__((weak));
 // ... and so do the device-input entries: a stand-in without them refuses a DeviceImage, it has nowhere to read one from.
-extern "C" gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) __attribute__((weak));
-extern "C" int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out) __attribute__((weak));
+extern "C" gz_ctx* gz_create_from_device_pixels(int device, int w, int h, const gz_device_pixels* img, float target, int* err) __attribute__((weak));
+extern "C" int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, int h, uint8_t* host_rgb_out) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -443,24 +443,26 @@ bool Encoder::RunDevice(const DeviceImage& image, int w, int h, std::string* out
     fprintf(stderr, "Could not create jpg data from rgb pixels\n");
     return false;
   }
-  if (!gz_create_from_device || !gz_pack_rgb_device) return Fail("device-resident input (not in this device library)", GZ_E_STATE);
-  gz_device_image img;
+  if (!gz_create_from_device_pixels || !gz_pack_rgb_device_pixels) return Fail("device-resident input (not in this device library)", GZ_E_STATE);
+  gz_device_pixels img;
   memset(&img, 0, sizeof(img));
   img.struct_size = (int)sizeof(img);
   img.dtype = image.dtype;
   img.data = image.data;
   img.stride_y = image.stride_y; img.stride_x = image.stride_x; img.stride_c = image.stride_c;
   img.producer_stream = image.producer_stream;
+  img.alpha = image.alpha;
+  memcpy(img.background, image.background, 3);
   SetGeometry(w, h, 1);
   if (w < 32 || h < 32) {   // too small for a context: the kernel's bytes come to the host, the rest is Run's
     std::vector<uint8_t> rgb((size_t)3 * w * h);
-    const int rc0 = gz_pack_rgb_device(params_.device, &img, w, h, rgb.data());
-    if (rc0 != GZ_OK) return Fail("gz_pack_rgb_device", rc0);
+    const int rc0 = gz_pack_rgb_device_pixels(params_.device, &img, w, h, rgb.data());
+    if (rc0 != GZ_OK) return Fail("gz_pack_rgb_device_pixels", rc0);
     return RunTooSmall(rgb.data(), w, h, out);
   }
   int err = 0;
-  ctx_ = gz_create_from_device(params_.device, w, h, &img, params_.butteraugli_target, &err);
-  if (!ctx_) return Fail("gz_create_from_device", err);
+  ctx_ = gz_create_from_device_pixels(params_.device, w, h, &img, params_.butteraugli_target, &err);
+  if (!ctx_) return Fail("gz_create_from_device_pixels", err);
   return RunFromContext(start, out);
 }
 

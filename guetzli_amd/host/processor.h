@@ -46,14 +46,18 @@ struct ProcessStats {                 // guetzli::ProcessStats, stats.h:34-41
   std::map<std::string, double> timers;
 };
 
-// gz_device_image of include/guetzli_amd.h: a w x h x 3 image that already lives in the memory of GPU
+// gz_device_pixels of include/guetzli_amd.h: a w x h x 3 image that already lives in the memory of GPU
 // Params::device.  Element (y, x, c) is data[y*stride_y + x*stride_x + c*stride_c], strides in elements, >= 0.
+// With alpha != nullptr pixel (y, x) has the alpha sample alpha[y*stride_y + x*stride_x], of the colours' dtype, and
+// is blended over `background` as the PNG front end blends over black: (v * a + bg * (255 - a) + 128) / 255 on bytes.
 struct DeviceImage {
-  enum Dtype { kU8 = 0, kF32 = 1, kF16 = 2, kBF16 = 3 };   // GZ_DT_*
+  enum Dtype { kU8 = 0, kF32 = 1, kF16 = 2, kBF16 = 3, kU16 = 4 };   // GZ_DT_* (kU16: the high byte counts)
   int dtype = kU8;
   const void* data = nullptr;         // device address of element (0, 0, 0)
   int64_t stride_y = 0, stride_x = 0, stride_c = 0;
   void* producer_stream = nullptr;    // hipStream_t whose work writes the data; nullptr: none to wait for
+  const void* alpha = nullptr;        // device address of the alpha sample of pixel (0, 0); nullptr: opaque
+  uint8_t background[3] = {0, 0, 0};  // r, g, b
 };
 
 double ButteraugliScoreForQuality(double quality);                       // quality.cc:78-85
@@ -64,7 +68,8 @@ double ScoreJPEG(double butteraugli_distance, int size, double target);  // scor
 bool Process(const Params& params, ProcessStats* stats, const std::vector<uint8_t>& rgb,
              int w, int h, std::string* out);
 
-// The same from pixels on the GPU (floats: [0, 1] -> rint(x * 255), clamped; include/guetzli_amd.h has the rule):
+// The same from pixels on the GPU (floats: [0, 1] -> rint(x * 255), clamped; uint16: the high byte; alpha blended over
+// the background; include/guetzli_amd.h has the rules):
 // nothing goes through host memory but, for w or h < 32, the bytes of the tiny image itself.  Same refusals and
 // messages as above; memory that GPU params.device cannot read is a failure, not a fault.
 bool Process(const Params& params, ProcessStats* stats, const DeviceImage& image, int w, int h,

@@ -53,7 +53,8 @@ typedef struct gz_ctx gz_ctx;
 int gz_abi_version(void);                 /* currently 6 (5 without the two experiment fields of gz_config); the
                                              device-input entries (gz_device_image, gz_create_from_device,
                                              gz_set_rgb_device, gz_pack_rgb_device) were ADDED to version 6: no
-                                             existing declaration, struct or call sequence changed, so the number stays */
+                                             existing declaration, struct or call sequence changed, so the number stays;
+                                             so were gz_device_pixels and its three entries, by the same rule */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -157,6 +158,38 @@ int gz_set_rgb_device(gz_ctx* ctx, const gz_device_image* img);
 /* The conversion alone, without a context: img (w x h, 0 < w, h < 65536) -> host_rgb_out, packed uint8 w*h*3.  For
  * images too small for a context (w or h < 32: gz_encode_rgb_only takes the bytes from there). */
 int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uint8_t* host_rgb_out);
+
+/* Device-resident input with alpha and 16-bit samples: the pixel forms a PNG can hold (grey, grey + alpha, RGB, RGBA;
+ * 8 or 16 bits), under the arithmetic of the PNG front end (host/png_reader.cc, the reference's ReadPNG) -- the raw
+ * samples of a PNG handed over as device memory encode to the bytes `guetzli in.png out.jpg` writes.
+ * gz_device_pixels is gz_device_image (same addressing, same stream contract, same memory rules) and
+ *   dtype GZ_DT_U16: the byte of a sample v is v >> 8, the HIGH byte (libpng's STRIP_16), not a rounding;
+ *   alpha: the device address of the alpha sample of pixel (0, 0), of the colours' dtype; the alpha of pixel (y, x) is
+ *     alpha[y*stride_y + x*stride_x] -- data + 3 of HWC RGBA, the fourth plane of CHW, data + 1 of interleaved
+ *     grey + alpha (stride_c = 0, stride_x = 2), or a mask in an allocation of its own.  NULL: the image is opaque.
+ *   background: the bytes r, g, b (and 0) the pixels are blended over.
+ * With a the byte of the alpha sample (floats by the float rule above: NaN is transparent), v the byte of a colour
+ * sample and bg the background's byte of that channel:
+ *   out = (v * a + bg * (255 - a) + 128) / 255     integer (floor) division
+ * which is BlendOnBlack (guetzli.cc:42-44) at bg = 0; a = 255 gives v, a = 0 gives bg.  Nothing is premultiplied.
+ * The three entries are the three above for such pixels (those forward here with alpha = NULL), with the same
+ * contract: GZ_E_ARG before any device call for NULL img or data, a wrong struct_size, an unknown dtype, a negative
+ * stride, an extent -- the alpha extent (h-1) stride_y + (w-1) stride_x included -- beyond 62 bits; alpha gets data's
+ * pointer checks (readable by the context's device, its extent inside its allocation; a host pointer is GZ_E_ARG and
+ * gz_last_error names alpha). */
+#define GZ_DT_U16 4                      /* gz_device_pixels only */
+typedef struct gz_device_pixels {
+  int struct_size;            /* sizeof(gz_device_pixels) */
+  int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 / GZ_DT_U16 */
+  const void* data;           /* device address of element (0,0,0) */
+  int64_t stride_y, stride_x, stride_c;   /* elements, >= 0 */
+  void* producer_stream;      /* hipStream_t whose work produced the data; NULL = none to wait for */
+  const void* alpha;          /* device address of the alpha sample of pixel (0,0); NULL = opaque */
+  uint8_t background[4];      /* r, g, b, 0 */
+} gz_device_pixels;
+gz_ctx* gz_create_from_device_pixels(int device, int w, int h, const gz_device_pixels* img, float target, int* err);
+int gz_set_rgb_device_pixels(gz_ctx* ctx, const gz_device_pixels* img);
+int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, int h, uint8_t* host_rgb_out);
 
 int gz_synchronize(gz_ctx* ctx);
 /* Run subsequent work of this context on an externally owned hipStream_t (e.g. torch's
