@@ -62,6 +62,19 @@ def device_pixels(ptr, dtype, strides, stream=0, alpha=0, background=(0, 0, 0)):
                           int(alpha) or None, (C.c_uint8 * 4)(r, g, b, 0))
 
 
+class GzDeviceOutput(C.Structure):
+    """gz_device_output of include/guetzli_amd.h: where decoded pixels go, a strided w x h x 3 image in device memory."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_y", C.c_int64), ("stride_x", C.c_int64),
+                ("stride_c", C.c_int64), ("consumer_stream", _P)]
+
+
+def device_output(ptr, dtype, strides, stream=0):
+    """A GzDeviceOutput: ptr = device address of element (0, 0, 0), dtype = GZ_DT_*, strides = (y, x, c) in elements,
+    stream = the hipStream_t that used the memory before and reads it afterwards (0: none)."""
+    sy, sx, sc = (int(v) for v in strides)
+    return GzDeviceOutput(C.sizeof(GzDeviceOutput), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None)
+
+
 # name -> (restype, argtypes); mirrors include/guetzli_amd.h one to one
 SIGNATURES = {
     "gz_abi_version": (_I, []),
@@ -82,6 +95,9 @@ SIGNATURES = {
     "gz_create_from_device_pixels": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
     "gz_set_rgb_device_pixels": (_I, [_P, _P]),
     "gz_pack_rgb_device_pixels": (_I, [_I, _P, _I, _I, _P]),
+    "gz_decode_coeffs_device": (_I, [_I, _P, _I, _I, _I, _P]),
+    "gz_decode_coeffs": (_I, [_I, _P, _I, _I, _I, _P]),
+    "gz_reconstruct_device": (_I, [_P, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -332,6 +348,19 @@ class Library:
         self.check(entry(device, C.byref(image), w, h, _ptr(out)))
         return out
 
+    def decode_coeffs(self, coeffs, w, h, chroma_factor=1, device=0):
+        """gz_decode_coeffs: OutputImage::ToSRGB of dequantised coefficients (frame layout of the header) without a
+        context -> uint8 [h][w][3]."""
+        co = np.ascontiguousarray(coeffs, np.int16)
+        out = np.zeros((h, w, 3), np.uint8)
+        self.check(self.lib.gz_decode_coeffs(device, _ptr(co), w, h, chroma_factor, _ptr(out)))
+        return out
+
+    def decode_coeffs_device(self, coeffs, w, h, output, chroma_factor=1, device=0):
+        """gz_decode_coeffs_device: the same written into `output` (device_output(...))."""
+        co = np.ascontiguousarray(coeffs, np.int16)
+        self.check(self.lib.gz_decode_coeffs_device(device, _ptr(co), w, h, chroma_factor, C.byref(output)))
+
 
 class Context:
     """One (image, GPU) context == one guetzli::ButteraugliComparator + OutputImage."""
@@ -422,6 +451,11 @@ class Context:
         self.rgb = None
         entry = self.L.lib.gz_set_rgb_device_pixels if isinstance(image, GzDevicePixels) else self.L.lib.gz_set_rgb_device
         self._chk(entry(self.handle, C.byref(image)))
+
+    def reconstruct_device(self, output):
+        """gz_reconstruct_device: the candidate's pixels (gz_reconstruct's srgb) written into `output`
+        (device_output(...), w x h)."""
+        self._chk(self.L.lib.gz_reconstruct_device(self.handle, C.byref(output)))
 
     def synchronize(self):
         self._chk(self.L.lib.gz_synchronize(self.handle))

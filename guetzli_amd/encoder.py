@@ -8,7 +8,9 @@ import os
 
 import numpy as np
 
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_pixels
+import time
+
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_output, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -67,6 +69,14 @@ class HostLibrary:
         self.lib.gzh_jpeg_head.restype = C.c_long
         self.lib.gzh_jpeg_head.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+        self.lib.gzh_jpeg_size.restype = C.c_long
+        self.lib.gzh_jpeg_size.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
+        self.lib.gzh_decode_jpeg_device.restype = C.c_long
+        self.lib.gzh_decode_jpeg_device.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+        self.lib.gzh_decode_jpeg_device_sized.restype = C.c_long
+        self.lib.gzh_decode_jpeg_device_sized.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        self.lib.gzh_decode_jpeg.restype = C.c_long
+        self.lib.gzh_decode_jpeg.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long]
         self.lib.gzh_butteraugli_score_for_quality.restype = C.c_double
         self.lib.gzh_butteraugli_score_for_quality.argtypes = [C.c_double]
 
@@ -146,6 +156,46 @@ class HostLibrary:
         image = device_pixels(ptr, code, strides, stream, alpha, _background(background) or (0, 0, 0))
         return self._process(image, w, h, quality, target, device, True, try_420, force_420,
                              use_silver_screen, lookahead, new_model, want_trace)
+
+    def jpeg_size(self, data):
+        """(w, h) of a JPEG the reader accepts; raises if the stream is rejected."""
+        buf = np.frombuffer(data, np.uint8)
+        wh = (C.c_int * 2)()
+        if self.lib.gzh_jpeg_size(buf.ctypes.data, len(data), wh) != 0:
+            raise ValueError("not a readable JPEG (see stderr)")
+        return wh[0], wh[1]
+
+    def decode_jpeg(self, data, device=0):
+        """guetzli::DecodeJpegToRGB computed on GPU `device`, the pixels brought back: uint8 [h][w][3].  Raises if the
+        stream is refused (one component, or YCbCr 4:4:4 / 4:2:0, are decoded; message on stderr)."""
+        buf = np.frombuffer(data, np.uint8)
+        w, h = _jpeg_dimensions(data)   # (the frame header: the stream is read once, by the decode itself)
+        if w * h > (1 << 28):
+            w = h = 0
+        out = np.zeros(max(3 * w * h, 1), np.uint8)
+        for _ in range(2):
+            n = self.lib.gzh_decode_jpeg(buf.ctypes.data if len(data) else None, len(data), device, out.ctypes.data, out.size)
+            if n < 0:
+                raise ValueError("guetzli_amd.DecodeJpegToRGB: not a JPEG this library decodes (see stderr)")
+            if n <= out.size:
+                break
+            out = np.zeros(n, np.uint8)
+        w, h = self.jpeg_size(data) if n != 3 * w * h else (w, h)
+        return out[:n].reshape(h, w, 3)
+
+    def decode_jpeg_device(self, data, ptr, dtype, strides, stream=0, device=0, size=None):
+        """guetzli_amd::DecodeJpegToRGB(jpeg, device, DeviceOutput, ...): the raw form.  ptr = address, in the memory of
+        GPU `device`, of element (0, 0, 0) of the w x h x 3 image the JPEG decodes to (jpeg_size); dtype as
+        process_device's; strides = (y, x, c) in elements, no two elements at one address; stream = the hipStream_t
+        that used the memory before and reads it afterwards (0: none, the call waits for the pixels).  size = (w, h):
+        what the destination was made for -- a stream of another size is refused instead of written."""
+        buf = np.frombuffer(data, np.uint8)
+        image = device_output(ptr, DTYPE_CODES.get(dtype, dtype), strides, stream)
+        w, h = size or (0, 0)
+        n = self.lib.gzh_decode_jpeg_device_sized(buf.ctypes.data if len(data) else None, len(data), device, C.addressof(image), w, h)
+        if n != 0:
+            raise RuntimeError("guetzli_amd.DecodeJpegToRGB failed (see stderr)" if n == -1 else
+                               "guetzli_amd.DecodeJpegToRGB raised a C++ exception (see stderr)")
 
     def read_png(self, data):
         """ReadPNG of the reference's front end (guetzli.cc:47-152): PNG bytes -> uint8
@@ -336,8 +386,139 @@ class _Job:
         self.run, self.producer, self.keep = run, producer, keep   # keep: the object that owns the device memory
 
 
-def _prepared(rgb, layout, device, stream, background=None):
+def _strides_alias(strides, counts):
+    """gz_device_output's test: with the dimensions ordered by stride, a stride smaller than the extent (stride *
+    count) of the dimension before it, or smaller than 1, lets two elements share an address.  A dimension of one
+    element does not count."""
+    least = 1
+    for stride, count in sorted(zip(strides, counts)):
+        if count == 1:
+            continue
+        if stride < least:
+            return True
+        least = stride * count
+    return False
+
+
+def _device_destination(x, w, h, layout, device):
+    """(ptr, dtype name, element strides (y, x, c), consumer stream, device ordinal) of the device-resident image `x`
+    that is to receive w x h decoded pixels in `layout`."""
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"layout {layout!r}: 'HWC' or 'CHW'")
+    want = (h, w, 3) if layout == "HWC" else (3, h, w)
+    if getattr(x, "is_cuda", False):   # a torch tensor
+        import torch
+        name = str(x.dtype).replace("torch.", "")
+        if name not in DTYPE_CODES:
+            raise TypeError(f"dtype {x.dtype}: uint8, uint16, float32, float16 or bfloat16")
+        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        if device is not None and device != ordinal:
+            raise ValueError(f"the tensor lives on device {ordinal}, device={device} was asked for")
+        shape, strides = tuple(x.shape), tuple(x.stride())
+        ptr, stream = x.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream
+    else:
+        cai = x.__cuda_array_interface__
+        dt = np.dtype(cai["typestr"])
+        if dt.name not in DTYPE_CODES:
+            raise TypeError(f"dtype {dt}: uint8, uint16, float32 or float16")
+        if cai["data"][1]:
+            raise ValueError("out= is read-only (its __cuda_array_interface__ says so)")
+        name, shape = dt.name, tuple(cai["shape"])
+        if cai.get("strides") is None:
+            byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
+        else:
+            byte_strides = tuple(cai["strides"])
+        if any(b % dt.itemsize for b in byte_strides):
+            raise ValueError("strides that are no multiple of the element size")
+        strides = tuple(b // dt.itemsize for b in byte_strides)
+        stream = cai.get("stream") or 0   # (as _device_source reads it)
+        if stream == 1:
+            stream = 0
+        ptr, ordinal = cai["data"][0], 0 if device is None else device
+    if shape != want:
+        raise ValueError(f"out= has shape {shape}, the JPEG decodes to {want} in layout {layout}")
+    sy, sx, sc = strides if layout == "HWC" else (strides[1], strides[2], strides[0])
+    if min(sy, sx, sc) < 0:
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    if _strides_alias((sy, sx, sc), (h, w, 3)):
+        raise ValueError(f"out= has strides {strides} under which two of its elements share an address (an expanded view?)")
+    return ptr, name, (sy, sx, sc), stream, ordinal
+
+
+def _new_device_tensor(w, h, dtype, layout, ordinal):
+    """A fresh torch tensor on GPU `ordinal` for w x h decoded pixels, from the calling thread's current stream."""
+    import torch
+    name = str(dtype).replace("torch.", "")
+    if name not in DTYPE_CODES:
+        raise TypeError(f"dtype {dtype}: uint8, uint16, float32, float16 or bfloat16")
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"layout {layout!r}: 'HWC' or 'CHW'")
+    return torch.empty((h, w, 3) if layout == "HWC" else (3, h, w), dtype=getattr(torch, name), device=f"cuda:{ordinal}")
+
+
+def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None):
+    """guetzli::DecodeJpegToRGB with the pixels left on the GPU: the image a JPEG decodes to under the encoder's own
+    pixel model -- the integer IDCT and colour conversion every butteraugli distance of the search was computed on.
+    One-component (grey) and YCbCr 4:4:4 / 4:2:0 streams are decoded, everything else is refused.
+    Returns a torch tensor on GPU `device` (None: torch's current one), [h][w][3] ("HWC") or [3][h][w] ("CHW") of
+    `dtype`: uint8 the bytes, uint16 byte * 257, float32 / float16 / bfloat16 byte / 255 -- what process() reads back
+    as the same bytes.  It is allocated on the calling thread's current stream, and work enqueued on that stream
+    afterwards sees the pixels: no synchronisation is needed.
+    out=: a GPU tensor, or an object with __cuda_array_interface__, of the JPEG's size in `layout` is filled in place
+    and returned; dtype and strides are its own, so a crop inside a larger tensor is written without touching what
+    surrounds it.  stream= overrides the consumer stream (a hipStream_t handle; 0: none -- the call waits).
+    device="host": numpy uint8 [h][w][3] instead, computed on GPU 0."""
+    lib = load_host()
+    if isinstance(device, str):
+        if device != "host" or out is not None:
+            raise ValueError("device='host' (without out=) or a GPU ordinal")
+        return lib.decode_jpeg(jpeg, 0)
+    w, h = _jpeg_dimensions(jpeg)   # (the frame header alone: the stream is read once, by the decode, which checks the size)
+    if w <= 0 or h <= 0:
+        raise ValueError("not a JPEG: no frame header")
+    if out is None:
+        if device is None:
+            import torch
+            device = torch.cuda.current_device()
+        out = _new_device_tensor(w, h, dtype, layout, device)
+    ptr, name, strides, consumer, ordinal = _device_destination(out, w, h, layout, device)
+    lib.decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer if stream is None else int(stream), device=ordinal, size=(w, h))
+    return out
+
+
+def _with_decoded(job, decoded, w, h, ordinal):
+    """`job` followed by the decode of the bytes it returns -- every exit of the driver is covered by this one
+    mechanism -- into decoded= (True: a fresh uint8 [h][w][3] tensor on the encode's device).  Allocation and consumer
+    stream are taken here, in the CALLER's thread."""
+    if decoded is True:
+        decoded = _new_device_tensor(w, h, "uint8", "HWC", ordinal)
+    elif not is_device_resident(decoded):
+        raise TypeError("decoded=: True, or a device-resident image to fill")
+    layout = "HWC"
+    shape = tuple(decoded.shape) if hasattr(decoded, "shape") else tuple(decoded.__cuda_array_interface__["shape"])
+    if len(shape) == 3 and shape[0] == 3 and shape[2] != 3:
+        layout = "CHW"
+    ptr, name, strides, consumer, ordinal = _device_destination(decoded, w, h, layout, ordinal)
+
+    def run(**kw):
+        jpeg, info = job.run(**kw)
+        t0 = time.perf_counter()
+        load_host().decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h))
+        info.setdefault("timers", {})["decode_output"] = time.perf_counter() - t0
+        info["decoded"] = decoded
+        return jpeg, info
+    return _Job(run, job.producer, (job.keep, decoded))
+
+
+def _prepared(rgb, layout, device, stream, background=None, decoded=None):
     """What of an encode must happen in the CALLER's thread -- torch's current stream is a property of the thread."""
+    if decoded is not None and decoded is not False:
+        job = _prepared(rgb, layout, device, stream, background)
+        if is_device_resident(rgb):
+            _, w, h, _, _, _, ordinal, _ = _device_source(rgb, layout, device, _background(background))
+        else:
+            (h, w), ordinal = np.shape(rgb)[:2], 0 if device is None else device
+        return _with_decoded(job, decoded, w, h, ordinal)
     background = _background(background)
     if not is_device_resident(rgb):
         if layout not in (None, "HWC"):
@@ -359,7 +540,7 @@ def _prepared(rgb, layout, device, stream, background=None):
                 producer, rgb)
 
 
-def process(rgb, quality=95.0, layout=None, device=None, stream=None, background=None, **kw):
+def process(rgb, quality=95.0, layout=None, device=None, stream=None, background=None, decoded=None, **kw):
     """guetzli::Process of an image -> (jpeg_bytes, info).  `rgb` on the host: anything numpy turns into uint8
     [h][w][3].  `rgb` on the GPU -- a torch tensor with is_cuda, or an object with __cuda_array_interface__ -- is
     encoded where it is: uint8, uint16 (the high byte counts, as a 16-bit PNG is read), or float32 / float16 /
@@ -373,19 +554,26 @@ def process(rgb, quality=95.0, layout=None, device=None, stream=None, background
     blends over black, on bytes: (v * a + bg * (255 - a) + 128) // 255.  The raw samples of a PNG as a GPU tensor, with
     background=0, give the JPEG process_png gives.  Without background= such shapes are refused: nothing is blended
     silently.  With an opaque image it has no effect.  A uint8 host array [h][w][2] or [h][w][4] is blended by the same
-    rule in numpy."""
-    return _prepared(rgb, layout, device, stream, background).run(quality=quality, **kw)
+    rule in numpy.
+    decoded=True: info["decoded"] is the image the returned bytes decode to (decode() of them: a uint8 [h][w][3] torch
+    tensor on the encode's GPU, ready for work on the calling thread's current stream); decoded=tensor fills that image
+    instead ([h][w][3] or [3][h][w]; dtype and strides its own).  The time it takes is info["timers"]["decode_output"]."""
+    return _prepared(rgb, layout, device, stream, background, decoded).run(quality=quality, **kw)
 
 
-def process_many(batch, workers=4, layout=None, device=None, stream=None, background=None, **kw):
+def process_many(batch, workers=4, layout=None, device=None, stream=None, background=None, decoded=None, **kw):
     """A batch of images with `workers` of them in flight on one GPU (batch.encode_concurrent): a 4-D tensor
     [N,C,H,W] / [N,H,W,C] or a list of images, each as process() takes them (background= included).  Returns
     [(jpeg_bytes, info)] in order.
     The encodes run on worker threads, but every image's producer stream is the one process() would have taken in
     the CALLING thread, here and now: a batch made under `with torch.cuda.stream(s)` is encoded behind s.  (A
-    __cuda_array_interface__ stream of 2, the per-thread default stream, is refused: it names another stream there.)"""
+    __cuda_array_interface__ stream of 2, the per-thread default stream, is refused: it names another stream there.)
+    decoded=True: every info["decoded"] is that image's decoded output, as process() makes it; the tensors are allocated
+    here, on the calling thread's current stream, which is also the stream that may use them afterwards."""
     from .batch import encode_concurrent
-    jobs = [_prepared(batch[i], layout, device, stream, background) for i in range(len(batch))]
+    if decoded is not None and decoded is not False and decoded is not True:
+        raise ValueError("process_many(decoded=): True, or nothing -- one destination cannot take a batch")
+    jobs = [_prepared(batch[i], layout, device, stream, background, decoded) for i in range(len(batch))]
     if any(j.producer == PER_THREAD_STREAM for j in jobs):
         raise ValueError("a per-thread default stream cannot be waited for from the worker threads: synchronise it and "
                          "say stream=0, or encode with process()")

@@ -159,6 +159,49 @@ long gzh_process_jpeg(const uint8_t* data, long len, double quality, float targe
   return gzh_process_params(data, len, 0, 0, quality, target, ip, out, cap, trace, trace_cap, nullptr, 0);
 }
 
+// The size of a JPEG the reader accepts: wh[0..1] = width, height.  0, or -1 if the stream is rejected.
+long gzh_jpeg_size(const uint8_t* data, long len, int* wh) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0 || !wh) return -1;
+  return guetzli_amd::JpegSize(std::string((const char*)data, (size_t)len), &wh[0], &wh[1]) ? 0 : -1;
+  GZH_GUARD_END
+}
+
+// DecodeJpegToRGB into `out`, a gz_device_output (include/guetzli_amd.h) on GPU `device` that describes the JPEG's
+// w x h pixels (gzh_jpeg_size).  0, or -1 (message on stderr).
+// ... and _sized: the stream must hold w x h pixels (a destination sized from the frame header alone), else -1.
+long gzh_decode_jpeg_device_sized(const uint8_t* data, long len, int device, const gz_device_output* out, int w, int h) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0 || w < 0 || h < 0) return -1;
+  if (!out || out->struct_size != (int)sizeof(gz_device_output)) {
+    fprintf(stderr, "guetzli_amd: gzh_decode_jpeg_device: not a gz_device_output of this library\n");
+    return -1;
+  }
+  guetzli_amd::DeviceOutput o;
+  o.dtype = out->dtype;
+  o.data = out->data;
+  o.stride_y = out->stride_y; o.stride_x = out->stride_x; o.stride_c = out->stride_c;
+  o.consumer_stream = out->consumer_stream;
+  return guetzli_amd::DecodeJpegToRGB(std::string((const char*)data, (size_t)len), device, o, nullptr, nullptr, w, h) ? 0 : -1;
+  GZH_GUARD_END
+}
+long gzh_decode_jpeg_device(const uint8_t* data, long len, int device, const gz_device_output* out) {
+  return gzh_decode_jpeg_device_sized(data, len, device, out, 0, 0);
+}
+
+// DecodeJpegToRGB into packed host bytes: returns 3 * w * h (copied only if it fits `cap`: a larger size asks for a
+// retry with that much room -- the frame header says how much, gzh_jpeg_size), -1 on failure.
+long gzh_decode_jpeg(const uint8_t* data, long len, int device, uint8_t* host_rgb_out, long cap) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0) return -1;
+  std::vector<uint8_t> rgb;
+  int w = 0, h = 0;
+  if (!guetzli_amd::DecodeJpegToRGB(std::string((const char*)data, (size_t)len), device, &rgb, &w, &h)) return -1;
+  if (host_rgb_out && (long)rgb.size() <= cap) memcpy(host_rgb_out, rgb.data(), rgb.size());
+  return (long)rgb.size();
+  GZH_GUARD_END
+}
+
 double gzh_butteraugli_score_for_quality(double q) {
   return guetzli_amd::ButteraugliScoreForQuality(q);
 }

@@ -16,6 +16,10 @@ extern "C" int gz_downsample_silver(gz_ctx* ctx, int16_t* coeffs_out, uint64_t c
 extern "C" gz_ctx* gz_create_from_device_pixels(int device, int w, int h, const gz_device_pixels* img, float target, int* err) __attribute__((weak));
 extern "C" int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, int h, uint8_t* host_rgb_out) __attribute__((weak));
 
+// ... and the device-output entries: a stand-in without them refuses DecodeJpegToRGB.
+extern "C" int gz_decode_coeffs_device(int device, const int16_t* coeffs, int w, int h, int chroma_factor, const gz_device_output* out) __attribute__((weak));
+extern "C" int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h, int chroma_factor, uint8_t* host_rgb_out) __attribute__((weak));
+
 namespace guetzli_amd {
 
 // ------------------------------------------------------------- quality / score tables --
@@ -464,6 +468,119 @@ bool Encoder::RunDevice(const DeviceImage& image, int w, int h, std::string* out
   ctx_ = gz_create_from_device_pixels(params_.device, w, h, &img, params_.butteraugli_target, &err);
   if (!ctx_) return Fail("gz_create_from_device_pixels", err);
   return RunFromContext(start, out);
+}
+
+// ------------------------------------------------------------- DecodeJpegToRGB ------
+namespace {
+// The stream's dequantised coefficients in the frame layout of include/guetzli_amd.h, as RunJpeg lays out its original
+// (RemoveOriginalQuantization; of a 4:2:0 input the blocks inside the image's grid, CopyFromJpegComponent).  A
+// one-component file gets two zero chroma components, as CopyFromJpegData leaves them.
+bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs) {
+  JpegInput jpg;
+  if (!ReadJpeg((const uint8_t*)data.data(), data.size(), &jpg)) {
+    fprintf(stderr, "Can't read jpg data from input file\n");
+    return false;
+  }
+  const size_t ncomp = jpg.components.size();
+  if (!(ncomp == 1 || (ncomp == 3 && HasYCbCrColorSpace(jpg) && (jpg.Is420() || jpg.Is444())))) {   // DecodeJpegToRGB is empty
+    fprintf(stderr, "Unsupported input JPEG file (e.g. unsupported downsampling mode).\n");
+    return false;
+  }
+  const int w = jpg.width, h = jpg.height;
+  const int factor = ncomp == 3 && jpg.Is420() ? 2 : 1;
+  const int bw = (w + 7) / 8, bh = (h + 7) / 8, nb = bw * bh;
+  const int cbw = (w + 8 * factor - 1) / (8 * factor), cbh = (h + 8 * factor - 1) / (8 * factor), nbc = cbw * cbh;
+  coeffs->resize(((size_t)nb + 2 * (size_t)nbc) * 64);
+  if (ncomp == 1) std::fill(coeffs->begin() + (size_t)nb * 64, coeffs->end(), (int16_t)0);   // (every other block is written below)
+  for (size_t c = 0; c < ncomp; ++c) {
+    const JpegComponentIn& comp = jpg.components[c];
+    const int* q = jpg.quant[comp.quant_idx].values;
+    const int rw = c == 0 ? bw : cbw, rh = c == 0 ? bh : cbh;
+    if (comp.width_in_blocks < rw || comp.height_in_blocks < rh) {
+      fprintf(stderr, "guetzli_amd: the JPEG's block grid is smaller than its image\n");
+      return false;
+    }
+    int16_t* dst = coeffs->data() + (c == 0 ? (size_t)0 : (size_t)nb + (c - 1) * (size_t)nbc) * 64;
+    // (a quantiser is at most 65535 and a coefficient an int16: the product fits 32 bits; the check is kept out of the
+    // loop's control flow so that the loop stays a vector loop -- 25 M coefficients at 4K)
+    int32_t qv[64];
+    for (int k = 0; k < 64; ++k) qv[k] = q[k];
+    int32_t wide = 0;
+    for (int by = 0; by < rh; ++by) {
+      const int16_t* src = &comp.coeffs[(size_t)by * comp.width_in_blocks * 64];
+      for (int bx = 0; bx < rw; ++bx, dst += 64, src += 64)
+        for (int k = 0; k < 64; ++k) {
+          const int32_t v = (int32_t)src[k] * qv[k];
+          dst[k] = (int16_t)v;
+          wide |= v ^ (int32_t)(int16_t)v;
+        }
+    }
+    if (wide != 0) {   // a product that does not fit the frame's int16
+      fprintf(stderr, "Unsupported input JPEG (unexpectedly large coefficient values).\n");
+      return false;
+    }
+  }
+  *w_out = w; *h_out = h; *factor_out = factor;
+  return true;
+}
+
+// The coefficients between the reader and the upload, kept per thread as the encoder's scratch is: a decode after the
+// first of a size touches no fresh pages (50 MB at 4K).
+std::vector<int16_t>& DecodeScratchCoeffs() {
+  static thread_local std::vector<int16_t> v;
+  return v;
+}
+
+bool DecodeFailed(const char* what, int rc) {
+  fprintf(stderr, "guetzli_amd: %s failed: %s\n", what, gz_strerror(rc));
+  return false;
+}
+}  // namespace
+
+bool JpegSize(const std::string& jpeg, int* w, int* h) {
+  JpegInput jpg;
+  if (!ReadJpeg((const uint8_t*)jpeg.data(), jpeg.size(), &jpg)) {
+    fprintf(stderr, "Can't read jpg data from input file\n");
+    return false;
+  }
+  if (w) *w = jpg.width;
+  if (h) *h = jpg.height;
+  return true;
+}
+
+bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w_out, int* h_out, int expect_w,
+                     int expect_h) {
+  int w = 0, h = 0, factor = 1;
+  std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
+  if (!DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs)) return false;
+  if (w_out) *w_out = w;
+  if (h_out) *h_out = h;
+  if ((expect_w > 0 || expect_h > 0) && (w != expect_w || h != expect_h)) {
+    fprintf(stderr, "guetzli_amd: the JPEG holds %d x %d pixels, the destination was made for %d x %d\n", w, h, expect_w, expect_h);
+    return false;
+  }
+  if (!gz_decode_coeffs_device) return DecodeFailed("device-resident output (not in this device library)", GZ_E_STATE);
+  gz_device_output o;
+  memset(&o, 0, sizeof(o));
+  o.struct_size = (int)sizeof(o);
+  o.dtype = out.dtype;
+  o.data = out.data;
+  o.stride_y = out.stride_y; o.stride_x = out.stride_x; o.stride_c = out.stride_c;
+  o.consumer_stream = out.consumer_stream;
+  const int rc = gz_decode_coeffs_device(device, coeffs.data(), w, h, factor, &o);
+  return rc == GZ_OK ? true : DecodeFailed("gz_decode_coeffs_device", rc);
+}
+
+bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w_out, int* h_out) {
+  int w = 0, h = 0, factor = 1;
+  std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
+  if (!DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs)) return false;
+  if (w_out) *w_out = w;
+  if (h_out) *h_out = h;
+  if (!gz_decode_coeffs) return DecodeFailed("gz_decode_coeffs (not in this device library)", GZ_E_STATE);
+  rgb->resize((size_t)3 * w * h);
+  const int rc = gz_decode_coeffs(device, coeffs.data(), w, h, factor, rgb->data());
+  return rc == GZ_OK ? true : DecodeFailed("gz_decode_coeffs", rc);
 }
 
 bool Process(const Params& params, ProcessStats* stats, const std::vector<uint8_t>& rgb, int w,

@@ -60,6 +60,16 @@ struct DeviceImage {
   uint8_t background[3] = {0, 0, 0};  // r, g, b
 };
 
+// gz_device_output of include/guetzli_amd.h: where decoded pixels go, a w x h x 3 image in the memory of GPU `device`.
+// Element (y, x, c) is data[y*stride_y + x*stride_x + c*stride_c], strides in elements; no two elements may share an
+// address.  A byte b arrives as b (kU8), b * 257 (kU16) or b / 255 (the three float types).
+struct DeviceOutput {
+  int dtype = DeviceImage::kU8;       // DeviceImage::Dtype
+  void* data = nullptr;               // device address of element (0, 0, 0)
+  int64_t stride_y = 0, stride_x = 0, stride_c = 0;
+  void* consumer_stream = nullptr;    // hipStream_t that used the memory before and reads it after; nullptr: none
+};
+
 double ButteraugliScoreForQuality(double quality);                       // quality.cc:78-85
 double ScoreJPEG(double butteraugli_distance, int size, double target);  // score.cc:23-41
 
@@ -83,5 +93,19 @@ bool Process(const Params& params, ProcessStats* stats, const DeviceImage& image
 // refuses them, processor.cc:811-823).
 bool Process(const Params& params, ProcessStats* stats, const std::string& jpeg_data,
              std::string* out);
+
+// guetzli::DecodeJpegToRGB (jpeg_data_decoder.cc:45-54) with the pixels left on the GPU: the stream is read on the host
+// (jpeg_reader.h), its coefficients are dequantised, and the device computes OutputImage::ToSRGB of them -- the pixel
+// model every butteraugli distance of a search is computed on -- into `out`.  Accepts what the reference's function
+// returns pixels for: one component (grey: the two chroma components are zero), or three with a YCbCr colour space in
+// 4:4:4 or 4:2:0; everything else is refused with a message on stderr and false.  *w, *h (either may be null) receive
+// the image's size -- `out` must describe that many pixels: JpegSize tells beforehand, and a caller that has sized
+// `out` some other way says for which size (expect_w, expect_h > 0): a stream of another size is refused, not written.
+bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w, int* h, int expect_w = 0,
+                     int expect_h = 0);
+// The same into packed host bytes, rgb[(y * w + x) * 3 + c].
+bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w, int* h);
+// The size the frame header declares (of a stream ReadJpeg accepts).
+bool JpegSize(const std::string& jpeg, int* w, int* h);
 
 }  // namespace guetzli_amd

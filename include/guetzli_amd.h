@@ -54,7 +54,9 @@ int gz_abi_version(void);                 /* currently 6 (5 without the two expe
                                              device-input entries (gz_device_image, gz_create_from_device,
                                              gz_set_rgb_device, gz_pack_rgb_device) were ADDED to version 6: no
                                              existing declaration, struct or call sequence changed, so the number stays;
-                                             so were gz_device_pixels and its three entries, by the same rule */
+                                             so were gz_device_pixels and its three entries, and gz_device_output and
+                                             its three (gz_decode_coeffs_device, gz_decode_coeffs,
+                                             gz_reconstruct_device), by the same rule */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -177,7 +179,7 @@ int gz_pack_rgb_device(int device, const gz_device_image* img, int w, int h, uin
  * stride, an extent -- the alpha extent (h-1) stride_y + (w-1) stride_x included -- beyond 62 bits; alpha gets data's
  * pointer checks (readable by the context's device, its extent inside its allocation; a host pointer is GZ_E_ARG and
  * gz_last_error names alpha). */
-#define GZ_DT_U16 4                      /* gz_device_pixels only */
+#define GZ_DT_U16 4                      /* gz_device_pixels and gz_device_output only */
 typedef struct gz_device_pixels {
   int struct_size;            /* sizeof(gz_device_pixels) */
   int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 / GZ_DT_U16 */
@@ -276,6 +278,48 @@ int gz_apply_coeff_edits(gz_ctx* ctx, const int32_t* pos, const int16_t* val, in
  * OutputImage::ToSRGB (output_image.cc:411-425) and ToLinearRGB (:427-440).
  * srgb: w*h*3 uint8 or NULL; linear: 3 planes of w*h float or NULL. */
 int gz_reconstruct(gz_ctx* ctx, uint8_t* srgb, float* linear);
+
+/* Device-resident output ----------------------------------------------------------
+ * The decoded pixels as a strided image in DEVICE memory of the caller's (a tensor a model, a metric or the next
+ * stage reads): element (y, x, c) of the w x h x 3 image is data[y*stride_y + x*stride_x + c*stride_c], strides in
+ * ELEMENTS -- HWC, CHW, cropped views inside a larger tensor, any element alignment of the base.  One kernel
+ * (k_emit_rgb, the mirror of the ingest kernel) converts the packed bytes of OutputImage::ToSRGB
+ * (output_image.cc:411-425) and writes exactly the w*h*3 elements of the image: what lies between them stays as it is.
+ * Element of a byte b: GZ_DT_U8 b; GZ_DT_U16 b * 257 (its high byte is b: the input rule gives b back); GZ_DT_F32
+ * (float)b / 255.0f, the IEEE quotient (not b * (1/255.f)); GZ_DT_F16 / GZ_DT_BF16 that float rounded to nearest, ties to
+ * even.  Under the input side's byte rule every such element is b again.
+ * GZ_E_ARG (before any device call): NULL out or data, a wrong struct_size, an unknown dtype, a negative stride, an
+ * extent whose last element offset does not fit 62 bits, and strides under which two of the w*h*3 elements would share
+ * an address: with the three (stride, count) pairs ordered by stride, every stride must be at least the stride times
+ * the count of the pair before it, and at least 1 -- a stride of 0 is an input convenience and an output error.  (A
+ * dimension of one element -- h or w of 1 -- addresses nothing: its stride is not looked at.)
+ * The memory must be device memory of that device that a kernel may write (or managed / mapped page-locked memory),
+ * its extent inside its allocation: an ordinary host pointer is GZ_E_ARG, not a fault.
+ * Stream contract, both directions: consumer_stream is the hipStream_t that used the memory before the call and
+ * reads it afterwards.  The library's stream first waits for an event recorded there (a caching allocator may have
+ * handed the memory out while earlier work of that stream still uses it), and behind the kernel that stream waits for
+ * an event recorded on the library's: work enqueued on it after the call sees the pixels, with no host
+ * synchronisation of the consumer.  NULL: the call synchronises its own stream before it returns, and the memory must
+ * not be in use when it starts.  (The context-free entries wait for their own work in either case -- their temporaries
+ * go back to the pool -- gz_reconstruct_device with a consumer stream returns behind the enqueue.) */
+typedef struct gz_device_output {
+  int struct_size;            /* sizeof(gz_device_output) */
+  int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 / GZ_DT_U16 */
+  void* data;                 /* device address of element (0,0,0) */
+  int64_t stride_y, stride_x, stride_c;   /* elements */
+  void* consumer_stream;      /* hipStream_t that used the memory before and reads it after; NULL = none */
+} gz_device_output;
+/* guetzli::DecodeJpegToRGB's arithmetic (jpeg_data_decoder.cc:45-54: OutputImage::ToSRGB of CopyFromJpegData's image)
+ * without a context: coeffs = DEQUANTISED coefficients in host memory, in the frame layout of this header
+ * ([3][nb][64] for chroma_factor 1; nb + 2*nbc blocks for chroma_factor 2), written into out.  0 < w, h < 65536 and
+ * gz_create's block limit; no lower bound: a 1 x 1 image decodes.  Temporaries (the coefficients, the chroma samples,
+ * 3*w*h bytes) come from the device pool, all of them or none: GZ_E_NOMEM leaves nothing behind. */
+int gz_decode_coeffs_device(int device, const int16_t* coeffs, int w, int h, int chroma_factor,
+                            const gz_device_output* out);
+/* The same into packed host bytes w*h*3: what gz_reconstruct returns as srgb, without a context. */
+int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h, int chroma_factor, uint8_t* host_rgb_out);
+/* The candidate of a context, as gz_reconstruct's srgb, into out (the context's w and h). */
+int gz_reconstruct_device(gz_ctx* ctx, const gz_device_output* out);
 
 /* Double-precision DCT -----------------------------------------
  * gz_dct_double_blocks: ComputeBlockDCTDouble (inverse == 0) / ComputeBlockIDCTDouble
