@@ -75,6 +75,19 @@ def device_output(ptr, dtype, strides, stream=0):
     return GzDeviceOutput(C.sizeof(GzDeviceOutput), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None)
 
 
+class GzDeviceMap(C.Structure):
+    """gz_device_map of include/guetzli_amd.h: where a distance map goes, a strided w x h image in device memory."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_y", C.c_int64), ("stride_x", C.c_int64),
+                ("consumer_stream", _P)]
+
+
+def device_map(ptr, dtype, strides, stream=0):
+    """A GzDeviceMap: ptr = device address of element (0, 0), dtype = GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16, strides =
+    (y, x) in elements, stream = the hipStream_t that used the memory before and reads it afterwards (0: none)."""
+    sy, sx = (int(v) for v in strides)
+    return GzDeviceMap(C.sizeof(GzDeviceMap), int(dtype), int(ptr) or None, sy, sx, int(stream) or None)
+
+
 # name -> (restype, argtypes); mirrors include/guetzli_amd.h one to one
 SIGNATURES = {
     "gz_abi_version": (_I, []),
@@ -98,6 +111,10 @@ SIGNATURES = {
     "gz_decode_coeffs_device": (_I, [_I, _P, _I, _I, _I, _P]),
     "gz_decode_coeffs": (_I, [_I, _P, _I, _I, _I, _P]),
     "gz_reconstruct_device": (_I, [_P, _P]),
+    "gz_compare_device_pixels": (_I, [_P, _P, _P, _P]),
+    "gz_compare_rgb": (_I, [_P, _P, _P, _P]),
+    "gz_distmap_device": (_I, [_P, _P]),
+    "gz_probe_emit_map": (_I, [_I, _P, _I, _I, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -361,6 +378,13 @@ class Library:
         co = np.ascontiguousarray(coeffs, np.int16)
         self.check(self.lib.gz_decode_coeffs_device(device, _ptr(co), w, h, chroma_factor, C.byref(output)))
 
+    def probe_emit_map(self, plane, dmap, device=0):
+        """gz_probe_emit_map: the float32 [h][w] `plane` (any bit patterns) through the map's emit kernel alone, into
+        `dmap` (device_map(...))."""
+        p = np.ascontiguousarray(plane, np.float32)
+        h, w = p.shape
+        self.check(self.lib.gz_probe_emit_map(device, _ptr(p), w, h, C.byref(dmap)))
+
 
 class Context:
     """One (image, GPU) context == one guetzli::ButteraugliComparator + OutputImage."""
@@ -554,6 +578,27 @@ class Context:
         bm = np.zeros(self.nb, np.float32) if want_block_max else None
         self._chk(self.L.lib.gz_compare(self.handle, _ptr(dist), _ptr(dm), _ptr(bm)))
         return float(dist[0]), dm, bm
+
+    def compare_device_pixels(self, other, dmap=None):
+        """gz_compare_device_pixels: the distance of the device-resident image `other` (device_pixels(...), w x h) from
+        the context's original, which is the reference; dmap (device_map(...)): where the distance map goes."""
+        dist = np.zeros(1, np.float32)
+        self._chk(self.L.lib.gz_compare_device_pixels(self.handle, C.byref(other), _ptr(dist),
+                                                      None if dmap is None else C.byref(dmap)))
+        return float(dist[0])
+
+    def compare_rgb(self, rgb, want_distmap=True):
+        """gz_compare_rgb: the same for host bytes uint8 [h][w][3] -> (distance, float32 [h][w] map or None)."""
+        px = np.ascontiguousarray(rgb, np.uint8)
+        assert px.shape == (self.h, self.w, 3)
+        dist = np.zeros(1, np.float32)
+        dm = np.zeros((self.h, self.w), np.float32) if want_distmap else None
+        self._chk(self.L.lib.gz_compare_rgb(self.handle, _ptr(px), _ptr(dist), _ptr(dm)))
+        return float(dist[0]), dm
+
+    def distmap_device(self, dmap):
+        """gz_distmap_device: the distance map of the last comparison that stored one, into dmap (device_map(...))."""
+        self._chk(self.L.lib.gz_distmap_device(self.handle, C.byref(dmap)))
 
     def compare_begin(self):
         self._chk(self.L.lib.gz_compare_begin(self.handle))

@@ -215,6 +215,7 @@ static int opsin_tile_rows(const gz_ctx*) { return kSmallTileRows; }   // (of a 
 // them; the caller joins that stream before k_combine (stage_diffmap).  Its row-pass result goes through the
 // distance-map plane, which nothing else touches before the chain's last kernel.
 int stage_separate(gz_ctx* c, const ChainStreams& cs, Psycho* ps) {
+  c->have_map_plane = false;   // (the plane is written below: whatever map it held is gone)
   TRY(fork(c, cs.main, cs.side2, c->ev_xyb));
   {
     SrcPack<SrcPlain, 1> s; PlanePack<1> t;
@@ -572,7 +573,7 @@ static int check_opsin_ahead(gz_ctx* c, hipStream_t stream) {
 
 // One full Compare of the current candidate, everything on the stream (and, forked, the two side streams).
 // want without kWantDistmap (the search loop, gz_time_compare): the last kernel leaves the per-block maxima and the
-// image maximum only; c->distmap then holds no distance map (have_distmap_plane).
+// image maximum only; c->distmap then holds no distance map (have_map_plane).
 // The candidate's linear planes: reconstructed here, unless every change of the candidate since the last full
 // reconstruction was patched into them by the call that made it (c->lin_is_cand; the search loop's steady state:
 // a fifth of a 4K image's blocks change per iteration).  kWholeChain: gz_time_compare, whose repetitions change

@@ -408,6 +408,9 @@ struct gz_ctx {
   // depends on that buffer before its first copy or launch.  RE-ARM ONLY ON SUCCESS -- a claim is set again only as the
   // last state change before `return GZ_OK`.  Dropping is always safe: it costs one full reconstruction or opsin pass.
   bool have_orig = false, have_cand = false, have_distmap = false;
+  // c->distmap holds the distance map of the last comparison (gz_distmap_device emits it): only a comparison asked for
+  // its map stores one (kWantDistmap), and the plane is scratch of every SeparateFrequencies (stage_separate drops this)
+  bool have_map_plane = false;
   // lin[] holds the reconstruction of d_cand as it is now (4:4:4 frames; cfg.patch_reconstruct): set by the Compare
   // chain's full reconstruction, kept by the mutators that transform the block positions they change
   // (gz_apply_candidate_steps, gz_apply_coeff_edits: PatchClaims), dropped by everything else that writes d_cand or lin[]
@@ -566,7 +569,7 @@ void set_frame(gz_ctx* c, int factor) {
   c->have_search = false;
   c->pending.void_up_to(Pending::kEverything);
   c->scan_pending = false;
-  c->have_distmap = false;
+  c->have_distmap = c->have_map_plane = false;
   c->have_scan = false;
 }
 size_t csamp_plane(const gz_ctx* c) {   // bytes of one chroma sample plane of a 4:2:0 frame

@@ -153,6 +153,7 @@ int gz_compare(gz_ctx* c, float* distance, float* distmap, float* block_max) {
     c->h_block_max_valid = true;
   }
   c->have_distmap = true;
+  c->have_map_plane = distmap != nullptr || c->cfg.store_distmap != 0;
   return GZ_OK;
 }
 
@@ -187,6 +188,7 @@ int gz_compare_end(gz_ctx* c, float* distance) {
   }
   *distance = c->last_distance;
   c->have_distmap = true;
+  c->have_map_plane = c->cfg.store_distmap != 0;
   c->pending.distance_taken();
   return GZ_OK;
 }
@@ -196,6 +198,7 @@ int gz_compare_enqueue(gz_ctx* c, int iters) {
   if (!c || iters < 0) return GZ_E_ARG;
   if (!c->have_cand) { c->err = "no candidate coefficients"; return GZ_E_STATE; }
   for (int i = 0; i < iters; ++i) TRY(enqueue_compare(c, kWantBlockMax | kWholeChain));   // (always the whole chain, as gz_time_compare)
+  c->have_map_plane = iters > 0 && c->cfg.store_distmap != 0;
   return GZ_OK;
 }
 
@@ -221,6 +224,7 @@ int gz_time_compare(gz_ctx* c, int iters, float* total_ms) {
   HIPCHK(c, hipEventRecord(e1, c->stream));
   HIPCHK(c, hipEventSynchronize(e1));
   HIPCHK(c, hipEventElapsedTime(total_ms, e0, e1));
+  c->have_map_plane = c->cfg.store_distmap != 0;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return GZ_OK;

@@ -1,0 +1,178 @@
+// C ABI: the butteraugli distance of an image PAIR -- the context's original against pixels that are no JPEG candidate
+// of it (gz_compare_device_pixels, gz_compare_rgb) -- and the distance map left on the device (gz_device_map,
+// gz_distmap_device), written into the caller's strided device image by k_emit_map.
+// (part of the one translation unit gz_api.hip, which includes these files in order -- no declaration here is visible
+// outside libguetzli_amd.so but the C ABI)
+#pragma once
+
+extern "C" {
+
+// The arguments alone: no device call (the library answers these without a GPU).
+static int check_device_map(const gz_device_map* map, int w, int h) {
+  if (!map || map->struct_size != (int)sizeof(gz_device_map) || !map->data) return GZ_E_ARG;
+  if (map->dtype != GZ_DT_F32 && map->dtype != GZ_DT_F16 && map->dtype != GZ_DT_BF16) return GZ_E_ARG;
+  if (map->stride_y < 0 || map->stride_x < 0) return GZ_E_ARG;
+  if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) return GZ_E_ARG;
+  // the last element's offset (h-1) sy + (w-1) sx in 62 bits: every term is bounded before it is formed
+  const uint64_t lim = (1ull << 62) - 1;
+  const uint64_t sy = (uint64_t)map->stride_y, sx = (uint64_t)map->stride_x;
+  if ((h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1))) return GZ_E_ARG;
+  if (sy * (uint64_t)(h - 1) + sx * (uint64_t)(w - 1) > lim) return GZ_E_ARG;
+  // No two of the w * h elements at one address: check_device_output's rule for two dimensions.
+  std::pair<uint64_t, uint64_t> dim[2] = {{sy, (uint64_t)h}, {sx, (uint64_t)w}};
+  std::sort(dim, dim + 2);
+  uint64_t least = 1;
+  for (const auto& d : dim) {
+    if (d.second == 1) continue;
+    if (d.first < least) return GZ_E_ARG;
+    least = d.first * d.second;
+  }
+  return GZ_OK;
+}
+
+static uint64_t device_map_last(const gz_device_map* map, int w, int h) {
+  return (uint64_t)map->stride_y * (uint64_t)(h - 1) + (uint64_t)map->stride_x * (uint64_t)(w - 1);
+}
+
+// k_emit_map on `stream`: plane (pitch floats per row) -> map (checked by the caller).
+static void launch_map(hipStream_t stream, const float* plane, int w, int h, int pitch, const gz_device_map* map) {
+  const long long sy = map->stride_y, sx = map->stride_x;
+  switch (map->dtype) {
+    case GZ_DT_F32: launch_emit_map(stream, plane, w, h, pitch, (float*)map->data, sy, sx); break;
+    case GZ_DT_F16: launch_emit_map(stream, plane, w, h, pitch, (ingest_f16*)map->data, sy, sx); break;
+    default: launch_emit_map(stream, plane, w, h, pitch, (ingest_bf16*)map->data, sy, sx); break;
+  }
+}
+
+// c->distmap -> map on the context's stream, under gz_device_output's stream contract in both directions (the
+// consumer's stream is waited for before the kernel and waits for it afterwards).  Nothing is waited for on the host.
+static int emit_distmap(gz_ctx* c, const gz_device_map* map) {
+  if (map->consumer_stream) {
+    if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
+    HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, map->consumer_stream));
+  }
+  launch_map(c->stream, c->distmap, c->w, c->h, c->pitch, map);
+  KCHK(c);
+  if (map->consumer_stream) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, map->consumer_stream));
+  return GZ_OK;
+}
+
+// What a pair comparison drops before its first copy or launch (context.h, DROP BEFORE WRITE): lin[] and xyb[] take the
+// other image, the map and the block maxima are about to be replaced.  The candidate, the original and the frame stay.
+static void pair_compare_drops(gz_ctx* c) {
+  c->lin_is_cand = c->xyb_is_cand = false;
+  c->have_distmap = c->h_block_max_valid = c->have_map_plane = false;
+}
+
+// lin[] holds the other image's linear planes: the chain from its second kernel on, as enqueue_compare runs it behind
+// the reconstruction -- against pi0, the image maximum cleared by a fill -- then the map's two exits and the distance.
+static int pair_compare_tail(gz_ctx* c, float* distance, const gz_device_map* map, float* host_map) {
+  const bool want_map = map != nullptr || host_map != nullptr;
+  const ChainStreams cs = chain_streams(c, !single_stream_wanted(c));
+  TRY(stage_opsin(c, cs.main));
+  TRY(stage_separate(c, cs, &c->pi1));
+  TRY(stage_diffmap(c, cs, c->pi0, c->pi1, kWantBlockMax | (want_map ? kWantDistmap : 0u), ClearMax::kMemset));
+  if (map) TRY(emit_distmap(c, map));
+  void* res = nullptr;
+  TRY(result_buffer(c, 4, &res));
+  HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits, 4, hipMemcpyDeviceToHost, c->stream));
+  if (host_map) TRY(download_plane(c, c->distmap, host_map));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // (for the distance: the consumer of a map does not wait for this)
+  memcpy(&c->last_distance, res, 4);
+  *distance = c->last_distance;
+  c->have_distmap = true;
+  c->have_map_plane = want_map;
+  return GZ_OK;
+}
+
+static int pair_compare_state(gz_ctx* c, const char* who) {
+  if (c->pending.busy()) { c->err = std::string(who) + " while a Compare or phase-B work of the context is in flight"; return GZ_E_STATE; }
+  return GZ_OK;
+}
+
+int gz_compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float* distance, const gz_device_map* map) {
+  if (!c || !distance) return GZ_E_ARG;
+  if (check_device_pixels(other, c->w, c->h) != GZ_OK) return GZ_E_ARG;   // (before any device call)
+  if (map && check_device_map(map, c->w, c->h) != GZ_OK) return GZ_E_ARG;
+  DeviceScope ds_(c);
+  if (const int rc = check_device_pointer(c->device, other, c->w, c->h, &c->err)) return rc;
+  if (map)
+    if (const int rc = check_device_range(c->device, map->data, device_map_last(map, c->w, c->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
+  TRY(pair_compare_state(c, "gz_compare_device_pixels"));
+  pair_compare_drops(c);
+  if (other->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
+    if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
+    HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)other->producer_stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
+  }
+  // the packed bytes go to the reconstruction's scratch: d_rgb is the original's, and stays
+  launch_ingest(c->stream, other, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+  KCHK(c);
+  return pair_compare_tail(c, distance, map, nullptr);   // (its synchronise: `other` is read when the call returns)
+}
+
+int gz_compare_rgb(gz_ctx* c, const uint8_t* host_rgb, float* distance, float* host_distmap) {
+  DeviceScope ds_(c);
+  if (!c || !host_rgb || !distance) return GZ_E_ARG;
+  TRY(pair_compare_state(c, "gz_compare_rgb"));
+  pair_compare_drops(c);
+  HIPCHK(c, hipMemcpyAsync(c->d_srgb_out, host_rgb, (size_t)3 * c->w * c->h, hipMemcpyHostToDevice, c->stream));
+  GZ_LAUNCH(k_linear_from_rgb8, dim3(gz_div_up(c->w, 256), c->h), dim3(256), c->stream, c->d_srgb_out, c->w, c->h, c->pitch,
+            c->plane, c->d_srgb_lut, c->lin[0]);
+  KCHK(c);
+  return pair_compare_tail(c, distance, nullptr, host_distmap);
+}
+
+int gz_distmap_device(gz_ctx* c, const gz_device_map* map) {
+  if (!c) return GZ_E_ARG;
+  if (check_device_map(map, c->w, c->h) != GZ_OK) return GZ_E_ARG;
+  DeviceScope ds_(c);
+  if (const int rc = check_device_range(c->device, map->data, device_map_last(map, c->w, c->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
+  if (!c->have_map_plane) { c->err = "the last comparison stored no distance map"; return GZ_E_STATE; }
+  TRY(emit_distmap(c, map));
+  if (map->consumer_stream) return GZ_OK;   // (ordered on the device: nothing to wait for here)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GZ_OK;
+}
+
+#ifndef GZ_NO_PROBES
+namespace {
+struct ProbeMapScratch {   // the plane from the device pool and a pooled event, given back on every path
+  void* plane = nullptr;
+  hipEvent_t ev = nullptr;
+  ~ProbeMapScratch() { pool_free(plane); pool_event_destroy(ev); }
+};
+int probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map) {
+  if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
+  if (check_device_range(device, map->data, device_map_last(map, w, h), ingest_elem_size(map->dtype), "map", nullptr) != GZ_OK) return GZ_E_ARG;
+  ProbeMapScratch s;
+  const size_t bytes = sizeof(float) * (size_t)w * h;
+  {
+    const hipError_t e = pool_malloc(&s.plane, bytes);
+    if (e != hipSuccess) { s.plane = nullptr; (void)hipGetLastError(); return e == hipErrorOutOfMemory ? GZ_E_NOMEM : GZ_E_HIP; }
+  }
+  const hipStream_t stream = (hipStream_t)0;
+  if (hipMemcpy(s.plane, host_plane, bytes, hipMemcpyHostToDevice) != hipSuccess) return GZ_E_HIP;
+  if (map->consumer_stream) {
+    if (pool_event_create(&s.ev) != hipSuccess) { s.ev = nullptr; return GZ_E_HIP; }
+    if (emit_after_consumer(stream, s.ev, map->consumer_stream) != hipSuccess) return GZ_E_HIP;
+  }
+  launch_map(stream, (const float*)s.plane, w, h, w, map);
+  int rc = hipGetLastError() == hipSuccess ? GZ_OK : GZ_E_HIP;
+  if (rc == GZ_OK && map->consumer_stream && consumer_after_emit(stream, s.ev, map->consumer_stream) != hipSuccess) rc = GZ_E_HIP;
+  if (hipStreamSynchronize(stream) != hipSuccess) rc = GZ_E_HIP;   // (the plane goes back to the pool behind this)
+  return rc;
+}
+}  // namespace
+
+int gz_probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map) {
+  if (!host_plane || check_device_map(map, w, h) != GZ_OK) return GZ_E_ARG;   // (before any device call)
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  const int rc = probe_emit_map(device, host_plane, w, h, map);
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
+  return rc;
+}
+#endif  // GZ_NO_PROBES
+
+}  // extern "C"

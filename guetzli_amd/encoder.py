@@ -588,3 +588,202 @@ def read_png(data):
 def process_png(data, quality=95.0, **kw):
     """`guetzli --quality Q in.png out.jpg`: ReadPNG + Process.  Returns (jpeg_bytes, info)."""
     return load_host().process(load_host().read_png(data), quality=quality, **kw)
+
+
+# ---- the butteraugli distance of two images (capi: gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device) ----
+MAP_DTYPES = ("float32", "float16", "bfloat16")
+
+
+def _pair_library():
+    """The C-ABI library the image-pair metric runs on (the product's; there is no other)."""
+    from .capi import load
+    return load()
+
+
+def _map_destination(x, w, h, device):
+    """(ptr, dtype name, element strides (y, x), consumer stream, device ordinal) of the device-resident 2-D image `x`
+    that is to receive a w x h distance map: _device_destination for one plane of floats."""
+    if getattr(x, "is_cuda", False):   # a torch tensor
+        import torch
+        name = str(x.dtype).replace("torch.", "")
+        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        if device is not None and device != ordinal:
+            raise ValueError(f"distmap= lives on device {ordinal}, the images on device {device}")
+        shape, strides = tuple(x.shape), tuple(x.stride())
+        ptr, stream = x.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream
+    elif hasattr(x, "__cuda_array_interface__"):
+        cai = x.__cuda_array_interface__
+        dt = np.dtype(cai["typestr"])
+        if cai["data"][1]:
+            raise ValueError("distmap= is read-only (its __cuda_array_interface__ says so)")
+        name, shape = dt.name, tuple(cai["shape"])
+        if cai.get("strides") is None:
+            byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
+        else:
+            byte_strides = tuple(cai["strides"])
+        if any(b % dt.itemsize for b in byte_strides):
+            raise ValueError("strides that are no multiple of the element size")
+        strides = tuple(b // dt.itemsize for b in byte_strides)
+        stream = cai.get("stream") or 0   # (as _device_source reads it)
+        if stream == 1:
+            stream = 0
+        ptr, ordinal = cai["data"][0], 0 if device is None else device
+    else:
+        raise TypeError("distmap=: True, or a device-resident 2-D image to fill")
+    if name not in MAP_DTYPES:
+        raise TypeError(f"distmap= has dtype {name}: float32, float16 or bfloat16")
+    if shape != (h, w):
+        raise ValueError(f"distmap= has shape {shape}, the images' map is {(h, w)}")
+    if min(strides) < 0:
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    if _strides_alias(strides, (h, w)):
+        raise ValueError(f"distmap= has strides {strides} under which two of its elements share an address (an expanded view?)")
+    return ptr, name, strides, stream, ordinal
+
+
+def _new_map_tensor(w, h, ordinal):
+    """A fresh float32 [h][w] torch tensor on GPU `ordinal`, from the calling thread's current stream."""
+    import torch
+    return torch.empty((h, w), dtype=torch.float32, device=f"cuda:{ordinal}")
+
+
+class _PairImage:
+    """One image of a pair, looked at but not touched: host bytes (rgb) or the description of device-resident pixels
+    (pixels, a capi.GzDevicePixels; keep: the object that owns the memory)."""
+
+    def __init__(self, w, h, rgb=None, pixels=None, ordinal=None, keep=None):
+        self.w, self.h, self.rgb, self.pixels, self.ordinal, self.keep = w, h, rgb, pixels, ordinal, keep
+
+
+def _pair_image(x, layout, device, stream, background):
+    """`x` as process() accepts it -> _PairImage.  No device call."""
+    background = _background(background)
+    if not is_device_resident(x):
+        if layout not in (None, "HWC"):
+            raise ValueError("host pixels are [h][w][3]")
+        if stream is not None:
+            raise ValueError("stream= goes with device-resident pixels")
+        px = np.asarray(x)
+        if background is not None and px.dtype == np.uint8 and px.ndim == 3 and px.shape[2] in (2, 4):
+            px = blend_on_background(px, background)
+        rgb = np.ascontiguousarray(px, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"host pixels are [h][w][3], not {rgb.shape}")
+        return _PairImage(rgb.shape[1], rgb.shape[0], rgb=rgb)
+    ptr, w, h, dtype, strides, producer, ordinal, alpha = _device_source(x, layout, device, background)
+    if stream is not None:
+        producer = int(stream)
+    if any(s < 0 for s in strides) or (alpha or 0) < 0:
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    code = DTYPE_CODES[dtype]
+    alpha_ptr = 0 if alpha is None else int(ptr) + int(alpha) * ITEMSIZE[code]
+    if alpha is not None and not alpha_ptr:
+        raise ValueError("an alpha sample at address 0")
+    return _PairImage(w, h, pixels=device_pixels(ptr, code, strides, producer, alpha_ptr, background or (0, 0, 0)),
+                      ordinal=ordinal, keep=x)
+
+
+def _pair_sizes(ref, other):
+    if min(ref.w, ref.h) < 8:
+        raise ValueError(f"a {ref.w} x {ref.h} image: butteraugli needs at least 8 x 8")
+    if other is not None and (other.w, other.h) != (ref.w, ref.h):
+        raise ValueError(f"the images differ in size: {ref.w} x {ref.h} against {other.w} x {other.h}")
+
+
+class Comparator:
+    """One reference image against many distorted ones: the reference's psycho image (OpsinDynamicsImage +
+    SeparateFrequencies + its half of the mask) is computed once, here, and kept on the GPU.  `reference` as process()
+    accepts an image -- host pixels numpy turns into uint8 [h][w][3], or a GPU tensor / __cuda_array_interface__ object
+    of any dtype, layout and strides process() takes, with layout=, background= and stream= as there.
+    The metric is ASYMMETRIC: this image is butteraugli's first argument, the one the masking is computed from.  The
+    bytes compared are the bytes process() would encode (floats in [0, 1] rounded to bytes, uint16's high byte, alpha
+    blended over background=).  A context manager; close() frees the GPU memory."""
+
+    def __init__(self, reference, layout=None, device=None, stream=None, background=None):
+        ref = _pair_image(reference, layout, device, stream, background)
+        _pair_sizes(ref, None)
+        self._open(ref, ref.ordinal if ref.ordinal is not None else (0 if device is None else device))
+
+    def _open(self, ref, ordinal):
+        from .capi import Context
+        lib = _pair_library()
+        self.w, self.h, self.device = ref.w, ref.h, ordinal
+        # (the target only scales gz_block_weights, which nothing here asks for)
+        self._ctx = lib.context(ref.rgb, 1.0, ordinal) if ref.rgb is not None else Context.from_device(lib, ref.pixels, ref.w, ref.h, 1.0, ordinal)
+
+    @classmethod
+    def _of(cls, ref, ordinal):
+        self = cls.__new__(cls)
+        self._open(ref, ordinal)
+        return self
+
+    def close(self):
+        ctx, self._ctx = getattr(self, "_ctx", None), None
+        if ctx is not None:
+            ctx.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def _destination(self, distmap, stream):
+        """distmap= -> (what compare returns as the map, capi.GzDeviceMap) -- (None, None) without one."""
+        from .capi import device_map
+        if distmap is None or distmap is False:
+            return None, None
+        if distmap is True:
+            distmap = _new_map_tensor(self.w, self.h, self.device)
+        ptr, name, strides, consumer, _ = _map_destination(distmap, self.w, self.h, self.device)
+        return distmap, device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+
+    def _compare(self, other, out, dmap):
+        if self._ctx is None:
+            raise ValueError("the Comparator is closed")
+        if other.rgb is not None:   # host bytes: their map comes back to the host too, and is emitted from the plane it left
+            d, _ = self._ctx.compare_rgb(other.rgb, want_distmap=dmap is not None)
+            if dmap is not None:
+                self._ctx.distmap_device(dmap)
+        else:
+            d = self._ctx.compare_device_pixels(other.pixels, dmap)
+        return d if dmap is None else (d, out)
+
+    def compare(self, distorted, distmap=None, layout=None, stream=None, background=None):
+        """The butteraugli distance of `distorted` (as process() accepts an image; the reference's size, on its GPU)
+        from the reference -> float, or with distmap= -> (float, map).  distmap=True: a fresh float32 [H, W] torch
+        tensor on the reference's GPU, allocated on the calling thread's current stream; work enqueued on that stream
+        afterwards sees the map.  distmap=tensor: that 2-D float32 / float16 / bfloat16 tensor (or
+        __cuda_array_interface__ object) is filled under its own strides -- a crop inside a larger tensor is written
+        without touching what surrounds it; flipped and expanded views are refused -- and returned.  stream= overrides
+        the producer's stream of `distorted` and the consumer's of the map (a hipStream_t handle; 0: none)."""
+        other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background)
+        _pair_sizes(_PairImage(self.w, self.h), other)
+        out, dmap = self._destination(distmap, stream if is_device_resident(distorted) else None)
+        return self._compare(other, out, dmap)
+
+
+def butteraugli(reference, distorted, distmap=None, layout=None, device=None, stream=None, background=None):
+    """The butteraugli distance (guetzli's, bit for bit) of two images of one size -> float, or with distmap= ->
+    (float, map): distmap=True gives a float32 [H, W] torch tensor on the reference's GPU, distmap=tensor fills a 2-D
+    float32 / float16 / bfloat16 tensor (see Comparator.compare).
+    The metric is ASYMMETRIC: `reference` is butteraugli's first argument (the original, whose masking counts),
+    `distorted` its second.  Both are accepted exactly as process() accepts an image -- host pixels, or GPU tensors /
+    __cuda_array_interface__ objects of every dtype, layout and stride it takes; layout=, background= and stream=
+    apply to both -- and the bytes compared are the bytes process() would encode.
+    ValueError, before anything is computed: sizes that differ, sizes under 8 x 8, images on different devices.
+    For many images against one reference, Comparator keeps the reference's half of the work."""
+    ref = _pair_image(reference, layout, device, stream if is_device_resident(reference) else None, background)
+    known = ref.ordinal if ref.ordinal is not None else device
+    other = _pair_image(distorted, layout, known if is_device_resident(distorted) else None,
+                        stream if is_device_resident(distorted) else None, background)
+    _pair_sizes(ref, other)
+    ordinal = known if known is not None else (other.ordinal if other.ordinal is not None else 0)
+    if distmap is not None and distmap is not False and distmap is not True:
+        _map_destination(distmap, ref.w, ref.h, ordinal)   # (refused before the reference is worked on)
+    with Comparator._of(ref, ordinal) as cmp:
+        out, dmap = cmp._destination(distmap, stream if (ref.pixels is not None or other.pixels is not None) else None)
+        return cmp._compare(other, out, dmap)

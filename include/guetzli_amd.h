@@ -56,7 +56,9 @@ int gz_abi_version(void);                 /* currently 6 (5 without the two expe
                                              existing declaration, struct or call sequence changed, so the number stays;
                                              so were gz_device_pixels and its three entries, and gz_device_output and
                                              its three (gz_decode_coeffs_device, gz_decode_coeffs,
-                                             gz_reconstruct_device), by the same rule */
+                                             gz_reconstruct_device), and gz_device_map and its entries
+                                             (gz_compare_device_pixels, gz_compare_rgb, gz_distmap_device), by the same
+                                             rule */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -320,6 +322,49 @@ int gz_decode_coeffs_device(int device, const int16_t* coeffs, int w, int h, int
 int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h, int chroma_factor, uint8_t* host_rgb_out);
 /* The candidate of a context, as gz_reconstruct's srgb, into out (the context's w and h). */
 int gz_reconstruct_device(gz_ctx* ctx, const gz_device_output* out);
+
+/* Image pairs: the butteraugli distance of two images, and its map on the device --------
+ * A context compares its original with JPEG candidates of it (gz_compare, below).  These entries compare it with ANY
+ * image of its size: the context's original is the reference (butteraugli's rgb0), `other` the distorted image (rgb1).
+ * The metric is not symmetric.  The chain is gz_compare's from its second kernel on -- OpsinDynamicsImage,
+ * SeparateFrequencies, DiffmapPsychoImage against the original's psycho image, which gz_create computed once -- so
+ * distance and map are, bit for bit, ButteraugliComparator's of the two images' 8-bit samples.
+ *
+ * gz_device_map: where a distance map goes, a strided w x h image in DEVICE memory: element (y, x) is
+ * data[y*stride_y + x*stride_x], strides in ELEMENTS, of float32, float16 or bfloat16.  One kernel (k_emit_map)
+ * converts the context's float plane and writes exactly the w*h elements: what lies between them stays as it is.
+ * GZ_DT_F32 is the map bit for bit; GZ_DT_F16 / GZ_DT_BF16 round to nearest, ties to even, over the whole float32
+ * domain (subnormal results, overflow to infinity, NaN stays NaN).
+ * GZ_E_ARG (before any device call): NULL data, a wrong struct_size, a dtype other than those three, a negative stride,
+ * an extent whose last offset does not fit 62 bits, strides under which two elements share an address
+ * (gz_device_output's rule: a stride of 0 is an error; the stride of a dimension of one element is not looked at).
+ * The memory must be device memory of the context's device (or managed / mapped page-locked memory), its extent
+ * inside its allocation: an ordinary host pointer is GZ_E_ARG, not a fault.
+ * consumer_stream: as gz_device_output's, in both directions.  With one, a call does not wait for the map on the
+ * host: work enqueued on that stream after the call sees it. */
+typedef struct gz_device_map {
+  int struct_size;            /* sizeof(gz_device_map) */
+  int dtype;                  /* GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 */
+  void* data;                 /* device address of element (0,0) */
+  int64_t stride_y, stride_x; /* elements, >= 0, no two elements at one address */
+  void* consumer_stream;      /* hipStream_t that used the memory before and reads it after; NULL = none */
+} gz_device_map;
+/* gz_compare_device_pixels: `other` is a device-resident image of the context's w x h, described and checked as
+ * gz_set_rgb_device_pixels' (every dtype, alpha over a background, the producer's stream is waited for on the device);
+ * its bytes are those the ingest kernel makes of it -- what an encode of `other` would read.  *distance receives the
+ * image maximum, as gz_compare returns it; map (may be NULL) receives the distance map.  The call synchronises for the
+ * distance in every case; with map->consumer_stream it does not wait for the map on the host.
+ * Afterwards gz_block_weights (use_distmap) speaks of THIS comparison.  The candidate, the original, its coefficients
+ * and the frame (4:4:4 or 4:2:0) stay as they were: the next gz_compare of the candidate returns what it would have
+ * returned.  GZ_E_STATE between gz_compare_begin and gz_compare_end, and while an order or a descent of phase B is in
+ * flight.  A failed call leaves the context valid; no later call trusts what it may have half written.
+ * gz_compare_rgb: the same for packed host bytes w*h*3; host_distmap (may be NULL) receives the map, w*h floats.
+ * gz_distmap_device: the map of the LAST comparison that stored one -- gz_compare with distmap != NULL, the two entries
+ * above called with a map, any comparison under gz_config.store_distmap -- written into map; a coefficient
+ * candidate's map stays on the device this way.  GZ_E_STATE if the last comparison stored none. */
+int gz_compare_device_pixels(gz_ctx* ctx, const gz_device_pixels* other, float* distance, const gz_device_map* map);
+int gz_compare_rgb(gz_ctx* ctx, const uint8_t* host_rgb, float* distance, float* host_distmap);
+int gz_distmap_device(gz_ctx* ctx, const gz_device_map* map);
 
 /* Double-precision DCT -----------------------------------------
  * gz_dct_double_blocks: ComputeBlockDCTDouble (inverse == 0) / ComputeBlockIDCTDouble
@@ -622,6 +667,10 @@ int gz_probe_diffmap(gz_ctx* ctx, const float* rgb0_3, const float* rgb1_3,
                      float* diffmap, float* score);             /* :784-908 both sides */
 int gz_probe_mask(gz_ctx* ctx, const float* xyb0_3, const float* xyb1_3, float* mask3,
                   float* mask_dc3);                             /* Mask, :1741-1817 */
+/* k_emit_map alone, without a context: host_plane (w*h floats of the caller's choosing, 0 < w, h < 65536; any bit
+ * pattern) is uploaded to a plane from the device pool and written into map as gz_distmap_device writes a distance
+ * map.  The call waits for its own work. */
+int gz_probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map);
 /* Block kernels on bare 64-element blocks (n blocks each). */
 int gz_probe_idct_blocks(int device, const int16_t* blocks, int n, uint8_t* out);
 int gz_probe_fdct_blocks(int device, int16_t* blocks, int n);
