@@ -64,7 +64,44 @@ typedef std::vector<float> Plane;
   X(search420_subblock_outside_image)                                                      \
   X(search420_subblock_outside_right) X(search420_subblock_outside_below)                  \
   X(search420_max_from_later_subblock)                                                     \
-  X(search_evaluations)
+  X(search_evaluations)                                                                    \
+  GZ_FRAME_ARMS(X)
+// The frame_* arms are the frame path's (tests/test_frame_domain.py): quantize_coeff, the integer IDCT and the
+// colour transform as orc_reconstruct / orc_reconstruct420 run them OUTSIDE the search (the search_* clamp arms
+// above count the same statements inside it), orc_encode_rgb's edge replication, the 4:2:0 upsampler's neighbour
+// samples, orc_set_downsampled's source clamps and rounding ties, and PreProcessChannel's thresholds, maps and
+// borders, once per pass (pp2 = channel 2, the first pass; pp1 = channel 1).  The pp1 arms repeat the pp2 arms in
+// the same order: pp_arm() relies on it.
+#define GZ_FRAME_PP_ARMS(X, p)                                                             \
+  X(frame_##p##_dark_true) X(frame_##p##_dark_false)                                       \
+  X(frame_##p##_red_true) X(frame_##p##_red_false)                                         \
+  X(frame_##p##_erode_clears) X(frame_##p##_erode_keeps)                                   \
+  X(frame_##p##_dilate_sets) X(frame_##p##_dilate_keeps)                                   \
+  X(frame_##p##_morph_border_pixel)                                                        \
+  X(frame_##p##_edge_below_threshold) X(frame_##p##_edge_not_below_threshold)              \
+  X(frame_##p##_v_below_scaled_u_true) X(frame_##p##_v_below_scaled_u_false)               \
+  X(frame_##p##_out_sharpened) X(frame_##p##_out_blurred) X(frame_##p##_out_unchanged)     \
+  X(frame_##p##_conv_h_border) X(frame_##p##_conv_h_interior)                              \
+  X(frame_##p##_conv_v_border) X(frame_##p##_conv_v_interior)
+#define GZ_FRAME_ARMS(X)                                                                   \
+  X(frame_quant_round_up) X(frame_quant_round_down) X(frame_quant_toward_zero)             \
+  X(frame_quant_tie_positive) X(frame_quant_tie_negative)                                  \
+  X(frame_quant_q_above_raw) X(frame_quant_wrapped_int16)                                  \
+  X(frame_idct_column_wraps_int16) X(frame_idct_column_fits_int16)                         \
+  X(frame_idct_pixel_clamped_low) X(frame_idct_pixel_clamped_high)                         \
+  X(frame_idct_pixel_inside)                                                               \
+  X(frame_rgb444_clamped_low) X(frame_rgb444_clamped_high) X(frame_rgb444_inside)          \
+  X(frame_rgb420_clamped_low) X(frame_rgb420_clamped_high) X(frame_rgb420_inside)          \
+  X(frame_encode_x_replicated) X(frame_encode_y_replicated) X(frame_encode_pixel_inside)   \
+  X(frame_up420_neighbour_clamped_left) X(frame_up420_neighbour_clamped_right)             \
+  X(frame_up420_neighbour_clamped_top) X(frame_up420_neighbour_clamped_bottom)             \
+  X(frame_up420_neighbour_not_clamped)                                                     \
+  X(frame_setds_source_x_clamped) X(frame_setds_source_y_clamped)                          \
+  X(frame_setds_source_inside)                                                             \
+  X(frame_setds_round_tie_positive) X(frame_setds_round_tie_negative)                      \
+  X(frame_setds_round_no_tie)                                                              \
+  GZ_FRAME_PP_ARMS(X, pp2)                                                                 \
+  GZ_FRAME_PP_ARMS(X, pp1)
 enum CensusArm {
 #define X(n) kArm_##n,
   GZ_CENSUS_ARMS(X)
@@ -88,6 +125,26 @@ struct InSearch {
 // (`first`: the census entry of the low arm -- high, inside follow)
 inline void tick_clamp(int first, int v) {
   if (g_in_search) tick(first + (v < 0 ? 0 : v > 255 ? 1 : 2));
+}
+// The frame_* arms count what runs outside phase A's loops.  g_frame_layout: which reconstruction the colour
+// transform serves (1 = orc_reconstruct, 2 = orc_reconstruct420, 0 = neither: orc_ycbcr_to_rgb on its own).
+inline void tick_frame(int arm) { if (!g_in_search) tick(arm); }
+inline void tick_frame_clamp(int first, int v) {
+  if (!g_in_search) tick(first + (v < 0 ? 0 : v > 255 ? 1 : 2));
+}
+int g_frame_layout = 0;
+struct FrameLayout {
+  int saved;
+  explicit FrameLayout(int f) : saved(g_frame_layout) { g_frame_layout = f; }
+  ~FrameLayout() { g_frame_layout = saved; }
+};
+inline void tick_frame_rgb(int v) {
+  if (g_frame_layout == 1) tick_frame_clamp(kArm_frame_rgb444_clamped_low, v);
+  if (g_frame_layout == 2) tick_frame_clamp(kArm_frame_rgb420_clamped_low, v);
+}
+// (`arm`: a pp2 arm; pass 0 = channel 2, pass 1 = channel 1)
+inline int pp_arm(int arm, int pass) {
+  return arm + pass * (kArm_frame_pp1_dark_true - kArm_frame_pp2_dark_true);
 }
 
 // ===================================================================== block path ==
@@ -191,6 +248,9 @@ inline void ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {
   tick_clamp(kArm_search_rgb_clamped_low, r);
   tick_clamp(kArm_search_rgb_clamped_low, g);
   tick_clamp(kArm_search_rgb_clamped_low, b);
+  tick_frame_rgb(r);
+  tick_frame_rgb(g);
+  tick_frame_rgb(b);
   rgb[0] = clamp255(r);
   rgb[1] = clamp255(g);
   rgb[2] = clamp255(b);
@@ -214,6 +274,16 @@ inline int16_t quantize_coeff(int16_t raw, int quant) {
   const int r = raw % quant;
   const int16_t delta =
       (int16_t)(2 * r > quant ? quant - r : (-2) * r > quant ? -quant - r : -r);
+  {   // census (64-bit: the exact value, whatever quant is)
+    const long long q = quant, rr = r;
+    const long long exact = raw + (2 * rr > q ? q - rr : -2 * rr > q ? -q - rr : -rr);
+    tick_frame(2 * rr > q ? kArm_frame_quant_round_up
+                          : -2 * rr > q ? kArm_frame_quant_round_down : kArm_frame_quant_toward_zero);
+    if (rr > 0 && 2 * rr == q) tick_frame(kArm_frame_quant_tie_positive);
+    if (rr < 0 && -2 * rr == q) tick_frame(kArm_frame_quant_tie_negative);
+    if (q > (raw < 0 ? -(long long)raw : (long long)raw)) tick_frame(kArm_frame_quant_q_above_raw);
+    if ((long long)(int16_t)(raw + delta) != exact) tick_frame(kArm_frame_quant_wrapped_int16);
+  }
   return (int16_t)(raw + delta);
 }
 
@@ -806,6 +876,7 @@ void reconstruct(const int16_t* coeffs, int w, int h, const int* q, int16_t* coe
   const int bw = (w + 7) / 8, bh = (h + 7) / 8, nb = bw * bh;
   const size_t n = (size_t)w * h;
   const double* lut = srgb_table();
+  const FrameLayout census_scope(1);
   std::vector<uint8_t> ycc(3 * n);
   for (int c = 0; c < 3; ++c) {
     for (int by = 0; by < bh; ++by) {
@@ -1061,7 +1132,11 @@ void orc_idct_block(const int16_t* block, uint8_t* out) {
   for (int x = 0; x < 8; ++x) {
     int t[8];
     idct_1d(block + x, 8, t);
-    for (int y = 0; y < 8; ++y) cols[8 * y + x] = (int16_t)((t[y] + (1 << 10)) >> 11);
+    for (int y = 0; y < 8; ++y) {
+      const int v = (t[y] + (1 << 10)) >> 11;
+      tick_frame(v != (int16_t)v ? kArm_frame_idct_column_wraps_int16 : kArm_frame_idct_column_fits_int16);
+      cols[8 * y + x] = (int16_t)v;
+    }
   }
   for (int y = 0; y < 8; ++y) {
     int t[8];
@@ -1069,6 +1144,7 @@ void orc_idct_block(const int16_t* block, uint8_t* out) {
     for (int x = 0; x < 8; ++x) {
       const int v = (t[x] + (257 << 17)) >> 18;
       tick_clamp(kArm_search_idct_pixel_clamped_low, v);
+      tick_frame_clamp(kArm_frame_idct_pixel_clamped_low, v);
       out[8 * y + x] = clamp255(v);
     }
   }
@@ -1136,6 +1212,10 @@ int orc_set_downsampled(const float* pixels, int w, int h, int fx, int fy, int16
             for (int i = 0; i < fx; ++i) {
               const int x = std::min(8 * bx * fx + ix * fx + i, w - 1);
               const int y = std::min(8 * by * fy + iy * fy + j, h - 1);
+              const bool xc = 8 * bx * fx + ix * fx + i > w - 1, yc = 8 * by * fy + iy * fy + j > h - 1;
+              if (xc) tick_frame(kArm_frame_setds_source_x_clamped);
+              if (yc) tick_frame(kArm_frame_setds_source_y_clamped);
+              if (!xc && !yc) tick_frame(kArm_frame_setds_source_inside);
               avg += pixels[(size_t)y * w + x];
             }
           avg /= fx * fy;
@@ -1143,8 +1223,12 @@ int orc_set_downsampled(const float* pixels, int w, int h, int fx, int fy, int16
         }
       orc_dct_double(d, 0);
       d[0] -= 1024.0;
-      for (int k = 0; k < 64; ++k)
+      for (int k = 0; k < 64; ++k) {
+        const double frac = d[k] - std::trunc(d[k]);   // (exact: both are doubles of the same binade or below)
+        tick_frame(frac == 0.5 ? kArm_frame_setds_round_tie_positive
+                               : frac == -0.5 ? kArm_frame_setds_round_tie_negative : kArm_frame_setds_round_no_tie);
         out[((size_t)by * bw + bx) * 64 + k] = static_cast<int16_t>(std::round(d[k]));
+      }
     }
   return bw * bh;
 }
@@ -1181,6 +1265,9 @@ int orc_encode_rgb(const uint8_t* rgb, int w, int h, int16_t* coeffs) {
         for (int ix = 0; ix < 8; ++ix) {
           const int y = std::min(h - 1, 8 * by + iy);
           const int x = std::min(w - 1, 8 * bx + ix);
+          if (8 * bx + ix > w - 1) tick_frame(kArm_frame_encode_x_replicated);
+          if (8 * by + iy > h - 1) tick_frame(kArm_frame_encode_y_replicated);
+          if (8 * bx + ix <= w - 1 && 8 * by + iy <= h - 1) tick_frame(kArm_frame_encode_pixel_inside);
           const uint8_t* p = rgb + 3 * ((size_t)y * w + x);
           const int r = p[0], g = p[1], b = p[2];
           const int HALF = 1 << 15;
@@ -1531,6 +1618,14 @@ struct Comp {   // OutputImageComponent, output_image.h:27-97
         const int c0 = (x & ~1) / 2 - bx * 8 + 1;
         const int dx = (x & 1) * 2 - 1;
         const int ix = c0 + r0;
+        {   // census: where the neighbour samples (column c0 + dx, row r0 / 10 + dy / 10 of `sub`) lie
+          const int nx = bx * 16 + (c0 + dx - 1) * 2, ny = by * 16 + (r0 / 10 + dy / 10 - 1) * 2;
+          if (nx < 0) tick_frame(kArm_frame_up420_neighbour_clamped_left);
+          if (nx >= w) tick_frame(kArm_frame_up420_neighbour_clamped_right);
+          if (ny < 0) tick_frame(kArm_frame_up420_neighbour_clamped_top);
+          if (ny >= h) tick_frame(kArm_frame_up420_neighbour_clamped_bottom);
+          if (nx >= 0 && nx < w && ny >= 0 && ny < h) tick_frame(kArm_frame_up420_neighbour_not_clamped);
+        }
         pixels[(size_t)y * w + x] =
             (uint16_t)((sub[ix] * 9 + sub[ix + dy] * 3 + sub[ix + dx] * 3 + sub[ix + dx + dy]) >> 4);
       }
@@ -1615,10 +1710,11 @@ double compare_block_image(const BlockSearch* bs, const Image3& img, int bxx, in
 // ---- preprocess_downsample.cc:28-279 ----
 typedef std::vector<float> Fl;
 
-Fl convolve2x(const Fl& image, int w, int h, const double* kernel, double mul) {   // :53-83, size 5
+Fl convolve2x(const Fl& image, int w, int h, const double* kernel, double mul, int pass) {   // :53-83, size 5
   Fl temp = image;
   for (size_t i = 0; i < image.size(); ++i) {
     const int x = (int)(i % w), y = (int)(i / w);
+    tick_frame(pp_arm(x < 2 || x + 2 >= w ? kArm_frame_pp2_conv_h_border : kArm_frame_pp2_conv_h_interior, pass));
     if (x < 2 || x + 2 >= w) continue;
     float v = 0;
     for (int j = 0; j < 5; ++j) v += static_cast<float>(kernel[j]) * image[(size_t)y * w + x + j - 2];
@@ -1627,6 +1723,7 @@ Fl convolve2x(const Fl& image, int w, int h, const double* kernel, double mul) {
   Fl result = temp;
   for (size_t i = 0; i < temp.size(); ++i) {
     const int x = (int)(i % w), y = (int)(i / w);
+    tick_frame(pp_arm(y < 2 || y + 2 >= h ? kArm_frame_pp2_conv_v_border : kArm_frame_pp2_conv_v_interior, pass));
     if (y < 2 || y + 2 >= h) continue;
     float v = 0;
     for (int j = 0; j < 5; ++j) v += static_cast<float>(kernel[j]) * temp[(size_t)(y + j - 2) * w + x];
@@ -1643,13 +1740,18 @@ void normal_kernel(double sigma, double kernel[5], double* mul) {   // :85-100
   }
   *mul = 1.0 / sum;
 }
-void morph(int w, int h, std::vector<char>* image, bool erode) {   // :110-134
+void morph(int w, int h, std::vector<char>* image, bool erode, int pass) {   // :110-134
   const std::vector<char> t = *image;
+  for (int y = 0; y < h; ++y)   // census: the pixels the loops below leave alone
+    for (int x = 0; x < w; ++x)
+      if (!(y >= 1 && y + 1 < h && x >= 1 && x + 1 < w)) tick_frame(pp_arm(kArm_frame_pp2_morph_border_pixel, pass));
   for (int y = 1; y + 1 < h; ++y)
     for (int x = 1; x + 1 < w; ++x) {
       const size_t i = (size_t)y * w + x;
       const bool all = t[i] && t[i - 1] && t[i + 1] && t[i - w] && t[i + w];
       const bool any = t[i] || t[i - 1] || t[i + 1] || t[i - w] || t[i + w];
+      if (erode && t[i]) tick_frame(pp_arm(all ? kArm_frame_pp2_erode_keeps : kArm_frame_pp2_erode_clears, pass));
+      if (!erode && !t[i]) tick_frame(pp_arm(any ? kArm_frame_pp2_dilate_sets : kArm_frame_pp2_dilate_keeps, pass));
       if (erode) { if (!all) (*image)[i] = 0; }
       else if (any) (*image)[i] = 1;
     }
@@ -1657,6 +1759,7 @@ void morph(int w, int h, std::vector<char>* image, bool erode) {   // :110-134
 // ref: PreProcessChannel, :157-279, with blur and sharpen both on
 void preprocess_channel(int w, int h, int channel, float sigma, float amount, Fl yuv[3]) {
   const size_t n = (size_t)w * h;
+  const int pass = channel == 2 ? 0 : 1;   // (census: the pp2 arms, then the pp1 arms)
   for (size_t i = 0; i < n; ++i) {
     yuv[0][i] /= 255.0;
     yuv[1][i] = yuv[1][i] / 255.0f - 0.5f;
@@ -1672,9 +1775,11 @@ void preprocess_channel(int w, int h, int channel, float sigma, float amount, Fl
     if (channel == 1 && r < 0.85 && g < 0.85 && b < 0.9) dark[i] = 1;
     if (channel == 2 && 2.116 * v > -0.34414 * u + 0.2 && 1.402 * v > 1.772 * u + 0.2) red[i] = 1;
     if (channel == 1 && v < 1.263 * u - 0.1 && u > -0.33741 * v) red[i] = 1;
+    tick_frame(pp_arm(dark[i] ? kArm_frame_pp2_dark_true : kArm_frame_pp2_dark_false, pass));
+    tick_frame(pp_arm(red[i] ? kArm_frame_pp2_red_true : kArm_frame_pp2_red_false, pass));
   }
-  for (int k = 0; k < 3; ++k) morph(w, h, &dark, true);
-  for (int k = 0; k < 3; ++k) morph(w, h, &red, false);
+  for (int k = 0; k < 3; ++k) morph(w, h, &dark, true, pass);
+  for (int k = 0; k < 3; ++k) morph(w, h, &red, false, pass);
   for (size_t i = 0; i < n; ++i) sharp[i] = red[i] && dark[i];
   const double threshold = (channel == 2 ? 0.02 : 1.0) * 127.5;
   static const double kEdge[9] = {0, -1, 0, -1, 4, -1, 0, -1, 0};
@@ -1688,17 +1793,23 @@ void preprocess_channel(int w, int h, int channel, float sigma, float amount, Fl
     }
   for (size_t i = 0; i < n; ++i) {
     if (sharp[i] || !dark[i]) continue;
+    tick_frame(pp_arm(fabs(edge[i]) < threshold ? kArm_frame_pp2_edge_below_threshold
+                                                : kArm_frame_pp2_edge_not_below_threshold, pass));
+    tick_frame(pp_arm(yuv[2][i] < -0.162 * yuv[1][i] ? kArm_frame_pp2_v_below_scaled_u_true
+                                                     : kArm_frame_pp2_v_below_scaled_u_false, pass));
     if (fabs(edge[i]) < threshold && yuv[2][i] < -0.162 * yuv[1][i]) blurm[i] = 1;
   }
-  morph(w, h, &blurm, true);
-  morph(w, h, &blurm, true);
+  morph(w, h, &blurm, true, pass);
+  morph(w, h, &blurm, true, pass);
   double ks[5], kb[5], ms, mb;
   normal_kernel(sigma, ks, &ms);   // Sharpen: float sigma promoted
   normal_kernel(1.3, kb, &mb);     // Blur: kSigma
-  Fl sharpened = convolve2x(yuv[channel], w, h, ks, ms);
+  Fl sharpened = convolve2x(yuv[channel], w, h, ks, ms, pass);
   for (size_t i = 0; i < n; ++i) sharpened[i] = yuv[channel][i] + (yuv[channel][i] - sharpened[i]) * amount;
-  const Fl blurred = convolve2x(yuv[channel], w, h, kb, mb);
+  const Fl blurred = convolve2x(yuv[channel], w, h, kb, mb, pass);
   for (size_t i = 0; i < n; ++i) {
+    tick_frame(pp_arm(sharp[i] ? kArm_frame_pp2_out_sharpened
+                               : blurm[i] ? kArm_frame_pp2_out_blurred : kArm_frame_pp2_out_unchanged, pass));
     if (sharp[i]) yuv[channel][i] = sharpened[i];
     else if (blurm[i]) yuv[channel][i] = blurred[i];
   }
@@ -1739,6 +1850,7 @@ int orc_downsample(const int16_t* coeffs, int w, int h, int use_silver_screen, i
 
 void orc_reconstruct420(const int16_t* coeffs, int w, int h, const int* q, int shuffle,
                         int16_t* coeffs_out, uint8_t* srgb, float* linear) {
+  const FrameLayout census_scope(2);
   Image3 img;
   img.init(w, h, 2);
   img.fill(coeffs);

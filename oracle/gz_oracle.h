@@ -53,6 +53,10 @@ double orc_diffmap(const float* rgb0, const float* rgb1, int w, int h, float* di
  * candidate wins and ties kept, errors of exactly 0, the monotone minimum, the cut at the error limit, the clamps
  * of the IDCT and the colour transform inside the search, equal ranking scores, 4:2:0 sub-blocks outside the image;
  * search_evaluations is a plain counter of the CompareBlock calls the search loops make.
+ * The frame_* arms are the frame path's, counted outside the search: orc_quantize_block's rounding, ties and int16
+ * wrap, the integer IDCT's column wrap and pixel clamps, the colour transform's clamps (orc_reconstruct and
+ * orc_reconstruct420 apart), orc_encode_rgb's edge replication, the 4:2:0 upsampler's clamped neighbour samples,
+ * orc_set_downsampled's source clamps and rounding ties, PreProcessChannel's thresholds, maps and borders per pass.
  * orc_branch_census fills out[0..n) and returns the number of arms. ---- */
 int  orc_branch_census(unsigned long long* out, int n);
 const char* orc_branch_census_name(int i);

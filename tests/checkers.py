@@ -233,12 +233,26 @@ class Checker:
     def census(self):
         """{arm: samples that took it since census_reset()} for every value branch of the
         butteraugli stages (oracle/gz_oracle.h)."""
-        return {k: v for k, v in self._census_all().items() if not k.startswith("search")}
+        return {k: v for k, v in self._census_all().items() if not k.startswith(("search", "frame_"))}
 
     def search_census(self):
         """The same for phase A's arms (search_*, search420_*; search_evaluations is a plain counter
         of the CompareBlock calls the search loops made): orc_block_zeroing_orders[_masked]."""
         return {k: v for k, v in self._census_all().items() if k.startswith("search")}
+
+    def frame_census(self):
+        """The same for the frame path's arms (frame_*): quantisation, the integer IDCT and the colour transform outside
+        the search, orc_encode_rgb, the 4:2:0 upsampler, orc_set_downsampled and PreProcessChannel."""
+        return {k: v for k, v in self._census_all().items() if k.startswith("frame_")}
+
+    def set_downsampled(self, pixels, fx, fy):
+        """orc_set_downsampled of an h x w float plane (oracle only)."""
+        px = np.ascontiguousarray(pixels, np.float32)
+        h, w = px.shape
+        nb = ((w + 8 * fx - 1) // (8 * fx)) * ((h + 8 * fy - 1) // (8 * fy))
+        out = np.zeros((nb, 64), np.int16)
+        assert self._set_downsampled(_ptr(px), w, h, fx, fy, _ptr(out)) == nb
+        return out
 
     def _census_all(self):
         n = self._branch_census(None, 0)

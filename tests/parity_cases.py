@@ -1451,3 +1451,277 @@ def case_order_descent(contexts, per_block, big, short=False, log_every=1, every
             log2 = b.order_descend(last, 16, 12)
             assert_bits_equal(log, log2, f"cut log, per_block {per_block} blocks_to_change {btc}")
             assert_bits_equal(a.order_fetch(0, n), b.order_fetch(0, n), f"order after the descent, {per_block} {btc}")
+
+
+# ------------------------------------------------ the frame path on tests/frame_domain.py --
+# Pixels -> coefficients -> pixels on synthetic families (tests/test_frame_domain.py counts the arms they take with the
+# oracle's frame_* census; tests/test_frame_gpu.py runs these cases on the GPU).  Integers and float bit patterns only.
+def frame_context(contexts, w, h):
+    """The frame cases' context of this size, with the patches' self-check on (gz_config.patch_reconstruct = 2: a Compare
+    that relies on patched planes compares them, word for word, with a full reconstruction first)."""
+    ctx = contexts.get(w, h, 1.0, "frame")
+    ctx.set_config(patch_reconstruct=2)
+    return ctx
+
+
+def case_frame_encode(L, contexts, sizes):
+    """k_encode_rgb with and without a context: the lattice of colours, and the pixel families at sizes that replicate
+    one and seven columns / rows."""
+    import frame_domain as fd
+    img = fd.lattice_image()
+    assert_bits_equal(L.encode_rgb_only(img), oracle.encode_rgb(img), "encode_rgb_only lattice")
+    for w, h in sizes:
+        for name, rgb in fd.pixel_cases(w, h):
+            exp = oracle.encode_rgb(rgb)
+            assert_bits_equal(L.encode_rgb_only(rgb), exp, f"encode_rgb_only {name} {w}x{h}")
+            if w >= 8 and h >= 8:
+                ctx = frame_context(contexts, w, h)
+                ctx.set_rgb(rgb)
+                assert_bits_equal(ctx.encode_rgb(), exp, f"encode_rgb {name} {w}x{h}")
+
+
+def _frame_block_list(nb):
+    """Block positions for a patching call: repeats (adjacent and not), the first and the last block; at most nb / 2
+    entries, beyond which the library leaves the planes to the next full reconstruction."""
+    return np.array([0, 0, nb - 1, nb // 2, 0, nb - 1, nb - 1, nb // 3][:nb // 2], np.int32)
+
+
+def _frame_patched_planes(L, ctx, co, w, h, what):
+    """k_reconstruct_listed on the family's blocks: bulk steps (gz_apply_candidate_steps, block positions) and
+    single-coefficient edits (gz_apply_coeff_edits, coefficient positions) with lists that hold repeats and the first
+    and last block; the Compare that follows checks the patched planes against a full reconstruction itself (mode 2)
+    and must give what a Compare of the same coefficients put in place as a whole gives."""
+    import order_domain as od
+    nb = ctx.nb
+    g = od.Grid(w, h)
+    ones = np.ones((3, 64), np.int32)
+    rng = np.random.default_rng(RNG_SEED + 13 * w + h)
+    ctx.set_orig_coeffs(co)
+    ctx.quantize(ones, download=False)             # the candidate = the family's coefficients
+    # one candidate per block: coefficient 2..63 but 8 (positions 1 and 8 may be kept as "precious") of a component
+    k = rng.integers(2, 64, nb)
+    k[k == 8] = 9
+    idx = (64 * rng.integers(0, 3, nb) + k).astype(np.uint8)
+    off = np.arange(nb + 1, dtype=np.int32)
+    ctx.probe_set_search(off, idx, np.zeros(nb, np.float32))
+    ctx.jpeg_histograms(ones)
+    ctx.compare()                                   # a full reconstruction: the planes are the candidate's
+    next_cand = np.zeros(nb, np.int32)
+    ctx.order_build(1, next_cand, np.zeros(nb, np.float32), np.zeros(nb, np.float32))   # (uploads next_cand)
+    blocks = _frame_block_list(nb)
+    before = L.compare_counters()
+    exp = np.asarray(co, np.int16).reshape(-1, 64).copy()
+    if blocks.size:
+        ctx.apply_candidate_steps(1, blocks, np.ones(blocks.size, np.int32))
+        ctx.steps_histogram_delta()
+        exp = od.apply_steps(g, exp, co, ones, off, idx, next_cand, 1, blocks, np.ones(blocks.size, np.int32))
+        eb = blocks[::-1].copy()                    # (the same positions, in another order, as coefficient positions)
+        pos = ((rng.integers(0, 3, eb.size) * nb + eb) * 64 + rng.integers(0, 64, eb.size)).astype(np.int32)
+        val = np.array([32767, -32768, 16384, -16384, 1, 0, -1, 8191], np.int16)[:eb.size]
+        ctx.apply_coeff_edits(pos, val)
+        for p, v in zip(pos, val):                  # (in order: a later edit of the same position wins)
+            exp.reshape(-1)[p] = v
+    import frame_domain as fd
+    assert fd.idct_sums_fit_int32(exp)
+    got = ctx.compare()
+    patched, checked, compares = (a - b for a, b in zip(L.compare_counters(), before))
+    # (no list at all on a frame of one block: the planes of the Compare before are still the candidate's)
+    assert (patched, checked, compares) == (1, 1, 1), (what, patched, checked, compares)
+    assert_bits_equal(ctx.get_coeffs().reshape(-1, 64), exp, f"coefficients after steps and edits: {what}")
+    ctx.set_coeffs(exp)
+    full = ctx.compare()
+    for a, b, name in zip(got, full, ("distance", "distance map", "block maxima")):
+        assert_bits_equal(np.asarray(a, np.float32), np.asarray(b, np.float32), f"patched {name}: {what}")
+    _, esrgb, elin = oracle.reconstruct(exp.reshape(3, nb, 64), w, h, None)
+    srgb, lin = ctx.reconstruct()
+    assert_bits_equal(srgb, esrgb, f"reconstruct srgb after steps and edits: {what}")
+    assert_bits_equal(lin, elin, f"reconstruct linear after steps and edits: {what}")
+
+
+def case_frame_coeffs444(L, contexts, w, h, family, tables=None, patched=True):
+    """gz_set_orig_coeffs -> gz_quantize -> gz_reconstruct (sRGB and linear), gz_decode_coeffs, gz_set_coeff_blocks and
+    the patched planes on a coefficient family, under every quantiser table."""
+    import frame_domain as fd
+    co = fd.coeffs_of(family, w, h, "444")
+    assert fd.idct_sums_fit_int32(co), "the family's IDCT sums leave int32"
+    ctx = frame_context(contexts, w, h)
+    ctx.set_orig_coeffs(co)
+    ecq = None
+    for qn, q in fd.quant_tables(co, "444", w, h, only=tables):
+        what = f"{family} q={qn} 444 {w}x{h}"
+        cq = ctx.quantize(q)
+        ecq, esrgb, elin = oracle.reconstruct(co, w, h, q)
+        assert fd.idct_sums_fit_int32(ecq)
+        assert_bits_equal(cq, fd.quantize_by_definition(co, q, "444", w, h), f"quantize, block by block: {what}")
+        assert_bits_equal(cq, ecq, f"quantize: {what}")
+        srgb, lin = ctx.reconstruct()
+        assert_bits_equal(srgb, esrgb, f"reconstruct srgb: {what}")
+        assert_bits_equal(lin, elin, f"reconstruct linear: {what}")
+        assert_bits_equal(L.decode_coeffs(ecq, w, h, 1), esrgb, f"decode_coeffs: {what}")
+    # block updates: the first, the middle and the last block replaced by the wrap family's
+    idx = np.unique(np.array([0, ctx.nb - 1, ctx.nb // 2], np.int32))
+    other = fd.coeffs_of("wrap", w, h, "444")
+    ctx.set_coeff_blocks(idx, np.ascontiguousarray(other[:, idx].transpose(1, 0, 2)))
+    exp = ecq.copy()
+    exp[:, idx] = other[:, idx]
+    assert_bits_equal(ctx.get_coeffs(), exp, f"set_coeff_blocks: {family} {w}x{h}")
+    _, esrgb, elin = oracle.reconstruct(exp, w, h, None)
+    srgb, lin = ctx.reconstruct()
+    assert_bits_equal(srgb, esrgb, f"reconstruct srgb after set_coeff_blocks: {family} {w}x{h}")
+    assert_bits_equal(lin, elin, f"reconstruct linear after set_coeff_blocks: {family} {w}x{h}")
+    if patched:
+        _frame_patched_planes(L, ctx, co, w, h, f"{family} {w}x{h}")
+
+
+def case_frame_coeffs420(L, contexts, w, h, family, tables=None):
+    """gz_set_orig_coeffs_420 -> gz_quantize (component boundaries nb, nb + nbc) -> gz_reconstruct (k_chroma_samples,
+    k_reconstruct420), and gz_decode_coeffs with factor 2 equal to reconstruct's bytes."""
+    import frame_domain as fd
+    co = fd.coeffs_of(family, w, h, "420")
+    assert fd.idct_sums_fit_int32(co), "the family's IDCT sums leave int32"
+    ctx = frame_context(contexts, w, h)
+    ctx.set_orig_coeffs_420(co)
+    assert ctx.frame_layout() == (2, ctx.nb, ctx.nbc)
+    for qn, q in fd.quant_tables(co, "420", w, h, only=tables):
+        what = f"{family} q={qn} 420 {w}x{h}"
+        cq = ctx.quantize(q)
+        ecq, esrgb, elin = oracle.reconstruct420(co, w, h, q, shuffle=7)
+        assert fd.idct_sums_fit_int32(ecq)
+        assert_bits_equal(cq, fd.quantize_by_definition(co, q, "420", w, h), f"quantize, block by block: {what}")
+        assert_bits_equal(cq, ecq, f"quantize: {what}")
+        srgb, lin = ctx.reconstruct()
+        assert_bits_equal(srgb, esrgb, f"reconstruct srgb: {what}")
+        assert_bits_equal(lin, elin, f"reconstruct linear: {what}")
+        assert_bits_equal(L.decode_coeffs(ecq, w, h, 2), srgb, f"decode_coeffs == reconstruct: {what}")
+
+
+def frame_downsample_inputs(w, h):
+    """(name, 4:4:4 coefficients) for gz_downsample: the YUV fields, the photograph, and the two coefficient families whose
+    pixels stay near [0, 255] (ToFloatPixels does not clamp: the others' samples are beyond what a rounded coefficient
+    of SetDownsampledCoefficients can hold)."""
+    import frame_domain as fd
+    yield from fd.yuv_cases(w, h)
+    for name in ("photo", "dc_ramp", "chroma_extreme"):
+        yield name, fd.coeffs_of(name, w, h, "444")
+
+
+def case_frame_downsample(L, contexts, w, h):
+    """gz_component_to_float_pixels and gz_downsample (k_to_float_pixels, the nine k_pp_* kernels,
+    k_set_downsampled_coeffs by 2 x 2) on foreign 4:4:4 coefficients."""
+    ctx = frame_context(contexts, w, h)
+    for name, co in frame_downsample_inputs(w, h):
+        what = f"{name} {w}x{h}"
+        assert np.asarray(co)[1:].any(), "a grey frame stays 4:4:4"
+        for c in range(3):
+            assert_bits_equal(L.component_to_float_pixels(co[c], w, h), oracle.to_float_pixels(co[c], w, h),
+                              f"ToFloatPixels c={c}: {what}")
+        exp = oracle.downsample(co, w, h)
+        # (the cast of a rounded double outside int16 is undefined in the reference)
+        assert np.abs(exp.astype(np.int32)).max() < 32767, what
+        ctx.set_orig_coeffs(co)
+        got = ctx.downsample()
+        assert ctx.frame_layout() == (2, ctx.nb, ctx.nbc)
+        assert_bits_equal(got, exp, f"downsample: {what}")
+
+
+def case_frame_planes(L):
+    """gz_component_set_downsampled for every (fx, fy) in 1..4 squared: source clamps at sizes that are no multiple of
+    8 fx / 8 fy (w < fx and a single row among them), samples outside [0, 255], and the rounding ties."""
+    import frame_domain as fd
+    for w, h in fd.PLANE_SIZES:
+        for name, p in fd.plane_cases(w, h):
+            lo, hi = fd.PLANE_RANGE
+            assert lo <= p.min() and p.max() <= hi
+            for fx, fy in fd.FACTORS:
+                assert_bits_equal(L.component_set_downsampled(p, fx, fy), oracle.set_downsampled(p, fx, fy),
+                                  f"SetDownsampledCoefficients {name} {w}x{h} by {fx}x{fy}")
+    for name, p, fx, fy in fd.tie_planes():
+        exp = oracle.set_downsampled(p, fx, fy)
+        t = float(name.split("/")[1])
+        assert exp[0, 0] == (t + 0.5 if t > 0 else t - 0.5), (name, exp[0, 0])   # half away from zero
+        assert_bits_equal(L.component_set_downsampled(p, fx, fy), exp, f"SetDownsampledCoefficients {name}")
+    for name, p in fd.constant_planes():
+        for fx, fy in ((1, 1), (2, 2)):
+            assert_bits_equal(L.component_set_downsampled(p, fx, fy), oracle.set_downsampled(p, fx, fy),
+                              f"SetDownsampledCoefficients {name} by {fx}x{fy}")
+
+
+def case_frame_free_sizes(L):
+    """The context-free entries below 8 pixels: gz_component_to_float_pixels and gz_decode_coeffs in both chroma
+    factors on the extreme families."""
+    import frame_domain as fd
+    for w, h in fd.FREE_SIZES:
+        for family in ("sparse", "matrix_rows", "wrap", "chroma_extreme"):
+            co = fd.coeffs_of(family, w, h, "444")
+            for c in range(3):
+                assert_bits_equal(L.component_to_float_pixels(co[c], w, h), oracle.to_float_pixels(co[c], w, h),
+                                  f"ToFloatPixels {family} c={c} {w}x{h}")
+            assert_bits_equal(L.decode_coeffs(co, w, h, 1), oracle.reconstruct(co, w, h, None)[1],
+                              f"decode_coeffs 444 {family} {w}x{h}")
+            co2 = fd.coeffs_of(family, w, h, "420")
+            assert_bits_equal(L.decode_coeffs(co2, w, h, 2), oracle.reconstruct420(co2, w, h, None)[1],
+                              f"decode_coeffs 420 {family} {w}x{h}")
+
+
+def case_frame_idct_copies(L, contexts, w, h):
+    """The copies of the integer IDCT against each other, no oracle: the same luma blocks (sparse, matrix rows, wrap)
+    under flat chroma (all chroma coefficients 0: Cb = Cr = 128, R = G = B = Y) through k_reconstruct (packed 16-bit
+    dot products), k_reconstruct420 (24-bit multiplies), k_idct_blocks, and k_reconstruct_listed (every block listed
+    once, at most half of them per call: the library's own word-for-word check against k_reconstruct, mode 2)."""
+    import frame_domain as fd
+    ctx = frame_context(contexts, w, h)
+    nb, nbc, bw = ctx.nb, ctx.nbc, ctx.bw
+    yb = fd.luma_extreme_blocks(nb, shift=w + h)
+    px = L.idct_blocks(yb)
+    pad = px.reshape(ctx.bh, bw, 8, 8).transpose(0, 2, 1, 3).reshape(ctx.bh * 8, bw * 8)[:h, :w]
+    ref_px, bound, wrapped = fd.idct_blocks_int64(yb)
+    assert bound < (1 << 31) and (nb < 3 or wrapped > 0)
+    assert_bits_equal(px, ref_px, "idct_blocks against the int64 evaluation")
+    grey = np.repeat(pad[:, :, None], 3, axis=2)
+    co444 = np.zeros((3, nb, 64), np.int16)
+    co444[0] = yb
+    ctx.set_orig_coeffs(co444)
+    ctx.quantize(None, download=False)
+    s444, l444 = ctx.reconstruct()
+    assert_bits_equal(s444, grey, f"k_reconstruct against k_idct_blocks {w}x{h}")
+    # every block through k_reconstruct_listed: an edit that writes the value already there, half the blocks per call
+    ctx.compare()
+    before = L.compare_counters()
+    halves = [np.arange(s, min(s + nb // 2, nb)) for s in range(0, nb, nb // 2)] if nb >= 2 else []
+    for half in halves:
+        pos = (half * 64 + 63).astype(np.int32)
+        ctx.apply_coeff_edits(pos, yb[half, 63])
+        ctx.compare()
+    patched, checked, _ = (a - b for a, b in zip(L.compare_counters(), before))
+    assert patched == checked == len(halves)
+    co420 = np.zeros((nb + 2 * nbc, 64), np.int16)
+    co420[:nb] = yb
+    ctx.set_orig_coeffs_420(co420)
+    ctx.quantize(None, download=False)
+    s420, l420 = ctx.reconstruct()
+    assert_bits_equal(s420, grey, f"k_reconstruct420 against k_idct_blocks {w}x{h}")
+    assert_bits_equal(l420, l444, f"k_reconstruct420 against k_reconstruct, linear {w}x{h}")
+
+
+def recon_strips_per_workgroup(w, h):
+    """stage_reconstruct's rule (chain.h): as many strips of 8 blocks per workgroup, up to 4, as leave 2000 workgroups."""
+    bw, bh = (w + 7) // 8, (h + 7) // 8
+    strips = -(-bw // 8)
+    per = 4
+    while per > 1 and bh * -(-strips // per) < 2000:
+        per >>= 1
+    return per
+
+
+def case_frame_strips(L, w, h):
+    """k_reconstruct's strip loop on the mixed synthetic coefficients, sRGB and linear."""
+    import frame_domain as fd
+    co = fd.mixed_coeffs(w, h)
+    assert fd.idct_sums_fit_int32(co)
+    _, esrgb, elin = oracle.reconstruct(co, w, h, None)
+    with L.context(np.zeros((h, w, 3), np.uint8), 1.0) as ctx:
+        ctx.set_orig_coeffs(co)
+        ctx.quantize(None, download=False)
+        srgb, lin = ctx.reconstruct()
+        assert_bits_equal(srgb, esrgb, f"reconstruct srgb {w}x{h}")
+        assert_bits_equal(lin, elin, f"reconstruct linear {w}x{h}")
