@@ -115,6 +115,13 @@ SIGNATURES = {
     "gz_compare_rgb": (_I, [_P, _P, _P, _P]),
     "gz_distmap_device": (_I, [_P, _P]),
     "gz_probe_emit_map": (_I, [_I, _P, _I, _I, _P]),
+    "gz_butteraugli_fuzzy_class": (C.c_double, [C.c_double]),
+    "gz_butteraugli_fuzzy_inverse": (C.c_double, [C.c_double]),
+    "gz_heatmap_device": (_I, [_P, C.c_double, C.c_double, _P]),
+    "gz_compare_device_pixels_heat": (_I, [_P, _P, _P, _P, _P, C.c_double, C.c_double]),
+    "gz_heatmap_from_map_device": (_I, [_I, _P, _I, _I, _I, C.c_double, C.c_double, _P]),
+    "gz_probe_emit_heat": (_I, [_I, _P, _I, _I, C.c_double, C.c_double, _P]),
+    "gz_probe_heat_thresholds": (_I, [_P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -385,6 +392,36 @@ class Library:
         h, w = p.shape
         self.check(self.lib.gz_probe_emit_map(device, _ptr(p), w, h, C.byref(dmap)))
 
+    def fuzzy_class(self, score):
+        """gz_butteraugli_fuzzy_class: ButteraugliFuzzyClass."""
+        return self.lib.gz_butteraugli_fuzzy_class(float(score))
+
+    def fuzzy_inverse(self, seek):
+        """gz_butteraugli_fuzzy_inverse: ButteraugliFuzzyInverse."""
+        return self.lib.gz_butteraugli_fuzzy_inverse(float(seek))
+
+    def default_heat_thresholds(self):
+        """(good, bad) as the reference's tool draws its heat maps: (fuzzy_inverse(1.5), fuzzy_inverse(0.5))."""
+        return self.fuzzy_inverse(1.5), self.fuzzy_inverse(0.5)
+
+    def heatmap_from_map_device(self, ptr, w, h, pitch, good, bad, output, device=0):
+        """gz_heatmap_from_map_device: the heat map of the float32 device plane at `ptr` (`pitch` floats per row) into
+        `output` (device_output(...))."""
+        self.check(self.lib.gz_heatmap_from_map_device(device, int(ptr) or None, w, h, pitch, good, bad, C.byref(output)))
+
+    def probe_emit_heat(self, plane, good, bad, output, device=0):
+        """gz_probe_emit_heat: the float32 [h][w] `plane` through the heat map's kernel alone, into `output`
+        (device_output(...))."""
+        p = np.ascontiguousarray(plane, np.float32)
+        h, w = p.shape
+        self.check(self.lib.gz_probe_emit_heat(device, _ptr(p), w, h, good, bad, C.byref(output)))
+
+    def probe_heat_thresholds(self):
+        """gz_probe_heat_thresholds: float64 [255], entry k - 1 the least v whose byte is >= k."""
+        thr = np.zeros(255, np.float64)
+        self.check(self.lib.gz_probe_heat_thresholds(_ptr(thr)))
+        return thr
+
 
 class Context:
     """One (image, GPU) context == one guetzli::ButteraugliComparator + OutputImage."""
@@ -587,6 +624,14 @@ class Context:
                                                       None if dmap is None else C.byref(dmap)))
         return float(dist[0])
 
+    def compare_device_pixels_heat(self, other, heat, good, bad, dmap=None):
+        """gz_compare_device_pixels_heat: compare_device_pixels, and the comparison's heat map into `heat`
+        (device_output(...)) under the thresholds good and bad."""
+        dist = np.zeros(1, np.float32)
+        self._chk(self.L.lib.gz_compare_device_pixels_heat(self.handle, C.byref(other), _ptr(dist), None if dmap is None else C.byref(dmap),
+                                                           C.byref(heat), good, bad))
+        return float(dist[0])
+
     def compare_rgb(self, rgb, want_distmap=True):
         """gz_compare_rgb: the same for host bytes uint8 [h][w][3] -> (distance, float32 [h][w] map or None)."""
         px = np.ascontiguousarray(rgb, np.uint8)
@@ -599,6 +644,10 @@ class Context:
     def distmap_device(self, dmap):
         """gz_distmap_device: the distance map of the last comparison that stored one, into dmap (device_map(...))."""
         self._chk(self.L.lib.gz_distmap_device(self.handle, C.byref(dmap)))
+
+    def heatmap_device(self, good, bad, output):
+        """gz_heatmap_device: the heat map of that distance map into `output` (device_output(...))."""
+        self._chk(self.L.lib.gz_heatmap_device(self.handle, good, bad, C.byref(output)))
 
     def compare_begin(self):
         self._chk(self.L.lib.gz_compare_begin(self.handle))

@@ -282,7 +282,7 @@ struct gz_ctx {
   std::vector<Owned> owned;
   std::vector<hipEvent_t*> owned_events;
   // The groups made on first use, each made only through its mark here (regrow() below: set last)
-  struct Made { bool entropy = false, rank = false, order_blocks = false, part = false, descent = false, step_delta = false, scan_state[2] = {false, false}, silver = false, emit = false; } made;
+  struct Made { bool entropy = false, rank = false, order_blocks = false, part = false, descent = false, step_delta = false, scan_state[2] = {false, false}, silver = false, emit = false, heat = false; } made;
   int device = 0;
   int w = 0, h = 0, bw = 0, bh = 0, nb = 0, pitch = 0;
   size_t plane = 0;   // floats per plane
@@ -317,6 +317,7 @@ struct gz_ctx {
   hipEvent_t ev_ingest = nullptr;      // gz_set_rgb_device: the producer's stream has written the source (made on first use)
   hipEvent_t ev_emit = nullptr;        // gz_reconstruct_device: the consumer's stream before, this context's stream behind the emit kernel (made on first use)
   float* d_emit_lut = nullptr;         // ... and the float32 elements of the 256 bytes (made.emit)
+  float* d_heat_tab = nullptr;         // gz_heatmap_device: those 256 floats, and behind them the 255 thresholds of a byte (made.heat)
   std::string err;
 
   uint8_t* d_rgb = nullptr;

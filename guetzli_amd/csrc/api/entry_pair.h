@@ -66,13 +66,15 @@ static void pair_compare_drops(gz_ctx* c) {
 
 // lin[] holds the other image's linear planes: the chain from its second kernel on, as enqueue_compare runs it behind
 // the reconstruction -- against pi0, the image maximum cleared by a fill -- then the map's two exits and the distance.
-static int pair_compare_tail(gz_ctx* c, float* distance, const gz_device_map* map, float* host_map) {
-  const bool want_map = map != nullptr || host_map != nullptr;
+// heat (may be NULL): the map's heat map goes out behind the map itself; asking for it stores the map.
+static int pair_compare_tail(gz_ctx* c, float* distance, const gz_device_map* map, float* host_map, const HeatRequest* heat = nullptr) {
+  const bool want_map = map != nullptr || host_map != nullptr || heat != nullptr;
   const ChainStreams cs = chain_streams(c, !single_stream_wanted(c));
   TRY(stage_opsin(c, cs.main));
   TRY(stage_separate(c, cs, &c->pi1));
   TRY(stage_diffmap(c, cs, c->pi0, c->pi1, kWantBlockMax | (want_map ? kWantDistmap : 0u), ClearMax::kMemset));
   if (map) TRY(emit_distmap(c, map));
+  if (heat) TRY(emit_heat(c, *heat));
   void* res = nullptr;
   TRY(result_buffer(c, 4, &res));
   HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits, 4, hipMemcpyDeviceToHost, c->stream));
@@ -90,15 +92,19 @@ static int pair_compare_state(gz_ctx* c, const char* who) {
   return GZ_OK;
 }
 
-int gz_compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float* distance, const gz_device_map* map) {
+// gz_compare_device_pixels, and with heat != NULL gz_compare_device_pixels_heat.
+static int compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float* distance, const gz_device_map* map, const HeatRequest* heat) {
   if (!c || !distance) return GZ_E_ARG;
   if (check_device_pixels(other, c->w, c->h) != GZ_OK) return GZ_E_ARG;   // (before any device call)
   if (map && check_device_map(map, c->w, c->h) != GZ_OK) return GZ_E_ARG;
+  if (heat && check_heat_request(*heat, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   DeviceScope ds_(c);
   if (const int rc = check_device_pointer(c->device, other, c->w, c->h, &c->err)) return rc;
   if (map)
     if (const int rc = check_device_range(c->device, map->data, device_map_last(map, c->w, c->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
-  TRY(pair_compare_state(c, "gz_compare_device_pixels"));
+  if (heat)
+    if (const int rc = check_device_range(c->device, heat->out->data, device_output_last(heat->out, c->w, c->h), ingest_elem_size(heat->out->dtype), "heat", &c->err)) return rc;
+  TRY(pair_compare_state(c, heat ? "gz_compare_device_pixels_heat" : "gz_compare_device_pixels"));
   pair_compare_drops(c);
   if (other->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
     if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
@@ -108,7 +114,17 @@ int gz_compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float* di
   // the packed bytes go to the reconstruction's scratch: d_rgb is the original's, and stays
   launch_ingest(c->stream, other, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
   KCHK(c);
-  return pair_compare_tail(c, distance, map, nullptr);   // (its synchronise: `other` is read when the call returns)
+  return pair_compare_tail(c, distance, map, nullptr, heat);   // (its synchronise: `other` is read when the call returns)
+}
+
+int gz_compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float* distance, const gz_device_map* map) {
+  return compare_device_pixels(c, other, distance, map, nullptr);
+}
+
+int gz_compare_device_pixels_heat(gz_ctx* c, const gz_device_pixels* other, float* distance, const gz_device_map* map,
+                                  const gz_device_output* heat, double good, double bad) {
+  const HeatRequest req{heat, good, bad};
+  return compare_device_pixels(c, other, distance, map, heat ? &req : nullptr);
 }
 
 int gz_compare_rgb(gz_ctx* c, const uint8_t* host_rgb, float* distance, float* host_distmap) {

@@ -641,6 +641,55 @@ def _map_destination(x, w, h, device):
     return ptr, name, strides, stream, ordinal
 
 
+def _new_heat_tensor(w, h, ordinal):
+    """A fresh uint8 [h][w][3] torch tensor on GPU `ordinal`, from the calling thread's current stream."""
+    return _new_device_tensor(w, h, "uint8", "HWC", ordinal)
+
+
+def _heat_destination(x, w, h, device):
+    """_device_destination of a heat map's destination: [h][w][3], or [3][h][w] where the shape says so."""
+    if not is_device_resident(x):
+        raise TypeError("heatmap=: True, or a device-resident image to fill")
+    shape = tuple(x.shape) if hasattr(x, "shape") else tuple(x.__cuda_array_interface__["shape"])
+    layout = "CHW" if len(shape) == 3 and shape[0] == 3 and shape[2] != 3 else "HWC"
+    return _device_destination(x, w, h, layout, device)
+
+
+def _heat_thresholds(good, bad):
+    """ScoreToRgb's thresholds: the caller's, or the reference tool's fuzzy_inverse(1.5) and fuzzy_inverse(0.5)."""
+    if good is None or bad is None:
+        dgood, dbad = _pair_library().default_heat_thresholds()
+        good, bad = dgood if good is None else good, dbad if bad is None else bad
+    good, bad = float(good), float(bad)
+    if not 0 < good < bad < float("inf"):
+        raise ValueError(f"heat map thresholds good={good}, bad={bad}: 0 < good < bad, both finite")
+    return good, bad
+
+
+def _heat_source(x):
+    """(ptr, w, h, pitch in floats, device ordinal, what keeps the memory alive) of a float32 2-D distance map on a GPU."""
+    if getattr(x, "is_cuda", False):   # a torch tensor
+        import torch
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise TypeError(f"a distance map is a 2-D float32 image, not {tuple(x.shape)} of {x.dtype}")
+        h, w = x.shape
+        if (w > 1 and x.stride(1) != 1) or (h > 1 and x.stride(0) < w):
+            x = x.contiguous()
+        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        return x.data_ptr(), w, h, max(x.stride(0), w), ordinal, x
+    if not hasattr(x, "__cuda_array_interface__"):
+        raise TypeError("a distance map is a device-resident 2-D float32 image")
+    cai = x.__cuda_array_interface__
+    dt, shape = np.dtype(cai["typestr"]), tuple(cai["shape"])
+    if dt != np.float32 or len(shape) != 2:
+        raise TypeError(f"a distance map is a 2-D float32 image, not {shape} of {dt}")
+    h, w = shape
+    sy, sx = (4 * w, 4) if cai.get("strides") is None else tuple(cai["strides"])
+    if (w > 1 and sx != 4) or (h > 1 and (sy % 4 or sy < 4 * w)):
+        raise ValueError(f"a distance map with byte strides {(sy, sx)}: make it contiguous in x first")
+    return cai["data"][0], w, h, max(sy // 4, w), 0, x
+
+
 def _new_map_tensor(w, h, ordinal):
     """A fresh float32 [h][w] torch tensor on GPU `ordinal`, from the calling thread's current stream."""
     import torch
@@ -741,32 +790,56 @@ class Comparator:
         ptr, name, strides, consumer, _ = _map_destination(distmap, self.w, self.h, self.device)
         return distmap, device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
 
-    def _compare(self, other, out, dmap):
+    def _heat_destination(self, heatmap, good, bad, stream):
+        """heatmap= -> (what compare returns as the heat map, capi.GzDeviceOutput, good, bad) -- None without one."""
+        if heatmap is None or heatmap is False:
+            return None
+        good, bad = _heat_thresholds(good, bad)
+        if heatmap is True:
+            heatmap = _new_heat_tensor(self.w, self.h, self.device)
+        ptr, name, strides, consumer, _ = _heat_destination(heatmap, self.w, self.h, self.device)
+        return heatmap, device_output(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)), good, bad
+
+    def _compare(self, other, out, dmap, heat=None):
         if self._ctx is None:
             raise ValueError("the Comparator is closed")
         if other.rgb is not None:   # host bytes: their map comes back to the host too, and is emitted from the plane it left
-            d, _ = self._ctx.compare_rgb(other.rgb, want_distmap=dmap is not None)
+            d, _ = self._ctx.compare_rgb(other.rgb, want_distmap=dmap is not None or heat is not None)
             if dmap is not None:
                 self._ctx.distmap_device(dmap)
+            if heat is not None:
+                self._ctx.heatmap_device(heat[2], heat[3], heat[1])
+        elif heat is not None:
+            d = self._ctx.compare_device_pixels_heat(other.pixels, heat[1], heat[2], heat[3], dmap)
         else:
             d = self._ctx.compare_device_pixels(other.pixels, dmap)
-        return d if dmap is None else (d, out)
+        if dmap is None and heat is None:
+            return d
+        return (d,) + (() if dmap is None else (out,)) + (() if heat is None else (heat[0],))
 
-    def compare(self, distorted, distmap=None, layout=None, stream=None, background=None):
+    def compare(self, distorted, distmap=None, layout=None, stream=None, background=None, heatmap=None, good=None, bad=None):
         """The butteraugli distance of `distorted` (as process() accepts an image; the reference's size, on its GPU)
         from the reference -> float, or with distmap= -> (float, map).  distmap=True: a fresh float32 [H, W] torch
         tensor on the reference's GPU, allocated on the calling thread's current stream; work enqueued on that stream
         afterwards sees the map.  distmap=tensor: that 2-D float32 / float16 / bfloat16 tensor (or
         __cuda_array_interface__ object) is filled under its own strides -- a crop inside a larger tensor is written
         without touching what surrounds it; flipped and expanded views are refused -- and returned.  stream= overrides
-        the producer's stream of `distorted` and the consumer's of the map (a hipStream_t handle; 0: none)."""
+        the producer's stream of `distorted` and the consumer's of the map (a hipStream_t handle; 0: none).
+        heatmap=: butteraugli's colour picture of the map (CreateHeatMapImage, byte for byte) is appended to the return
+        value -- (float, heat) or (float, map, heat).  True: a fresh uint8 [H, W, 3] torch tensor on the reference's
+        GPU; a tensor: filled in place, of any dtype, layout ([H, W, 3] or [3, H, W]) and crop view decode(out=) takes,
+        with the same refusals.  good= and bad=: ScoreToRgb's thresholds, by default fuzzy_inverse(1.5) and
+        fuzzy_inverse(0.5), as the reference's tool draws its heat maps."""
         other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background)
         _pair_sizes(_PairImage(self.w, self.h), other)
-        out, dmap = self._destination(distmap, stream if is_device_resident(distorted) else None)
-        return self._compare(other, out, dmap)
+        consumer = stream if is_device_resident(distorted) else None
+        heat = self._heat_destination(heatmap, good, bad, consumer)
+        out, dmap = self._destination(distmap, consumer)
+        return self._compare(other, out, dmap, heat)
 
 
-def butteraugli(reference, distorted, distmap=None, layout=None, device=None, stream=None, background=None):
+def butteraugli(reference, distorted, distmap=None, layout=None, device=None, stream=None, background=None, heatmap=None,
+                good=None, bad=None):
     """The butteraugli distance (guetzli's, bit for bit) of two images of one size -> float, or with distmap= ->
     (float, map): distmap=True gives a float32 [H, W] torch tensor on the reference's GPU, distmap=tensor fills a 2-D
     float32 / float16 / bfloat16 tensor (see Comparator.compare).
@@ -775,6 +848,7 @@ def butteraugli(reference, distorted, distmap=None, layout=None, device=None, st
     __cuda_array_interface__ objects of every dtype, layout and stride it takes; layout=, background= and stream=
     apply to both -- and the bytes compared are the bytes process() would encode.
     ValueError, before anything is computed: sizes that differ, sizes under 8 x 8, images on different devices.
+    heatmap=, good=, bad=: the map's heat map, appended to the return value (see Comparator.compare).
     For many images against one reference, Comparator keeps the reference's half of the work."""
     ref = _pair_image(reference, layout, device, stream if is_device_resident(reference) else None, background)
     known = ref.ordinal if ref.ordinal is not None else device
@@ -784,6 +858,41 @@ def butteraugli(reference, distorted, distmap=None, layout=None, device=None, st
     ordinal = known if known is not None else (other.ordinal if other.ordinal is not None else 0)
     if distmap is not None and distmap is not False and distmap is not True:
         _map_destination(distmap, ref.w, ref.h, ordinal)   # (refused before the reference is worked on)
+    if heatmap is not None and heatmap is not False:
+        _heat_thresholds(good, bad)
+        if heatmap is not True:
+            _heat_destination(heatmap, ref.w, ref.h, ordinal)
     with Comparator._of(ref, ordinal) as cmp:
-        out, dmap = cmp._destination(distmap, stream if (ref.pixels is not None or other.pixels is not None) else None)
-        return cmp._compare(other, out, dmap)
+        consumer = stream if (ref.pixels is not None or other.pixels is not None) else None
+        heat = cmp._heat_destination(heatmap, good, bad, consumer)
+        out, dmap = cmp._destination(distmap, consumer)
+        return cmp._compare(other, out, dmap, heat)
+
+
+def fuzzy_class(score):
+    """ButteraugliFuzzyClass (butteraugli.cc:1903-1921): a distance as a quality class between 2 (good) and 0 (bad)."""
+    return _pair_library().fuzzy_class(score)
+
+
+def fuzzy_inverse(seek):
+    """ButteraugliFuzzyInverse (butteraugli.cc:1923-1934): the distance of the class `seek`."""
+    return _pair_library().fuzzy_inverse(seek)
+
+
+def heatmap(distmap, good=None, bad=None, out=None, dtype="uint8", layout="HWC", stream=None):
+    """butteraugli's heat map (CreateHeatMapImage, byte for byte) of any float32 2-D distance map on a GPU -- a torch
+    tensor, or an object with __cuda_array_interface__; a tensor that is not contiguous in x is copied first.
+    Returns a torch tensor on the map's GPU, [H, W, 3] ("HWC") or [3, H, W] ("CHW") of `dtype` -- uint8 the bytes,
+    uint16 byte * 257, float32 / float16 / bfloat16 byte / 255 -- or fills out= as decode(out=) does.  good= and bad=
+    as in Comparator.compare.  The map must be complete on the calling thread's current stream (stream= overrides: a
+    hipStream_t handle; 0: none -- the map is complete when the call starts); work enqueued there afterwards sees the
+    picture."""
+    good, bad = _heat_thresholds(good, bad)
+    ptr, w, h, pitch, ordinal, keep = _heat_source(distmap)
+    if out is None:
+        out = _new_device_tensor(w, h, dtype, layout, ordinal)
+    optr, name, strides, consumer, _ = _heat_destination(out, w, h, ordinal)
+    _pair_library().heatmap_from_map_device(ptr, w, h, pitch, good, bad,
+                                            device_output(optr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)), device=ordinal)
+    del keep
+    return out

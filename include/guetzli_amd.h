@@ -57,8 +57,9 @@ int gz_abi_version(void);                 /* currently 6 (5 without the two expe
                                              so were gz_device_pixels and its three entries, and gz_device_output and
                                              its three (gz_decode_coeffs_device, gz_decode_coeffs,
                                              gz_reconstruct_device), and gz_device_map and its entries
-                                             (gz_compare_device_pixels, gz_compare_rgb, gz_distmap_device), by the same
-                                             rule */
+                                             (gz_compare_device_pixels, gz_compare_rgb, gz_distmap_device), and the heat
+                                             map's entries (gz_heatmap_device, gz_compare_device_pixels_heat,
+                                             gz_heatmap_from_map_device, gz_butteraugli_fuzzy_*), by the same rule */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -366,6 +367,34 @@ int gz_compare_device_pixels(gz_ctx* ctx, const gz_device_pixels* other, float* 
 int gz_compare_rgb(gz_ctx* ctx, const uint8_t* host_rgb, float* distance, float* host_distmap);
 int gz_distmap_device(gz_ctx* ctx, const gz_device_map* map);
 
+/* Heat maps: butteraugli's colour picture of a distance map, on the device -------------
+ * CreateHeatMapImage (butteraugli.cc:1979-1992): every distance through ScoreToRgb (:1938-1975) with the thresholds
+ * good and bad, written by one kernel (k_emit_heat) into a gz_device_output -- a strided w x h x 3 image of any of its
+ * five element types, described, checked and ordered on streams exactly as for the decoded pixels above; the element
+ * of a byte is the same.  The bytes are the reference's for every finite distance, both zeros, negatives (black) and
+ * +infinity (white); for NaN, where the reference is undefined, they are unspecified.  ScoreToRgb's arithmetic runs in
+ * FP64 in the reference's order; its (uint8_t)(255 * pow(v, 0.5) + 0.5) is answered from 255 thresholds that the HOST's
+ * libm yields once per process.  Should that libm's pow fail the table's monotonicity check, every
+ * entry here returns GZ_E_STATE (gz_last_error says why) and nothing else is affected.
+ * GZ_E_ARG (before any device call): gz_device_output's, and thresholds that are not 0 < good < bad < infinity.
+ * gz_butteraugli_fuzzy_class / _inverse: ButteraugliFuzzyClass / ButteraugliFuzzyInverse (butteraugli.cc:1903-1934) with
+ * the host's exp; no device call.  The reference's tool draws its heat maps with good = inverse(1.5), bad = inverse(0.5).
+ * gz_heatmap_device: the heat map of the map gz_distmap_device would write.  GZ_E_STATE if the last comparison stored
+ * none, and while a Compare or phase-B work of the context is in flight.  No claim of the context changes.
+ * gz_compare_device_pixels_heat: gz_compare_device_pixels with a heat map of the comparison into `heat` (may be NULL:
+ * then it IS gz_compare_device_pixels).  Asking for a heat map stores the distance map, with or without `map`.
+ * gz_heatmap_from_map_device: without a context, the heat map of a float32 plane in the caller's device memory,
+ * element (y, x) at map[y*pitch + x], pitch >= w in floats, 0 < w, h < 65536.  The plane must be complete on
+ * out->consumer_stream (without one: when the call starts).  Temporaries come from the device pool, all or none; the
+ * call waits for its own work. */
+double gz_butteraugli_fuzzy_class(double score);
+double gz_butteraugli_fuzzy_inverse(double seek);
+int gz_heatmap_device(gz_ctx* ctx, double good, double bad, const gz_device_output* out);
+int gz_compare_device_pixels_heat(gz_ctx* ctx, const gz_device_pixels* other, float* distance, const gz_device_map* map,
+                                  const gz_device_output* heat, double good, double bad);
+int gz_heatmap_from_map_device(int device, const float* map, int w, int h, int pitch, double good, double bad,
+                               const gz_device_output* out);
+
 /* Double-precision DCT -----------------------------------------
  * gz_dct_double_blocks: ComputeBlockDCTDouble (inverse == 0) / ComputeBlockIDCTDouble
  * (inverse != 0), dct_double.cc:76-85, on n bare blocks of 64 doubles, in place.
@@ -671,6 +700,12 @@ int gz_probe_mask(gz_ctx* ctx, const float* xyb0_3, const float* xyb1_3, float* 
  * pattern) is uploaded to a plane from the device pool and written into map as gz_distmap_device writes a distance
  * map.  The call waits for its own work. */
 int gz_probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map);
+/* k_emit_heat alone: host_plane as above, written into out as gz_heatmap_from_map_device writes a device plane.
+ * gz_probe_heat_thresholds: the table the kernel searches, thr255[k - 1] = the least double v for which the host's
+ * (uint8_t)(255 * pow(v, 0.5) + 0.5) is >= k; GZ_E_STATE where the host's pow fails the table's check.  No device call. */
+int gz_probe_emit_heat(int device, const float* host_plane, int w, int h, double good, double bad,
+                       const gz_device_output* out);
+int gz_probe_heat_thresholds(double* thr255);
 /* Block kernels on bare 64-element blocks (n blocks each). */
 int gz_probe_idct_blocks(int device, const int16_t* blocks, int n, uint8_t* out);
 int gz_probe_fdct_blocks(int device, int16_t* blocks, int n);
