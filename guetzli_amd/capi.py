@@ -122,6 +122,11 @@ SIGNATURES = {
     "gz_heatmap_from_map_device": (_I, [_I, _P, _I, _I, _I, C.c_double, C.c_double, _P]),
     "gz_probe_emit_heat": (_I, [_I, _P, _I, _I, C.c_double, C.c_double, _P]),
     "gz_probe_heat_thresholds": (_I, [_P]),
+    "gz_create_from_device_linear": (_P, [_I, _I, _I, _P, C.c_float, C.POINTER(_I)]),
+    "gz_set_linear_device": (_I, [_P, _P, C.c_float]),
+    "gz_compare_device_linear": (_I, [_P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
+    "gz_butteraugli_linear": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
+    "gz_probe_linear_planes": (_I, [_P, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -364,6 +369,21 @@ class Library:
         """gz_create_from_device: a context whose original is the device-resident `image` (device_image(...))."""
         return Context.from_device(self, image, w, h, target, device)
 
+    def context_from_device_linear(self, image, w, h, scale=1.0, device=0):
+        """gz_create_from_device_linear: a context whose original is the LINEAR float image `image` (device_pixels(...)
+        of float32 / float16 / bfloat16, raw intensity 0..255 after `scale`)."""
+        return Context.from_device_linear(self, image, w, h, scale, device)
+
+    def butteraugli_linear(self, ref, other, w, h, scale=1.0, dmap=None, heat=None, good=0.0, bad=0.0, device=0):
+        """gz_butteraugli_linear: ButteraugliInterface of two linear float images (device_pixels(...)), any size from
+        1 x 1 -> (distance, elements the clamp to [0, 255] altered, of both images)."""
+        dist = np.zeros(1, np.float32)
+        clamped = C.c_uint64(0)
+        self.check(self.lib.gz_butteraugli_linear(device, w, h, C.byref(ref), C.byref(other), float(scale), _ptr(dist),
+                                                  None if dmap is None else C.byref(dmap), None if heat is None else C.byref(heat),
+                                                  good, bad, C.byref(clamped)))
+        return float(dist[0]), clamped.value
+
     def pack_rgb_device(self, image, w, h, device=0):
         """gz_pack_rgb_device / gz_pack_rgb_device_pixels: the ingest kernel's bytes of `image` (device_image(...) /
         device_pixels(...)) -> uint8 [h][w][3]."""
@@ -454,6 +474,20 @@ class Context:
             library.check(err.value or -3)
         return self
 
+    @classmethod
+    def from_device_linear(cls, library, image, w, h, scale=1.0, device=0):
+        """gz_create_from_device_linear: the original is the linear float image `image`; such a context has rgb = None
+        and no coefficients (encode_rgb and the searches raise GZ_E_STATE until set_rgb* gives it 8-bit pixels)."""
+        self = cls.__new__(cls)
+        self.L = library
+        self.rgb = None
+        self._set_geometry(w, h)
+        err = C.c_int(0)
+        self.handle = library.lib.gz_create_from_device_linear(device, w, h, C.byref(image), float(scale), C.byref(err))
+        if not self.handle:
+            library.check(err.value or -3)
+        return self
+
     def _set_geometry(self, w, h):
         self.w, self.h = w, h
         self.bw, self.bh = (self.w + 7) // 8, (self.h + 7) // 8
@@ -512,6 +546,11 @@ class Context:
         self.rgb = None
         entry = self.L.lib.gz_set_rgb_device_pixels if isinstance(image, GzDevicePixels) else self.L.lib.gz_set_rgb_device
         self._chk(entry(self.handle, C.byref(image)))
+
+    def set_linear_device(self, image, scale=1.0):
+        """gz_set_linear_device: the original replaced by the linear float image `image` (device_pixels(...), w x h)."""
+        self.rgb = None
+        self._chk(self.L.lib.gz_set_linear_device(self.handle, C.byref(image), float(scale)))
 
     def reconstruct_device(self, output):
         """gz_reconstruct_device: the candidate's pixels (gz_reconstruct's srgb) written into `output`
@@ -631,6 +670,17 @@ class Context:
         self._chk(self.L.lib.gz_compare_device_pixels_heat(self.handle, C.byref(other), _ptr(dist), None if dmap is None else C.byref(dmap),
                                                            C.byref(heat), good, bad))
         return float(dist[0])
+
+    def compare_device_linear(self, other, scale=1.0, dmap=None, heat=None, good=0.0, bad=0.0):
+        """gz_compare_device_linear: compare_device_pixels for a LINEAR float image `other` (device_pixels(...) of
+        float32 / float16 / bfloat16, raw intensity 0..255 after `scale`) -> (distance, elements the clamp altered);
+        dmap (device_map(...)) and heat (device_output(...), under the thresholds good and bad) as there."""
+        dist = np.zeros(1, np.float32)
+        clamped = C.c_uint64(0)
+        self._chk(self.L.lib.gz_compare_device_linear(self.handle, C.byref(other), float(scale), _ptr(dist),
+                                                      None if dmap is None else C.byref(dmap), None if heat is None else C.byref(heat),
+                                                      good, bad, C.byref(clamped)))
+        return float(dist[0]), clamped.value
 
     def compare_rgb(self, rgb, want_distmap=True):
         """gz_compare_rgb: the same for host bytes uint8 [h][w][3] -> (distance, float32 [h][w] map or None)."""
@@ -934,6 +984,12 @@ class Context:
         s = np.zeros(1, np.float32)
         self._chk(self.L.lib.gz_probe_diffmap(self.handle, _ptr(a), _ptr(b), _ptr(d), _ptr(s)))
         return d, float(s[0])
+
+    def probe_linear_planes(self):
+        """gz_probe_linear_planes: the context's linear planes as they are now -> float32 [3][h][w]."""
+        out = np.zeros((3, self.h, self.w), np.float32)
+        self._chk(self.L.lib.gz_probe_linear_planes(self.handle, _ptr(out)))
+        return out
 
     def probe_mask(self, xyb0, xyb1):
         a = np.ascontiguousarray(xyb0, np.float32)

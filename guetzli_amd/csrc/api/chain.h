@@ -633,6 +633,7 @@ int ensure_pip(gz_ctx* c) {
 // (CompareBlock, :484-486).
 int ensure_block_mask(gz_ctx* c) {
   if (c->have_block_mask) return GZ_OK;
+  TRY(byte_original(c, "StartBlockComparisons' mask"));   // (it is Mask() of d_rgb)
   TRY(ensure_pip(c));
   if (!c->d_block_mask) TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&c->d_block_mask, sizeof(float) * 3 * c->nb}}));
   const hipStream_t stream = c->stream;

@@ -327,6 +327,11 @@ struct gz_ctx {
   float* d_srgb_lut = nullptr; // float(Srgb8ToLinearTable[i])
   double* d_mask_luts = nullptr;
   float* d_block_max = nullptr;
+  // [kResultWords]: [0] the image maximum the chain accumulates (its float bits); behind it, so that ONE copy fetches
+  // them with the distance, what the linear entries count (entry_linear.h): [kWordClamped] the elements k_ingest_linear
+  // altered, [kWordRegionMax] k_region_max's maximum of a small image's window.  Each is cleared by a fill in front of
+  // the kernel that accumulates into it.
+  enum { kWordClamped = 1, kWordRegionMax = 2, kResultWords = 4 };
   unsigned* d_max_bits = nullptr;
   uint8_t* d_srgb_out = nullptr;
   int32_t* d_blkidx = nullptr; size_t blkidx_cap = 0;
@@ -409,6 +414,12 @@ struct gz_ctx {
   // depends on that buffer before its first copy or launch.  RE-ARM ONLY ON SUCCESS -- a claim is set again only as the
   // last state change before `return GZ_OK`.  Dropping is always safe: it costs one full reconstruction or opsin pass.
   bool have_orig = false, have_cand = false, have_distmap = false;
+  // The original is a linear float image (gz_create_from_device_linear / gz_set_linear_device, entry_linear.h): pi0 and
+  // sup0 are its, d_rgb is NOT -- there are no 8-bit pixels of it, so no coefficients either.  The entries that read
+  // d_rgb or d_orig refuse such a context (byte_original below); gz_set_rgb* give it an 8-bit original again and clear
+  // this.  Set as the last state change of a successful call, dropped before the first write of a new original.
+  bool orig_linear = false;
+  unsigned long long orig_clamped = 0;   // elements of that image the value rule altered (gz_kernels_ingestlin.h)
   // c->distmap holds the distance map of the last comparison (gz_distmap_device emits it): only a comparison asked for
   // its map stores one (kWantDistmap), and the plane is scratch of every SeparateFrequencies (stage_separate drops this)
   bool have_map_plane = false;
@@ -478,6 +489,14 @@ namespace {
       return GZ_E_HIP;                                                               \
     }                                                                                \
   } while (0)
+
+// For the entries that read d_rgb or d_orig: a context whose original is a linear float image has neither.
+static int byte_original(gz_ctx* c, const char* who) {
+  if (!c->orig_linear) return GZ_OK;
+  c->err = std::string(who) + ": the context's original is a linear float image (gz_create_from_device_linear / gz_set_linear_device), "
+           "which has no 8-bit pixels and no coefficients; gz_set_rgb* gives the context an 8-bit original";
+  return GZ_E_STATE;
+}
 
 // The one way a context comes by memory: the buffers of `bufs`, device or pinned, all of them or none.  What they held
 // goes back to the pool first, the pointers null and the capacity zero BEFORE the allocations that may fail; if one

@@ -8,6 +8,7 @@ extern "C" {
 int gz_encode_rgb(gz_ctx* c, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_encode_rgb"));
   if (c->cfac != 1) set_frame(c, 1);   // back to 4:4:4
   c->have_orig = false;
   GZ_LAUNCH(k_encode_rgb, dim3(gz_div_up(c->nb, kBlocksPerWG)), dim3(256), c->stream, c->d_rgb,
@@ -53,6 +54,7 @@ int gz_frame_layout(gz_ctx* c, int* chroma_factor, int* luma_blocks, int* chroma
 int gz_quantize(gz_ctx* c, const int* q, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_quantize"));
   if (!c->have_orig) { c->err = "no original coefficients"; return GZ_E_STATE; }
   int ones[192];
   if (!q) { for (int i = 0; i < 192; ++i) ones[i] = 1; q = ones; }

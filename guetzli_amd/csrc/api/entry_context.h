@@ -231,7 +231,12 @@ static void launch_ingest(hipStream_t stream, const gz_device_pixels* img, int w
 }
 
 static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img);
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err);
+// (entry_linear.h: a linear float image as the original -- what it is, where its memory must live, its arrival)
+struct LinearSource;
+static int check_linear_pointer(int device, const LinearSource* src, std::string* why);
+static int set_linear_device(gz_ctx* c, const LinearSource* src);
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err,
+                              const LinearSource* linear = nullptr);
 gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
   int prev = -1;
   if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
@@ -258,12 +263,14 @@ gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* i
   }
   return gz_create_from_device_pixels(device, w, h, &px, target, err);
 }
-// The original from host pixels (rgb) or from a device-resident image (img, checked by the caller): one of the two.
-static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err) {
+// The original from host pixels (rgb), from a device-resident image (img, checked by the caller) or from a linear float
+// image (linear, checked by the caller; w x h is then the canvas it is extended to): one of the three.
+static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err,
+                              const LinearSource* linear) {
   int dummy;
   if (!err) err = &dummy;
   *err = GZ_OK;
-  if ((!rgb && !img) || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
+  if ((!rgb && !img && !linear) || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
   // coefficient positions (3 x blocks x 64) and candidate offsets (blocks x 189) are 32-bit
   // on both sides of the ABI: 11.18 M blocks = 715 MPix is the largest image (tested: 268 MPix)
   if ((uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8) * 192u > 0x7fffffffull) { *err = GZ_E_ARG; return nullptr; }
@@ -274,6 +281,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
     return nullptr;
   }
   if (img && check_device_pointer(device, img, w, h, nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
+  if (linear && check_linear_pointer(device, linear, nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
   gz_ctx* c = new gz_ctx;
   c->device = device;
   c->w = w; c->h = h;
@@ -314,7 +322,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
                             {{(void**)&c->d_rgb, (size_t)3 * w * h}, {(void**)&c->d_orig, ncoef * 2}, {(void**)&c->d_cand, ncoef * 2},
                              {(void**)&c->d_q, sizeof(int) * 192}, {(void**)&c->d_srgb_lut, sizeof(float) * 256},
                              {(void**)&c->d_mask_luts, sizeof(double) * 2048}, {(void**)&c->d_block_max, sizeof(float) * c->nb},
-                             {(void**)&c->d_max_bits, sizeof(unsigned)}, {(void**)&c->d_srgb_out, (size_t)3 * w * h},
+                             {(void**)&c->d_max_bits, sizeof(unsigned) * gz_ctx::kResultWords}, {(void**)&c->d_srgb_out, (size_t)3 * w * h},
                              {(void**)&c->arena, sizeof(float) * c->plane * kNumPlanes}}))
     return fail(rc);
   for (int i = kNumPlanes - 1; i >= 0; --i) c->free_planes.push_back(c->arena + (size_t)i * c->plane);
@@ -355,7 +363,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
     if (c->blur[b].r != kBlurSpecs[b].r) return fail(GZ_E_STATE);
   }
   {
-    const int rc = img ? set_rgb_device(c, img) : gz_set_rgb(c, rgb);
+    const int rc = linear ? set_linear_device(c, linear) : img ? set_rgb_device(c, img) : gz_set_rgb(c, rgb);
     if (rc != GZ_OK) return fail(rc);
   }
 #undef CHK0
@@ -387,7 +395,9 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   GZ_LAUNCH(k_linear_from_rgb8, grid, dim3(256), c->stream, c->d_rgb, c->w, c->h, c->pitch,
             c->plane, c->d_srgb_lut, c->lin[0]);
   KCHK(c);
-  return original_from_lin(c);
+  TRY(original_from_lin(c));
+  c->orig_linear = false;   // (d_rgb is the original's again)
+  return GZ_OK;
 }
 
 // (the context's device is current, img has passed check_device_pixels and check_device_pointer)
@@ -401,7 +411,9 @@ static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img) {
   }
   launch_ingest(c->stream, img, c->w, c->h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
   KCHK(c);
-  return original_from_lin(c);   // (its synchronise: the source is read when the call returns)
+  TRY(original_from_lin(c));   // (its synchronise: the source is read when the call returns)
+  c->orig_linear = false;      // (d_rgb is the original's again)
+  return GZ_OK;
 }
 
 int gz_set_rgb_device_pixels(gz_ctx* c, const gz_device_pixels* img) {

@@ -158,6 +158,7 @@ static void normal_taps(double sigma, float k[5], float* mul) {   // Normal(), :
 int gz_downsample(gz_ctx* c, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_downsample"));
   if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
   c->have_orig = false;     // (d_orig's chroma is rewritten)
   c->xyb_is_cand = false;   // scratch: planes of the candidate's evaluation (nothing of it is in flight here)
@@ -234,6 +235,7 @@ int gz_downsample(gz_ctx* c, int16_t* coeffs_out) {
 int gz_downsample_planes(gz_ctx* c, const float* y, const float* u, const float* v, int16_t* coeffs_out) {
   DeviceScope ds_(c);
   if (!c || !y || !u || !v) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_downsample_planes"));
   if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample_planes needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
   c->have_orig = false;
   c->xyb_is_cand = false;   // (xyb[] as scratch)
@@ -367,6 +369,7 @@ int silver_run(const SilverRun& r, uint64_t* counters, std::string* err) {
 int gz_downsample_silver(gz_ctx* c, int16_t* coeffs_out, uint64_t counters[2]) {
   DeviceScope ds_(c);
   if (!c) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_downsample_silver"));
   if (!c->have_orig || c->cfac != 1) { c->err = "gz_downsample_silver needs the original coefficients of a 4:4:4 frame"; return GZ_E_STATE; }
   const int w = c->w, h = c->h, w2 = (w + 1) / 2, h2 = (h + 1) / 2;
   const size_t cells = (size_t)w2 * h2;

@@ -72,9 +72,16 @@ static void launch_heat(hipStream_t stream, const float* plane, int w, int h, in
   }
 }
 
+// A window of the context's map plane: w x h from (x0, y0) on.  What a map and its heat map are emitted from where the
+// image is smaller than the plane (gz_butteraugli_linear under 8 pixels: the reference's crop, butteraugli.cc:1846-1854).
+struct MapWindow {
+  int x0, y0, w, h;
+};
+
 // c->distmap -> heat.out on the context's stream, under gz_device_output's stream contract in both directions, as
 // emit_distmap writes the map itself.  Nothing is waited for on the host, no claim of the context changes.
-static int emit_heat(gz_ctx* c, const HeatRequest& heat) {
+// win (may be NULL: the whole plane): the window heat.out, which is of ITS size, takes.
+static int emit_heat(gz_ctx* c, const HeatRequest& heat, const MapWindow* win = nullptr) {
   if (!heat_thresholds().ok) { c->err = heat_thresholds().why; return GZ_E_STATE; }
   if (!c->made.heat) {
     TRY(regrow(c, c->stream, nullptr, 0, {{(void**)&c->d_heat_tab, kHeatTabBytes}}));
@@ -85,7 +92,8 @@ static int emit_heat(gz_ctx* c, const HeatRequest& heat) {
     if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
     HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, heat.out->consumer_stream));
   }
-  launch_heat(c->stream, c->distmap, c->w, c->h, c->pitch, heat, c->d_heat_tab);
+  if (win) launch_heat(c->stream, c->distmap + ((size_t)win->y0 * c->pitch + win->x0), win->w, win->h, c->pitch, heat, c->d_heat_tab);
+  else launch_heat(c->stream, c->distmap, c->w, c->h, c->pitch, heat, c->d_heat_tab);
   KCHK(c);
   if (heat.out->consumer_stream) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, heat.out->consumer_stream));
   return GZ_OK;

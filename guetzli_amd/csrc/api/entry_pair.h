@@ -46,12 +46,14 @@ static void launch_map(hipStream_t stream, const float* plane, int w, int h, int
 
 // c->distmap -> map on the context's stream, under gz_device_output's stream contract in both directions (the
 // consumer's stream is waited for before the kernel and waits for it afterwards).  Nothing is waited for on the host.
-static int emit_distmap(gz_ctx* c, const gz_device_map* map) {
+// win (may be NULL: the whole plane): the window of the plane that map, which is of ITS size, takes.
+static int emit_distmap(gz_ctx* c, const gz_device_map* map, const MapWindow* win = nullptr) {
   if (map->consumer_stream) {
     if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
     HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, map->consumer_stream));
   }
-  launch_map(c->stream, c->distmap, c->w, c->h, c->pitch, map);
+  if (win) launch_map(c->stream, c->distmap + ((size_t)win->y0 * c->pitch + win->x0), win->w, win->h, c->pitch, map);
+  else launch_map(c->stream, c->distmap, c->w, c->h, c->pitch, map);
   KCHK(c);
   if (map->consumer_stream) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, map->consumer_stream));
   return GZ_OK;
@@ -67,20 +69,36 @@ static void pair_compare_drops(gz_ctx* c) {
 // lin[] holds the other image's linear planes: the chain from its second kernel on, as enqueue_compare runs it behind
 // the reconstruction -- against pi0, the image maximum cleared by a fill -- then the map's two exits and the distance.
 // heat (may be NULL): the map's heat map goes out behind the map itself; asking for it stores the map.
-static int pair_compare_tail(gz_ctx* c, float* distance, const gz_device_map* map, float* host_map, const HeatRequest* heat = nullptr) {
-  const bool want_map = map != nullptr || host_map != nullptr || heat != nullptr;
+// lin (may be NULL; entry_linear.h): the other image came through k_ingest_linear, whose count rides home with the
+// distance; with lin->win the images are smaller than the planes: map and heat map come from that window, and the
+// distance is k_region_max's over it.
+struct LinearTail {
+  const MapWindow* win;
+  uint64_t* clamped;   // (may be NULL)
+};
+static int pair_compare_tail(gz_ctx* c, float* distance, const gz_device_map* map, float* host_map, const HeatRequest* heat = nullptr,
+                             const LinearTail* lin = nullptr) {
+  const bool want_map = map != nullptr || host_map != nullptr || heat != nullptr || (lin && lin->win);   // (k_region_max reads the plane)
   const ChainStreams cs = chain_streams(c, !single_stream_wanted(c));
   TRY(stage_opsin(c, cs.main));
   TRY(stage_separate(c, cs, &c->pi1));
   TRY(stage_diffmap(c, cs, c->pi0, c->pi1, kWantBlockMax | (want_map ? kWantDistmap : 0u), ClearMax::kMemset));
-  if (map) TRY(emit_distmap(c, map));
-  if (heat) TRY(emit_heat(c, *heat));
+  const MapWindow* win = lin ? lin->win : nullptr;
+  if (map) TRY(emit_distmap(c, map, win));
+  if (heat) TRY(emit_heat(c, *heat, win));
+  if (win) {
+    HIPCHK(c, hipMemsetAsync(c->d_max_bits + gz_ctx::kWordRegionMax, 0, sizeof(unsigned), c->stream));
+    launch_region_max(c->stream, c->distmap, c->pitch, win->x0, win->y0, win->w, win->h, c->d_max_bits + gz_ctx::kWordRegionMax);
+    KCHK(c);
+  }
+  const size_t fetched = lin ? sizeof(unsigned) * gz_ctx::kResultWords : 4;
   void* res = nullptr;
-  TRY(result_buffer(c, 4, &res));
-  HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits, 4, hipMemcpyDeviceToHost, c->stream));
+  TRY(result_buffer(c, fetched, &res));
+  HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits, fetched, hipMemcpyDeviceToHost, c->stream));
   if (host_map) TRY(download_plane(c, c->distmap, host_map));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (for the distance: the consumer of a map does not wait for this)
-  memcpy(&c->last_distance, res, 4);
+  memcpy(&c->last_distance, (const unsigned*)res + (win ? (int)gz_ctx::kWordRegionMax : 0), 4);
+  if (lin && lin->clamped) *lin->clamped = ((const unsigned*)res)[gz_ctx::kWordClamped];
   *distance = c->last_distance;
   c->have_distmap = true;
   c->have_map_plane = want_map;

@@ -336,6 +336,7 @@ int gz_apply_candidate_steps(gz_ctx* c, int direction, const int32_t* blocks,
   DeviceScope ds_(c);
   if (!c || n < 0 || (n > 0 && (!blocks || !counts)) || !is_direction(direction))
     return GZ_E_ARG;
+  TRY(byte_original(c, "gz_apply_candidate_steps"));
   if (!c->have_search || !c->made.order_blocks || !c->have_cand || !c->have_orig) {
     c->err = "gz_order_build must precede gz_apply_candidate_steps";
     return GZ_E_STATE;

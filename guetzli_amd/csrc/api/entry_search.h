@@ -143,6 +143,7 @@ int gz_block_zeroing_orders_masked(gz_ctx* c, int comp_mask, int lookahead, int 
                                    int32_t* offsets, uint8_t* idx, float* err, int cap) {
   DeviceScope ds_(c);
   if (!c || !offsets || !idx || lookahead < 1 || cap < 0 || comp_mask < 1 || comp_mask > 7) return GZ_E_ARG;
+  TRY(byte_original(c, "gz_block_zeroing_orders"));
   if (!c->have_cand || !c->have_orig) { c->err = "needs original and candidate coefficients"; return GZ_E_STATE; }
   int mode = 0;
   TRY(search_mode_of(c, comp_mask, &mode));
@@ -263,6 +264,7 @@ int gz_compare_blocks(gz_ctx* c, int n, const int32_t* block_xy, const int16_t* 
   for (int i = 0; i < n; ++i)
     if (block_xy[2 * i] < 0 || block_xy[2 * i] >= c->bw || block_xy[2 * i + 1] < 0 || block_xy[2 * i + 1] >= c->bh)
       return GZ_E_ARG;
+  TRY(byte_original(c, "gz_compare_blocks"));
   if (c->cfac != 1) { c->err = "gz_compare_blocks takes coefficient blocks of a 4:4:4 frame (gz_compare_block_pixels serves any frame)"; return GZ_E_STATE; }
   TRY(ensure_block_mask(c));
   // staging: positions, coefficients and results share one device block kept by the context
@@ -289,6 +291,7 @@ int gz_compare_block_pixels(gz_ctx* c, int n, const int32_t* block_xy, const uin
   for (int i = 0; i < n; ++i)
     if (block_xy[2 * i] < 0 || block_xy[2 * i] >= c->bw || block_xy[2 * i + 1] < 0 || block_xy[2 * i + 1] >= c->bh)
       return GZ_E_ARG;
+  TRY(byte_original(c, "gz_compare_block_pixels"));
   TRY(ensure_block_mask(c));
   // staging: positions, pixels and results share one device block kept by the context
   const size_t need = (size_t)n * (8 + 8 + 192);

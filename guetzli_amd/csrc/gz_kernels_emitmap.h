@@ -94,6 +94,32 @@ __global__ __launch_bounds__(256) void k_emit_map(const float* __restrict__ map,
     if (i < n) emit_map_value(f[i], &dst[(long long)i * sx]);
 }
 
+// The maximum of the w x h window at (x0, y0) of a plane, into *max_bits as the chain's image maximum is formed: float
+// bits compared as unsigned -- the map is non-negative -- through atomicMax, one per wavefront at the most; the CALLER
+// has cleared *max_bits on the stream in front of the kernel.  ButteraugliScoreFromDiffmap (butteraugli.cc:1857-1867)
+// of an image under 8 pixels is the maximum over the CROPPED map (:1846-1854), not over the 8-pixel canvas the chain's
+// own maximum covers.  One lane per pixel, rows follow each other; every thread of the block reaches the wavefront's
+// exchange, lanes behind the last pixel with a 0.  Nothing outside the window is read.
+__global__ __launch_bounds__(256) void k_region_max(const float* __restrict__ plane, int pitch, int x0, int y0, int w, int h,
+                                                    unsigned* __restrict__ max_bits) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;              // (w * h < 8 * 65536)
+  unsigned m = 0;
+  if (i < (unsigned)w * (unsigned)h) {
+    const unsigned y = i / (unsigned)w, x = i - y * (unsigned)w;
+    m = __float_as_uint(plane[(size_t)(y0 + (int)y) * pitch + (x0 + (int)x)]);
+  }
+  const int lane = (int)(threadIdx.x & 63u);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned o = (unsigned)__shfl((int)m, lane ^ d);
+    m = o > m ? o : m;
+  }
+  if (lane == 0 && m > *(volatile unsigned*)max_bits) atomicMax(max_bits, m);
+}
+static inline void launch_region_max(hipStream_t stream, const float* plane, int pitch, int x0, int y0, int w, int h, unsigned* max_bits) {
+  GZ_LAUNCH(k_region_max, dim3((unsigned)(((size_t)w * h + 255) / 256)), dim3(256), stream, plane, pitch, x0, y0, w, h, max_bits);
+}
+
 // May a layout take the 16-byte stores (host side)?  The vector of a full group sits at base + (y sy + x0) elements,
 // x0 a multiple of P = 16 / elem: 16-byte aligned if the base is and sy is a multiple of P.
 static inline bool emit_map_wide(const void* data, size_t elem, long long sy, long long sx) {

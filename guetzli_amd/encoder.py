@@ -10,7 +10,7 @@ import numpy as np
 
 import time
 
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_output, device_pixels
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_map, device_output, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -700,8 +700,9 @@ class _PairImage:
     """One image of a pair, looked at but not touched: host bytes (rgb) or the description of device-resident pixels
     (pixels, a capi.GzDevicePixels; keep: the object that owns the memory)."""
 
-    def __init__(self, w, h, rgb=None, pixels=None, ordinal=None, keep=None):
+    def __init__(self, w, h, rgb=None, pixels=None, ordinal=None, keep=None, linear=False, scale=1.0):
         self.w, self.h, self.rgb, self.pixels, self.ordinal, self.keep = w, h, rgb, pixels, ordinal, keep
+        self.linear, self.scale = linear, scale   # linear: pixels are raw linear intensity 0..255 after `scale`, not sRGB samples
 
 
 def _pair_image(x, layout, device, stream, background):
@@ -732,6 +733,52 @@ def _pair_image(x, layout, device, stream, background):
                       ordinal=ordinal, keep=x)
 
 
+LINEAR_DTYPES = ("float32", "float16", "bfloat16")
+
+
+def _upload_linear(array, ordinal):
+    """Host floats -> a torch tensor on GPU `ordinal`, on the calling thread's current stream."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(array)).to(f"cuda:{ordinal}")
+
+
+def _linear_scale(scale):
+    s = float(np.float32(scale))
+    if not 0 < s < float("inf"):
+        raise ValueError(f"scale={scale}: a finite float32 above 0 (1 for data in 0..255, 255 for data in [0, 1])")
+    return s
+
+
+def _linear_image(x, layout, device, stream, scale):
+    """`x` as a LINEAR float image -> _PairImage: a GPU tensor / __cuda_array_interface__ object of float32, float16 or
+    bfloat16 in any layout and strides process() takes, three channels or one; host float32 / float16 arrays are
+    uploaded first.  ValueError for everything else.  No device call but that upload."""
+    scale = _linear_scale(scale)
+    if not is_device_resident(x):
+        a = np.asarray(x)
+        if a.dtype.name not in ("float32", "float16"):
+            raise ValueError(f"dtype {a.dtype}: a linear image is float32, float16 or bfloat16 (no integers; convert float64 yourself: it is a rounding)")
+        if a.ndim not in (2, 3):
+            raise ValueError(f"an image has 2 or 3 dimensions, not {a.ndim}")
+        x = _upload_linear(a, 0 if device is None else device)
+    try:
+        ptr, w, h, dtype, strides, producer, ordinal, _ = _device_source(x, layout, device, None)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    except ValueError as e:
+        if "alpha" in str(e):
+            raise ValueError("a linear image has three channels, or one (grey): alpha is not supported") from None
+        raise
+    if dtype not in LINEAR_DTYPES:
+        raise ValueError(f"dtype {dtype}: a linear image is float32, float16 or bfloat16")
+    if stream is not None:
+        producer = int(stream)
+    if any(s < 0 for s in strides):
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    return _PairImage(w, h, pixels=device_pixels(ptr, DTYPE_CODES[dtype], strides, producer), ordinal=ordinal, keep=x,
+                      linear=True, scale=scale)
+
+
 def _pair_sizes(ref, other):
     if min(ref.w, ref.h) < 8:
         raise ValueError(f"a {ref.w} x {ref.h} image: butteraugli needs at least 8 x 8")
@@ -746,10 +793,24 @@ class Comparator:
     of any dtype, layout and strides process() takes, with layout=, background= and stream= as there.
     The metric is ASYMMETRIC: this image is butteraugli's first argument, the one the masking is computed from.  The
     bytes compared are the bytes process() would encode (floats in [0, 1] rounded to bytes, uint16's high byte, alpha
-    blended over background=).  A context manager; close() frees the GPU memory."""
+    blended over background=).
+    linear=True: the images are LINEAR float images instead, as ButteraugliInterface takes them -- float32 / float16 /
+    bfloat16, three channels or one, raw linear intensity 0..255 after the multiplication by scale= (scale=255 is for
+    data in [0, 1]); nothing is rounded to a byte, so images closer than a byte step have a distance.  Values outside
+    [0, 255] after the scale (NaN too) are CLAMPED to it, which the reference does not do; `clamped` counts them.
+    linear= and scale= are the defaults of compare(), which may mix: an 8-bit image against a linear reference is its
+    table-linearised bytes against it.
+    A context manager; close() frees the GPU memory."""
 
-    def __init__(self, reference, layout=None, device=None, stream=None, background=None):
-        ref = _pair_image(reference, layout, device, stream, background)
+    def __init__(self, reference, layout=None, device=None, stream=None, background=None, linear=False, scale=1.0):
+        self.linear, self.scale = bool(linear), _linear_scale(scale)
+        self.clamped = 0   # elements of the last compare()'s image that the clamp of linear=True altered
+        if self.linear:
+            if background is not None:
+                raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
+            ref = _linear_image(reference, layout, device, stream, self.scale)
+        else:
+            ref = _pair_image(reference, layout, device, stream, background)
         _pair_sizes(ref, None)
         self._open(ref, ref.ordinal if ref.ordinal is not None else (0 if device is None else device))
 
@@ -758,11 +819,15 @@ class Comparator:
         lib = _pair_library()
         self.w, self.h, self.device = ref.w, ref.h, ordinal
         # (the target only scales gz_block_weights, which nothing here asks for)
-        self._ctx = lib.context(ref.rgb, 1.0, ordinal) if ref.rgb is not None else Context.from_device(lib, ref.pixels, ref.w, ref.h, 1.0, ordinal)
+        if ref.linear:
+            self._ctx = Context.from_device_linear(lib, ref.pixels, ref.w, ref.h, ref.scale, ordinal)
+        else:
+            self._ctx = lib.context(ref.rgb, 1.0, ordinal) if ref.rgb is not None else Context.from_device(lib, ref.pixels, ref.w, ref.h, 1.0, ordinal)
 
     @classmethod
     def _of(cls, ref, ordinal):
         self = cls.__new__(cls)
+        self.linear, self.scale, self.clamped = ref.linear, ref.scale, 0
         self._open(ref, ordinal)
         return self
 
@@ -803,7 +868,10 @@ class Comparator:
     def _compare(self, other, out, dmap, heat=None):
         if self._ctx is None:
             raise ValueError("the Comparator is closed")
-        if other.rgb is not None:   # host bytes: their map comes back to the host too, and is emitted from the plane it left
+        self.clamped = 0
+        if other.linear:
+            d, self.clamped = self._ctx.compare_device_linear(other.pixels, other.scale, dmap, *(() if heat is None else (heat[1], heat[2], heat[3])))
+        elif other.rgb is not None:   # host bytes: their map comes back to the host too, and is emitted from the plane it left
             d, _ = self._ctx.compare_rgb(other.rgb, want_distmap=dmap is not None or heat is not None)
             if dmap is not None:
                 self._ctx.distmap_device(dmap)
@@ -817,7 +885,8 @@ class Comparator:
             return d
         return (d,) + (() if dmap is None else (out,)) + (() if heat is None else (heat[0],))
 
-    def compare(self, distorted, distmap=None, layout=None, stream=None, background=None, heatmap=None, good=None, bad=None):
+    def compare(self, distorted, distmap=None, layout=None, stream=None, background=None, heatmap=None, good=None, bad=None,
+                linear=None, scale=None):
         """The butteraugli distance of `distorted` (as process() accepts an image; the reference's size, on its GPU)
         from the reference -> float, or with distmap= -> (float, map).  distmap=True: a fresh float32 [H, W] torch
         tensor on the reference's GPU, allocated on the calling thread's current stream; work enqueued on that stream
@@ -829,10 +898,19 @@ class Comparator:
         value -- (float, heat) or (float, map, heat).  True: a fresh uint8 [H, W, 3] torch tensor on the reference's
         GPU; a tensor: filled in place, of any dtype, layout ([H, W, 3] or [3, H, W]) and crop view decode(out=) takes,
         with the same refusals.  good= and bad=: ScoreToRgb's thresholds, by default fuzzy_inverse(1.5) and
-        fuzzy_inverse(0.5), as the reference's tool draws its heat maps."""
-        other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background)
+        fuzzy_inverse(0.5), as the reference's tool draws its heat maps.
+        linear= and scale= (default: the Comparator's own): `distorted` is a linear float image, raw linear intensity
+        0..255 after scale= (255 for data in [0, 1]); values outside [0, 255] are clamped, and `clamped` holds how many
+        of this call's image were."""
+        if self.linear if linear is None else linear:
+            if background is not None:
+                raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
+            other = _linear_image(distorted, layout, self.device, stream, self.scale if scale is None else scale)
+            consumer = stream
+        else:
+            other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background)
+            consumer = stream if is_device_resident(distorted) else None
         _pair_sizes(_PairImage(self.w, self.h), other)
-        consumer = stream if is_device_resident(distorted) else None
         heat = self._heat_destination(heatmap, good, bad, consumer)
         out, dmap = self._destination(distmap, consumer)
         return self._compare(other, out, dmap, heat)
@@ -867,6 +945,47 @@ def butteraugli(reference, distorted, distmap=None, layout=None, device=None, st
         heat = cmp._heat_destination(heatmap, good, bad, consumer)
         out, dmap = cmp._destination(distmap, consumer)
         return cmp._compare(other, out, dmap, heat)
+
+
+def butteraugli_linear(reference, distorted, scale=1.0, distmap=None, heatmap=None, good=None, bad=None, layout=None, device=None,
+                       stream=None, strict=False):
+    """ButteraugliInterface (butteraugli.h:44-79) of two LINEAR float images of one size, from 1 x 1 up -> what
+    butteraugli() returns: float, or with distmap= / heatmap= a tuple with the map and the heat map (see
+    Comparator.compare).  `reference` is butteraugli's first argument; the metric is ASYMMETRIC.
+    The values are raw linear intensity 0..255 AFTER the multiplication by scale=: scale=1 for data in 0..255, scale=255
+    for data in [0, 1].  Nothing is rounded to a byte and nothing is gamma-decoded: images closer than a byte step have a
+    distance, which butteraugli() cannot see.  Values outside [0, 255] after the scale (NaN too) are CLAMPED to it -- the
+    reference is undefined there and does not clamp; strict=True raises ValueError after the call if any element of
+    either image was.
+    The images: GPU tensors / __cuda_array_interface__ objects of float32, float16 or bfloat16 -- HWC or CHW, three
+    channels or one, crops and strided views, as process() takes them; host float32 / float16 arrays are uploaded first.
+    Under 8 pixels in a dimension the images are extended by replicating their border, as the reference does; map and heat
+    map are of the images' own size.
+    ValueError, before anything is computed: sizes that differ, integer dtypes, four channels, images on different
+    devices."""
+    scale = _linear_scale(scale)
+    ref = _linear_image(reference, layout, device, stream, scale)
+    other = _linear_image(distorted, layout, ref.ordinal, stream, scale)
+    if (other.w, other.h) != (ref.w, ref.h):
+        raise ValueError(f"the images differ in size: {ref.w} x {ref.h} against {other.w} x {other.h}")
+    w, h, ordinal = ref.w, ref.h, ref.ordinal
+    out = dmap = heat = None
+    if distmap is not None and distmap is not False:
+        out = _new_map_tensor(w, h, ordinal) if distmap is True else distmap
+        ptr, name, strides, consumer, _ = _map_destination(out, w, h, ordinal)
+        dmap = device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+    if heatmap is not None and heatmap is not False:
+        good, bad = _heat_thresholds(good, bad)
+        hout = _new_heat_tensor(w, h, ordinal) if heatmap is True else heatmap
+        ptr, name, strides, consumer, _ = _heat_destination(hout, w, h, ordinal)
+        heat = (hout, device_output(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)))
+    d, clamped = _pair_library().butteraugli_linear(ref.pixels, other.pixels, w, h, scale, dmap, None if heat is None else heat[1],
+                                                    good if heat else 0.0, bad if heat else 0.0, device=ordinal)
+    if strict and clamped:
+        raise ValueError(f"{clamped} elements of the two images lie outside [0, 255] after scale={scale} (NaN included) and were clamped")
+    if dmap is None and heat is None:
+        return d
+    return (d,) + (() if dmap is None else (out,)) + (() if heat is None else (heat[0],))
 
 
 def fuzzy_class(score):

@@ -395,6 +395,45 @@ int gz_compare_device_pixels_heat(gz_ctx* ctx, const gz_device_pixels* other, fl
 int gz_heatmap_from_map_device(int device, const float* map, int w, int h, int pitch, double good, double bad,
                                const gz_device_output* out);
 
+/* Linear float images: ButteraugliInterface on the device -------------------------------
+ * The entries above compare 8-bit sRGB samples: every element is rounded to the byte an encode would read.  These take
+ * what the reference's documented entry takes -- ButteraugliInterface(rgb0, rgb1, diffmap, diffvalue), butteraugli.h:44-79
+ * and butteraugli.cc:1819-1878: three planes of LINEAR light, raw intensity 0..255, as floats -- from device memory, with
+ * nothing rounded and nothing gamma-decoded.  Two images that differ by less than a byte step have a distance.
+ * The images are gz_device_pixels: dtype GZ_DT_F32, GZ_DT_F16 or GZ_DT_BF16, alpha NULL, background ignored; strides, the
+ * producer's stream and where the memory must live as for gz_set_rgb_device_pixels.  One kernel (k_ingest_linear) writes
+ * the planes.  The value of an element x is  v = (float)x * scale  -- one float32 multiplication; scale = 1 for data in
+ * 0..255, 255 for data in [0, 1] -- and then: NaN and everything below 0 become 0, everything above 255 (+infinity too)
+ * becomes 255.  Inside [0, 255] nothing is altered and distance and map are the reference's bit for bit; outside it the
+ * reference is outside its documented domain (butteraugli.h:52-56) and this clamp is a deliberate difference (DESIGN.md
+ * 3.10).  `clamped` (may be NULL) receives the number of elements the clamp altered.
+ * GZ_E_ARG (before any device call): gz_device_pixels' own, any other dtype, alpha != NULL, a scale that is not finite
+ * and > 0; for map and heat what gz_compare_device_pixels_heat refuses.
+ * gz_create_from_device_linear: gz_create_from_device_pixels for such an original, w, h >= 8, with the target 1 (which
+ *   only scales gz_block_weights).  The context is a LINEAR
+ *   one: it has no 8-bit pixels and no coefficients of its original, so the entries that read them -- gz_encode_rgb,
+ *   gz_quantize, gz_downsample*, gz_apply_candidate_steps, gz_block_zeroing_orders*, gz_compare_blocks,
+ *   gz_compare_block_pixels -- return GZ_E_STATE (gz_last_error says why).  Every pair entry works on it:
+ *   gz_compare_device_pixels of an 8-bit image against a linear original compares that image's table-linearised bytes
+ *   with it.  gz_set_rgb* give the context an 8-bit original again.
+ * gz_set_linear_device: replaces the original of ANY context by a linear image of its size; the context is a linear
+ *   one from then on (from the call's first write: after a failed call too).  GZ_E_STATE while work is in flight.
+ * gz_compare_device_linear: gz_compare_device_pixels_heat for a linear `other` (rgb1), on every context, under the
+ *   same state rules and stream contracts; map, heat and clamped may be NULL.
+ * gz_butteraugli_linear: ButteraugliInterface itself, without a context: ref is rgb0, other rgb1, any 1 <= w, h < 65536
+ *   within a context's limits.  Under 8 pixels in a dimension both images are extended to 8 by replicating their border,
+ *   xborder = (8 - w) / 2 in integers (ButteraugliDiffmap, :1825-1855); map and heat are of the images' own w x h, and
+ *   *distance is the maximum over that window (ButteraugliScoreFromDiffmap of the cropped map).  *clamped counts both
+ *   images.  The caller's current device stays current; the temporaries come from the pools and go back to them. */
+gz_ctx* gz_create_from_device_linear(int device, int w, int h, const gz_device_pixels* img, float scale, int* err);
+int gz_set_linear_device(gz_ctx* ctx, const gz_device_pixels* img, float scale);
+int gz_compare_device_linear(gz_ctx* ctx, const gz_device_pixels* other, float scale, float* distance,
+                             const gz_device_map* map, const gz_device_output* heat, double good, double bad,
+                             uint64_t* clamped);
+int gz_butteraugli_linear(int device, int w, int h, const gz_device_pixels* ref, const gz_device_pixels* other,
+                          float scale, float* distance, const gz_device_map* map, const gz_device_output* heat,
+                          double good, double bad, uint64_t* clamped);
+
 /* Double-precision DCT -----------------------------------------
  * gz_dct_double_blocks: ComputeBlockDCTDouble (inverse == 0) / ComputeBlockIDCTDouble
  * (inverse != 0), dct_double.cc:76-85, on n bare blocks of 64 doubles, in place.
@@ -706,6 +745,9 @@ int gz_probe_emit_map(int device, const float* host_plane, int w, int h, const g
 int gz_probe_emit_heat(int device, const float* host_plane, int w, int h, double good, double bad,
                        const gz_device_output* out);
 int gz_probe_heat_thresholds(double* thr255);
+/* The context's three linear planes as they are now, [3][h][w] floats: after gz_create_from_device_linear /
+ * gz_set_linear_device (and gz_set_rgb*) the original's, after a pair comparison the other image's. */
+int gz_probe_linear_planes(gz_ctx* ctx, float* planes3);
 /* Block kernels on bare 64-element blocks (n blocks each). */
 int gz_probe_idct_blocks(int device, const int16_t* blocks, int n, uint8_t* out);
 int gz_probe_fdct_blocks(int device, int16_t* blocks, int n);
