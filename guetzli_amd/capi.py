@@ -33,6 +33,7 @@ class GzConfig(C.Structure):
 
 GZ_DT_U8, GZ_DT_F32, GZ_DT_F16, GZ_DT_BF16 = 0, 1, 2, 3
 GZ_DT_U16 = 4   # gz_device_pixels only
+GZ_SAMPLES_SRGB8, GZ_SAMPLES_LINEAR = 0, 1   # how gz_opsin_device / gz_mask_device read an image's elements
 
 
 class GzDeviceImage(C.Structure):
@@ -127,6 +128,9 @@ SIGNATURES = {
     "gz_compare_device_linear": (_I, [_P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
     "gz_butteraugli_linear": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
     "gz_probe_linear_planes": (_I, [_P, _P]),
+    "gz_opsin_device": (_I, [_I, _I, _I, _P, _I, C.c_float, _P, _P]),
+    "gz_mask_device": (_I, [_I, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P]),
+    "gz_adaptive_quantization": (_I, [_I, _I, _I, _P, C.c_float, _P, _P]),
     "gz_synchronize": (_I, [_P]),
     "gz_set_stream": (_I, [_P, _P]),
     "gz_encode_rgb": (_I, [_P, _P]),
@@ -383,6 +387,29 @@ class Library:
                                                   None if dmap is None else C.byref(dmap), None if heat is None else C.byref(heat),
                                                   good, bad, C.byref(clamped)))
         return float(dist[0]), clamped.value
+
+    def opsin_device(self, image, w, h, xyb, samples=GZ_SAMPLES_SRGB8, scale=1.0, device=0):
+        """gz_opsin_device: OpsinDynamicsImage of `image` (device_pixels(...), read as `samples` say) into `xyb`
+        (device_output(...) of a float type) -> elements the linear reader's clamp altered."""
+        clamped = C.c_uint64(0)
+        self.check(self.lib.gz_opsin_device(device, w, h, C.byref(image), samples, float(scale), C.byref(xyb), C.byref(clamped)))
+        return clamped.value
+
+    def mask_device(self, image0, image1, w, h, mask=None, mask_dc=None, samples=GZ_SAMPLES_SRGB8, scale=1.0, device=0):
+        """gz_mask_device: Mask of the opsin images of `image0` and `image1` (None: image0 again) into `mask` and / or
+        `mask_dc` (device_output(...) of a float type) -> elements the clamp altered, of both images."""
+        clamped = C.c_uint64(0)
+        self.check(self.lib.gz_mask_device(device, w, h, C.byref(image0), None if image1 is None else C.byref(image1), samples, float(scale),
+                                           None if mask is None else C.byref(mask), None if mask_dc is None else C.byref(mask_dc),
+                                           C.byref(clamped)))
+        return clamped.value
+
+    def adaptive_quantization(self, image, w, h, quant, scale=1.0, device=0):
+        """gz_adaptive_quantization: ButteraugliAdaptiveQuantization of the linear float `image` (device_pixels(...)) into
+        `quant` (device_map(...)) -> elements the clamp altered."""
+        clamped = C.c_uint64(0)
+        self.check(self.lib.gz_adaptive_quantization(device, w, h, C.byref(image), float(scale), C.byref(quant), C.byref(clamped)))
+        return clamped.value
 
     def pack_rgb_device(self, image, w, h, device=0):
         """gz_pack_rgb_device / gz_pack_rgb_device_pixels: the ingest kernel's bytes of `image` (device_image(...) /

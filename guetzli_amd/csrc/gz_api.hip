@@ -40,6 +40,7 @@
 #include "gz_kernels_emit.h"
 #include "gz_kernels_emitmap.h"
 #include "gz_kernels_emitheat.h"
+#include "gz_kernels_emitmask.h"
 #include "gz_host_weights.h"
 #include "order_tables_generated.h"   // host-side csf/bias of order.inc
 
@@ -59,5 +60,6 @@ using namespace gz;
 #include "api/entry_heat.h"     // gz_heatmap_device / gz_heatmap_from_map_device / gz_butteraugli_fuzzy_* (the heat map of a distance map)
 #include "api/entry_pair.h"     // gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device (image pairs, the map on the device)
 #include "api/entry_linear.h"   // gz_create_from_device_linear / gz_set_linear_device / gz_compare_device_linear / gz_butteraugli_linear (linear float images)
+#include "api/entry_mask.h"     // gz_opsin_device / gz_mask_device / gz_adaptive_quantization (the masking images on the device)
 #include "api/entry_search.h"   // gz_block_zeroing_orders*, gz_compare_blocks
 #include "api/entry_probes.h"   // gz_probe_* (diagnostics)

@@ -10,7 +10,7 @@ import numpy as np
 
 import time
 
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GzDevicePixels, device_map, device_output, device_pixels
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_map, device_output, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -1014,4 +1014,116 @@ def heatmap(distmap, good=None, bad=None, out=None, dtype="uint8", layout="HWC",
     _pair_library().heatmap_from_map_device(ptr, w, h, pitch, good, bad,
                                             device_output(optr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)), device=ordinal)
     del keep
+    return out
+
+
+# ---- butteraugli's masking on the GPU: the opsin image, Mask, the quantisation field ----
+def _masking_image(x, linear, image_layout, device, stream, background, scale):
+    """`x` as butteraugli() (linear=False) or butteraugli_linear() (linear=True) takes an image -> _PairImage with
+    device-resident pixels: host arrays are uploaded first."""
+    if linear:
+        if background is not None:
+            raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
+        return _linear_image(x, image_layout, device, stream, scale)
+    if not is_device_resident(x):
+        host = _pair_image(x, image_layout, None, None, background)      # (its checks, and the blend of host alpha)
+        x, image_layout, background = _upload_linear(host.rgb, 0 if device is None else device), "HWC", None
+    return _pair_image(x, image_layout, device, stream, background)
+
+
+def _masking_size(img, least, what):
+    if min(img.w, img.h) < least:
+        raise ValueError(f"a {img.w} x {img.h} image: {what} needs at least {least} x {least}")
+
+
+def _float_destination(out, w, h, dtype, layout, ordinal, stream, name="out="):
+    """out= (None: a fresh tensor of `dtype` in `layout`) -> (the tensor, capi.GzDeviceOutput) for w x h x 3 floats."""
+    if dtype not in MAP_DTYPES and out is None:
+        raise TypeError(f"dtype {dtype}: float32, float16 or bfloat16")
+    if out is None:
+        out = _new_device_tensor(w, h, dtype, layout, ordinal)
+    elif not is_device_resident(out):
+        raise TypeError(f"{name} a device-resident image to fill")
+    ptr, found, strides, consumer, _ = _device_destination(out, w, h, layout, ordinal)
+    if found not in MAP_DTYPES:
+        raise TypeError(f"{name} has dtype {found}: float32, float16 or bfloat16")
+    return out, device_output(ptr, DTYPE_CODES[found], strides, consumer if stream is None else int(stream))
+
+
+def _new_plane_tensor(w, h, dtype, ordinal):
+    """A fresh [h][w] torch tensor of a float `dtype` on GPU `ordinal`, from the calling thread's current stream."""
+    import torch
+    return torch.empty((h, w), dtype=getattr(torch, dtype), device=f"cuda:{ordinal}")
+
+
+def _strict_clamp(strict, clamped, scale, what):
+    if strict and clamped:
+        raise ValueError(f"{clamped} elements of {what} lie outside [0, 255] after scale={scale} (NaN included) and were clamped")
+
+
+def opsin_dynamics(image, linear=False, scale=1.0, out=None, dtype="float32", layout="CHW", device=None, stream=None,
+                   background=None, strict=False, image_layout=None):
+    """butteraugli's OpsinDynamicsImage -- the XYB image Mask is fed with -- of an image, on its GPU -> a torch tensor
+    [3, H, W] ("CHW") or [H, W, 3] ("HWC") of `dtype` (float32: the reference's floats bit for bit; float16 / bfloat16:
+    rounded to nearest even), or out= filled in place and returned (a GPU tensor of a float type in `layout`; a crop view
+    is written without touching what surrounds it).
+    linear=False: `image` as butteraugli() takes one -- host pixels or a GPU tensor of any dtype, alpha over background= --
+    its bytes linearised by the sRGB table.  linear=True: as butteraugli_linear() takes one -- float32 / float16 /
+    bfloat16, raw linear intensity 0..255 after scale=, values outside it CLAMPED (strict=True raises if any was).
+    image_layout= names the layout of `image` where its shape is ambiguous.  stream= overrides the producer's stream of
+    the image and the consumer's of the result.  ValueError, before anything is computed: an image under 8 x 8."""
+    scale = _linear_scale(scale)
+    img = _masking_image(image, linear, image_layout, device, stream, background, scale)
+    _masking_size(img, 8, "the opsin image")
+    out, dest = _float_destination(out, img.w, img.h, dtype, layout, img.ordinal, stream)
+    clamped = _pair_library().opsin_device(img.pixels, img.w, img.h, dest, GZ_SAMPLES_LINEAR if linear else GZ_SAMPLES_SRGB8, scale,
+                                           device=img.ordinal)
+    _strict_clamp(strict, clamped, scale, "the image")
+    return out
+
+
+def mask(reference, distorted=None, dc=False, linear=False, scale=1.0, out=None, out_dc=None, dtype="float32", layout="CHW",
+         device=None, stream=None, background=None, strict=False, image_layout=None):
+    """butteraugli's Mask(OpsinDynamicsImage(reference), OpsinDynamicsImage(distorted)) on the GPU: the visual-masking
+    image, which says where an error of a given size is visible -> a torch tensor [3, H, W] / [H, W, 3] as
+    opsin_dynamics() returns one; dc=True (or out_dc=): the tuple (mask, mask_dc).  distorted=None is the mask of an
+    image with itself, which the encoder's block search works with.  The images, linear=, scale=, the clamp, strict=,
+    out= / out_dc=, dtype=, layout=, stream= and the 8 x 8 lower bound as for opsin_dynamics(); both images have one size
+    and live on one GPU."""
+    scale = _linear_scale(scale)
+    ref = _masking_image(reference, linear, image_layout, device, stream, background, scale)
+    other = None if distorted is None else _masking_image(distorted, linear, image_layout, ref.ordinal, stream, background, scale)
+    _masking_size(ref, 8, "Mask")
+    if other is not None and (other.w, other.h) != (ref.w, ref.h):
+        raise ValueError(f"the images differ in size: {ref.w} x {ref.h} against {other.w} x {other.h}")
+    out, dest = _float_destination(out, ref.w, ref.h, dtype, layout, ref.ordinal, stream)
+    out_dc, dest_dc = _float_destination(out_dc, ref.w, ref.h, dtype, layout, ref.ordinal, stream, "out_dc=") if dc or out_dc is not None else (None, None)
+    clamped = _pair_library().mask_device(ref.pixels, None if other is None else other.pixels, ref.w, ref.h, dest, dest_dc,
+                                          GZ_SAMPLES_LINEAR if linear else GZ_SAMPLES_SRGB8, scale, device=ref.ordinal)
+    _strict_clamp(strict, clamped, scale, "the images")
+    return out if out_dc is None else (out, out_dc)
+
+
+def adaptive_quantization(image, scale=1.0, out=None, dtype="float32", layout=None, device=None, stream=None, strict=False):
+    """ButteraugliAdaptiveQuantization (butteraugli.cc:1880-1901) on the GPU: the per-pixel field a codec multiplies its
+    quantisation steps with -- plane 1 of Mask applied to the LINEAR RGB planes themselves, as the reference computes
+    it -> a float [H, W] torch tensor of `dtype` on the image's GPU, or out= (a 2-D GPU tensor of a float type, crop views
+    included) filled in place and returned.  `image` is a linear float image as butteraugli_linear() takes one (layout=
+    names its layout where the shape is ambiguous), raw linear intensity 0..255 after scale=; values outside it are
+    CLAMPED (strict=True raises if any was).  ValueError, before anything is computed: an image under 16 x 16, where the
+    reference gives up."""
+    scale = _linear_scale(scale)
+    img = _linear_image(image, layout, device, stream, scale)
+    _masking_size(img, 16, "the quantisation field")
+    if out is None:
+        if dtype not in MAP_DTYPES:
+            raise TypeError(f"dtype {dtype}: float32, float16 or bfloat16")
+        out = _new_plane_tensor(img.w, img.h, dtype, img.ordinal)
+    try:
+        ptr, name, strides, consumer, _ = _map_destination(out, img.w, img.h, img.ordinal)
+    except (TypeError, ValueError) as e:
+        raise type(e)(str(e).replace("distmap=", "out=")) from None
+    quant = device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+    clamped = _pair_library().adaptive_quantization(img.pixels, img.w, img.h, quant, scale, device=img.ordinal)
+    _strict_clamp(strict, clamped, scale, "the image")
     return out

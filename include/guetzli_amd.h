@@ -59,7 +59,10 @@ int gz_abi_version(void);                 /* currently 6 (5 without the two expe
                                              gz_reconstruct_device), and gz_device_map and its entries
                                              (gz_compare_device_pixels, gz_compare_rgb, gz_distmap_device), and the heat
                                              map's entries (gz_heatmap_device, gz_compare_device_pixels_heat,
-                                             gz_heatmap_from_map_device, gz_butteraugli_fuzzy_*), by the same rule */
+                                             gz_heatmap_from_map_device, gz_butteraugli_fuzzy_*), the linear float
+                                             entries (gz_create_from_device_linear, gz_set_linear_device,
+                                             gz_compare_device_linear, gz_butteraugli_linear) and the masking entries
+                                             (gz_opsin_device, gz_mask_device, gz_adaptive_quantization), by the same rule */
 /* Device and pinned host memory of destroyed contexts is kept (per device, exact sizes, at
  * most GZ_POOL_MB megabytes of device memory, default 16384) for the next context of the same
  * image size: a batch of same-sized images allocates once.  gz_trim_pool releases everything
@@ -433,6 +436,50 @@ int gz_compare_device_linear(gz_ctx* ctx, const gz_device_pixels* other, float s
 int gz_butteraugli_linear(int device, int w, int h, const gz_device_pixels* ref, const gz_device_pixels* other,
                           float scale, float* distance, const gz_device_map* map, const gz_device_output* heat,
                           double good, double bad, uint64_t* clamped);
+
+/* Masking: Mask, the opsin image and the quantisation field, on the device ---------------
+ * What butteraugli.h offers beside the distance: OpsinDynamicsImage(rgb), the XYB image; Mask(xyb0, xyb1, &mask,
+ * &mask_dc) (butteraugli.cc:1741-1817), the visual-masking images that say where an error of a given size is visible;
+ * and ButteraugliAdaptiveQuantization(xsize, ysize, rgb, quant) (:1880-1901), the per-pixel field a codec multiplies
+ * its step sizes with.  Context-free, as gz_butteraugli_linear: a context lives for the call, the caller's current
+ * device stays current, temporaries come from the pools, all or none (GZ_E_NOMEM leaves nothing behind), and the call
+ * waits for its own work.  (The context is made with the first image as its original, so that image's psycho image is
+ * computed too, though nothing here reads it: DESIGN.md 3.11.)
+ * samples: how the elements of a gz_device_pixels become linear planes --
+ *   GZ_SAMPLES_SRGB8   as gz_set_rgb_device_pixels reads them: the ingest kernel's bytes (every dtype, alpha over a
+ *                      background), linearised by the sRGB table -- what the 8-bit pair entries compare; scale is ignored;
+ *   GZ_SAMPLES_LINEAR  as gz_set_linear_device reads them: (float)x * scale, NaN and < 0 -> 0, > 255 -> 255, counted in
+ *                      *clamped (may be NULL; 0 for 8-bit samples); float32 / float16 / bfloat16 only.  The clamp is the
+ *                      deliberate difference of the linear entries above.
+ * gz_opsin_device: OpsinDynamicsImage of the image's linear planes into xyb, a gz_device_output used as a w x h x 3
+ *   image of FLOATS: GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 (GZ_DT_U8 / GZ_DT_U16: GZ_E_ARG).
+ * gz_mask_device: Mask(OpsinDynamicsImage(lin0), OpsinDynamicsImage(lin1)); img1 == NULL is the mask of img0 with
+ *   itself, what StartBlockComparisons computes for the block search.  mask and mask_dc are float gz_device_outputs as
+ *   xyb, each optional, one at least; *clamped counts both images.
+ * gz_adaptive_quantization: ButteraugliAdaptiveQuantization to the letter -- Mask applied to the LINEAR planes
+ *   themselves (no opsin step: the reference passes rgb as xyb0 and xyb1), plane 1 of `mask` into quant, a gz_device_map.
+ *   The image is read as GZ_SAMPLES_LINEAR.  w < 16 or h < 16: GZ_E_ARG (the reference returns false).  Only the Y
+ *   plane's half of Mask's first stage runs: half the blurs of gz_mask_device.
+ * Sizes: gz_opsin_device and gz_mask_device need w, h >= 8, a context's minimum (GZ_E_ARG below): a limit of this
+ *   library, not of the reference.
+ * Elements of the outputs: gz_device_map's rule -- GZ_DT_F32 the reference's float bit for bit, GZ_DT_F16 / GZ_DT_BF16
+ *   rounded to nearest, ties to even, over the whole float32 domain.  Exactly the image's elements are written: a crop
+ *   view's surroundings stay as they are.
+ * GZ_E_ARG (before any device call): what gz_set_rgb_device_pixels / gz_set_linear_device refuse of an image, what
+ *   gz_device_output / gz_device_map refuse of a destination, an unknown `samples`, an output dtype that is no float,
+ *   both mask outputs NULL.  Memory that is not device memory of `device` -- an ordinary host pointer -- is GZ_E_ARG too,
+ *   not a fault.
+ * Streams: every input's producer_stream is waited for on the device; with an output's consumer_stream, that stream
+ *   waits for the output on the device (the call still waits for its own work: its temporaries go back to the pool). */
+#define GZ_SAMPLES_SRGB8 0
+#define GZ_SAMPLES_LINEAR 1
+int gz_opsin_device(int device, int w, int h, const gz_device_pixels* img, int samples, float scale,
+                    const gz_device_output* xyb, uint64_t* clamped);
+int gz_mask_device(int device, int w, int h, const gz_device_pixels* img0, const gz_device_pixels* img1 /* NULL: img0 */,
+                   int samples, float scale, const gz_device_output* mask, const gz_device_output* mask_dc,
+                   uint64_t* clamped);
+int gz_adaptive_quantization(int device, int w, int h, const gz_device_pixels* img, float scale,
+                             const gz_device_map* quant, uint64_t* clamped);
 
 /* Double-precision DCT -----------------------------------------
  * gz_dct_double_blocks: ComputeBlockDCTDouble (inverse == 0) / ComputeBlockIDCTDouble
