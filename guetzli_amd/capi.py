@@ -76,6 +76,46 @@ def device_output(ptr, dtype, strides, stream=0):
     return GzDeviceOutput(C.sizeof(GzDeviceOutput), int(dtype), int(ptr) or None, sy, sx, sc, int(stream) or None)
 
 
+class GzHuffmanSpec(C.Structure):
+    _fields_ = [("counts", C.c_uint8 * 16), ("values", C.c_uint8 * 256)]
+
+
+class GzScan(C.Structure):
+    """gz_scan of include/guetzli_amd.h: an eligible baseline scan, its tables and quantisers."""
+    _fields_ = [("struct_size", _I), ("w", _I), ("h", _I), ("ncomp", _I), ("chroma_factor", _I), ("data", _P), ("len", C.c_uint64),
+                ("dc", GzHuffmanSpec * 3), ("ac", GzHuffmanSpec * 3), ("quant", (_I * 64) * 3), ("subseq_bytes", _I),
+                ("max_sync_rounds", _I)]
+
+
+class GzScanResult(C.Structure):
+    _fields_ = [("status", _I), ("subsequences", _I), ("sync_rounds", _I), ("reserved", _I), ("end_offset", C.c_uint64)]
+
+
+SCAN_STATUS = {0: "DECODED", 1: "NOT_CONVERGED", 2: "BAD_SYMBOL", 3: "RUN_PAST_BAND", 4: "DC_RANGE", 5: "COEFF_RANGE", 6: "ENDS_EARLY"}
+
+
+def scan_spec(w, h, ncomp, chroma_factor, data, dc, ac, quant, subseq_bytes=0, max_sync_rounds=0):
+    """A GzScan.  data: the bytes from behind the SOS header to the end of the file (kept alive by the returned object);
+    dc / ac: per component (counts[16], values) as a DHT holds them; quant: per component 64 quantisers, natural order."""
+    sc = GzScan()
+    sc.struct_size = C.sizeof(GzScan)
+    sc.w, sc.h, sc.ncomp, sc.chroma_factor = int(w), int(h), int(ncomp), int(chroma_factor)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    sc._keep = buf
+    sc.data = buf.ctypes.data if buf.size else None
+    sc.len = buf.size
+    for c in range(min(3, len(dc))):
+        for spec, (counts, values) in ((sc.dc[c], dc[c]), (sc.ac[c], ac[c])):
+            for i, v in enumerate(counts):
+                spec.counts[i] = int(v)
+            for i, v in enumerate(values):
+                spec.values[i] = int(v)
+        for k in range(64):
+            sc.quant[c][k] = int(quant[c][k])
+    sc.subseq_bytes, sc.max_sync_rounds = int(subseq_bytes), int(max_sync_rounds)
+    return sc
+
+
 class GzDeviceMap(C.Structure):
     """gz_device_map of include/guetzli_amd.h: where a distance map goes, a strided w x h image in device memory."""
     _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_y", C.c_int64), ("stride_x", C.c_int64),
@@ -112,6 +152,8 @@ SIGNATURES = {
     "gz_decode_coeffs_device": (_I, [_I, _P, _I, _I, _I, _P]),
     "gz_decode_coeffs": (_I, [_I, _P, _I, _I, _I, _P]),
     "gz_reconstruct_device": (_I, [_P, _P]),
+    "gz_decode_scan": (_I, [_I, _P, _P, _P]),
+    "gz_decode_scan_device": (_I, [_I, _P, _P, _P]),
     "gz_compare_device_pixels": (_I, [_P, _P, _P, _P]),
     "gz_compare_rgb": (_I, [_P, _P, _P, _P]),
     "gz_distmap_device": (_I, [_P, _P]),
@@ -431,6 +473,33 @@ class Library:
         """gz_decode_coeffs_device: the same written into `output` (device_output(...))."""
         co = np.ascontiguousarray(coeffs, np.int16)
         self.check(self.lib.gz_decode_coeffs_device(device, _ptr(co), w, h, chroma_factor, C.byref(output)))
+
+    @staticmethod
+    def _scan_result(res):
+        return {"status": SCAN_STATUS.get(res.status, res.status), "subsequences": res.subsequences, "sync_rounds": res.sync_rounds,
+                "end_offset": int(res.end_offset)}
+
+    def decode_scan(self, scan, device=0):
+        """gz_decode_scan: a baseline scan (scan_spec(...)) read on the device -> (dequantised coefficients int16
+        [nb + 2 nbc][64] in the frame layout, or None where the status is not "DECODED"; the gz_scan_result as a dict)."""
+        f = scan.chroma_factor if scan.chroma_factor in (1, 2) else 1
+        nb = ((scan.w + 7) // 8) * ((scan.h + 7) // 8)
+        nbc = ((scan.w + 8 * f - 1) // (8 * f)) * ((scan.h + 8 * f - 1) // (8 * f))
+        out = np.full((max(nb + 2 * nbc, 1), 64), 0x5a5a, np.int16)
+        res = GzScanResult()
+        self.check(self.lib.gz_decode_scan(device, C.byref(scan), _ptr(out), C.byref(res)))
+        r = self._scan_result(res)
+        if r["status"] != "DECODED":
+            assert (out == 0x5a5a).all(), "coefficients written without a verdict"
+            return None, r
+        return out, r
+
+    def decode_scan_device(self, scan, output, device=0):
+        """gz_decode_scan_device: the scan's pixels into `output` (device_output(...)) where the status is "DECODED"
+        -> the gz_scan_result as a dict."""
+        res = GzScanResult()
+        self.check(self.lib.gz_decode_scan_device(device, C.byref(scan), C.byref(output), C.byref(res)))
+        return self._scan_result(res)
 
     def probe_emit_map(self, plane, dmap, device=0):
         """gz_probe_emit_map: the float32 [h][w] `plane` (any bit patterns) through the map's emit kernel alone, into

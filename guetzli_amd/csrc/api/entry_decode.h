@@ -70,6 +70,7 @@ struct DecodeScratch {
   gz_ctx t;
   StreamSet ss;
   float* d_lut = nullptr;
+  uint8_t* d_scan = nullptr;   // gz_decode_scan*: the scan decoder's scratch (entry_scandec.h)
   hipEvent_t ev = nullptr;
   bool have_streams = false;
   bool idle = true;   // nothing enqueued that has not been waited for

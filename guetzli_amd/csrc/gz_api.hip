@@ -41,6 +41,7 @@
 #include "gz_kernels_emitmap.h"
 #include "gz_kernels_emitheat.h"
 #include "gz_kernels_emitmask.h"
+#include "gz_kernels_scandec.h"
 #include "gz_host_weights.h"
 #include "order_tables_generated.h"   // host-side csf/bias of order.inc
 
@@ -57,6 +58,7 @@ using namespace gz;
 #include "api/entry_entropy.h"  // gz_jpeg_*
 #include "api/entry_frame.h"    // context-free transforms, 4:2:0 frame
 #include "api/entry_decode.h"   // gz_decode_coeffs* / gz_reconstruct_device (device-resident output)
+#include "api/entry_scandec.h"  // gz_decode_scan / gz_decode_scan_device (a baseline scan read on the device)
 #include "api/entry_heat.h"     // gz_heatmap_device / gz_heatmap_from_map_device / gz_butteraugli_fuzzy_* (the heat map of a distance map)
 #include "api/entry_pair.h"     // gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device (image pairs, the map on the device)
 #include "api/entry_linear.h"   // gz_create_from_device_linear / gz_set_linear_device / gz_compare_device_linear / gz_butteraugli_linear (linear float images)

@@ -77,6 +77,12 @@ class HostLibrary:
         self.lib.gzh_decode_jpeg_device_sized.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_int]
         self.lib.gzh_decode_jpeg.restype = C.c_long
         self.lib.gzh_decode_jpeg.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long]
+        for name, args in (("gzh_decode_jpeg_device_entropy", [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+                           ("gzh_decode_jpeg_coeffs", [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                                       C.c_void_p, C.c_long, C.c_void_p])):
+            if hasattr(self.lib, name):   # (a host library built before the device's scan decoder has neither)
+                getattr(self.lib, name).restype = C.c_long
+                getattr(self.lib, name).argtypes = args
         self.lib.gzh_butteraugli_score_for_quality.restype = C.c_double
         self.lib.gzh_butteraugli_score_for_quality.argtypes = [C.c_double]
 
@@ -196,6 +202,55 @@ class HostLibrary:
         if n != 0:
             raise RuntimeError("guetzli_amd.DecodeJpegToRGB failed (see stderr)" if n == -1 else
                                "guetzli_amd.DecodeJpegToRGB raised a C++ exception (see stderr)")
+
+    @staticmethod
+    def _entropy_mode(entropy, subseq_bytes=0, max_sync_rounds=0):
+        if entropy not in ("host", "device"):
+            raise ValueError(f"entropy={entropy!r}: 'host' or 'device'")
+        return (C.c_int * 3)(int(entropy == "device"), int(subseq_bytes), int(max_sync_rounds))
+
+    @staticmethod
+    def _entropy_info(info):
+        from .capi import SCAN_STATUS
+        return {"path": "device" if info[0] else "host", "status": None if info[1] < 0 else SCAN_STATUS.get(info[1], info[1]),
+                "subsequences": int(info[2]), "sync_rounds": int(info[3]), "end_offset": int(info[4]), "rc": int(info[5])}
+
+    def decode_jpeg_device_entropy(self, data, ptr, dtype, strides, stream=0, device=0, size=None, entropy="device",
+                                   subseq_bytes=0, max_sync_rounds=0):
+        """decode_jpeg_device with the entropy-coded scan read by `entropy`: "host", or "device" -- the device's Huffman
+        decoder where the scan is eligible and it reaches a verdict, the host's reader otherwise.  Returns which path
+        produced the coefficients and the gz_scan_result of the attempt, as a dict."""
+        buf = np.frombuffer(data, np.uint8)
+        image = device_output(ptr, DTYPE_CODES.get(dtype, dtype), strides, stream)
+        w, h = size or (0, 0)
+        info = (C.c_int64 * 6)()
+        n = self.lib.gzh_decode_jpeg_device_entropy(buf.ctypes.data if len(data) else None, len(data), device, C.addressof(image), w, h,
+                                                    self._entropy_mode(entropy, subseq_bytes, max_sync_rounds), info)
+        if n != 0:
+            raise RuntimeError("guetzli_amd.DecodeJpegToRGB failed (see stderr)" if n == -1 else
+                               "guetzli_amd.DecodeJpegToRGB raised a C++ exception (see stderr)")
+        return self._entropy_info(info)
+
+    def decode_jpeg_coeffs(self, data, entropy="host", device=0, subseq_bytes=0, max_sync_rounds=0):
+        """The dequantised coefficients DecodeJpegToRGB hands to the device, by either entropy path: (int16 [blocks][64] in
+        the frame layout, (w, h, chroma_factor), the entropy info of decode_jpeg_device_entropy, the reader's metadata
+        as bytes), or None where the stream is refused."""
+        buf = np.frombuffer(data, np.uint8)
+        whf, info, mlen = (C.c_int * 3)(), (C.c_int64 * 6)(), C.c_long(0)
+        mode = self._entropy_mode(entropy, subseq_bytes, max_sync_rounds)
+        w, h = _jpeg_dimensions(data)
+        cap = 0 if w * h > (1 << 28) else 3 * ((w + 7) // 8) * ((h + 7) // 8) * 64
+        meta = np.zeros(len(data) + 64, np.uint8)
+        for _ in range(2):
+            out = np.zeros(max(cap, 1), np.int16)
+            n = self.lib.gzh_decode_jpeg_coeffs(buf.ctypes.data if len(data) else None, len(data), device, mode, whf, out.ctypes.data,
+                                                cap, info, meta.ctypes.data, meta.size, C.byref(mlen))
+            if n < 0:
+                return None
+            if n <= cap:
+                break
+            cap = n
+        return out[:n].reshape(-1, 64), (whf[0], whf[1], whf[2]), self._entropy_info(info), meta[:mlen.value].tobytes()
 
     def read_png(self, data):
         """ReadPNG of the reference's front end (guetzli.cc:47-152): PNG bytes -> uint8
@@ -456,7 +511,7 @@ def _new_device_tensor(w, h, dtype, layout, ordinal):
     return torch.empty((h, w, 3) if layout == "HWC" else (3, h, w), dtype=getattr(torch, name), device=f"cuda:{ordinal}")
 
 
-def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None):
+def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None, entropy="host"):
     """guetzli::DecodeJpegToRGB with the pixels left on the GPU: the image a JPEG decodes to under the encoder's own
     pixel model -- the integer IDCT and colour conversion every butteraugli distance of the search was computed on.
     One-component (grey) and YCbCr 4:4:4 / 4:2:0 streams are decoded, everything else is refused.
@@ -467,12 +522,37 @@ def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None
     out=: a GPU tensor, or an object with __cuda_array_interface__, of the JPEG's size in `layout` is filled in place
     and returned; dtype and strides are its own, so a crop inside a larger tensor is written without touching what
     surrounds it.  stream= overrides the consumer stream (a hipStream_t handle; 0: none -- the call waits).
-    device="host": numpy uint8 [h][w][3] instead, computed on GPU 0."""
+    device="host": numpy uint8 [h][w][3] instead, computed on GPU 0.
+    entropy="device": the entropy-coded scan is read on the GPU too (a self-synchronising parallel Huffman decoder) where
+    it is a baseline scan of all components without restart intervals, one component or 4:4:4 / 4:2:0 -- what this
+    library, Pillow and libjpeg write by default; every other stream, and every scan that decoder reaches no verdict
+    on, is read by the host as with entropy="host", silently: the same streams are accepted and the same pixels
+    returned.  decode_info() tells which path ran."""
+    return _decode(jpeg, out, dtype, layout, device, stream, entropy)[0]
+
+
+def decode_info(jpeg, entropy="device", out=None, dtype="uint8", layout="HWC", device=None, stream=None, subseq_bytes=0,
+                max_sync_rounds=0):
+    """decode() of `jpeg` that says what it did: {"path": "device" | "host" (whose reader produced the coefficients),
+    "status": the device decoder's verdict (gz_scan_result: "DECODED", "NOT_CONVERGED", ...; None: it was not asked),
+    "subsequences", "sync_rounds", "end_offset", "rc": what the device call returned (0; a GZ_E_* code: it failed, and the host
+    read the scan instead), "decoded": the pixels}.  subseq_bytes / max_sync_rounds: gz_scan's."""
+    pixels, info = _decode(jpeg, out, dtype, layout, device, stream, entropy, subseq_bytes, max_sync_rounds)
+    info["decoded"] = pixels
+    return info
+
+
+def _decode(jpeg, out, dtype, layout, device, stream, entropy, subseq_bytes=0, max_sync_rounds=0):
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy={entropy!r}: 'host' or 'device'")
     lib = load_host()
+    none = {"path": "host", "status": None, "subsequences": 0, "sync_rounds": 0, "end_offset": 0, "rc": 0}
     if isinstance(device, str):
         if device != "host" or out is not None:
             raise ValueError("device='host' (without out=) or a GPU ordinal")
-        return lib.decode_jpeg(jpeg, 0)
+        if entropy == "device":
+            raise ValueError("entropy='device' leaves the pixels on the GPU: device='host' goes with entropy='host'")
+        return lib.decode_jpeg(jpeg, 0), none
     w, h = _jpeg_dimensions(jpeg)   # (the frame header alone: the stream is read once, by the decode, which checks the size)
     if w <= 0 or h <= 0:
         raise ValueError("not a JPEG: no frame header")
@@ -482,8 +562,12 @@ def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None
             device = torch.cuda.current_device()
         out = _new_device_tensor(w, h, dtype, layout, device)
     ptr, name, strides, consumer, ordinal = _device_destination(out, w, h, layout, device)
-    lib.decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer if stream is None else int(stream), device=ordinal, size=(w, h))
-    return out
+    consumer = consumer if stream is None else int(stream)
+    if entropy == "host":   # (the call every decode made before there was a choice)
+        lib.decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h))
+        return out, none
+    return out, lib.decode_jpeg_device_entropy(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h), entropy=entropy,
+                                               subseq_bytes=subseq_bytes, max_sync_rounds=max_sync_rounds)
 
 
 def _with_decoded(job, decoded, w, h, ordinal):

@@ -202,6 +202,83 @@ long gzh_decode_jpeg(const uint8_t* data, long len, int device, uint8_t* host_rg
   GZH_GUARD_END
 }
 
+// What a decode says of its entropy path: info[0] 1 = the device's coefficients were used, 0 = the host's; info[1] the
+// gz_scan_result status of the attempt, -1 = none; info[2] subsequences; info[3] inter-workgroup rounds; info[4] end_offset;
+// info[5] what gz_decode_scan* returned (0, or the GZ_E_* code of a call that failed and fell back).
+static void CopyDecodeInfo(const guetzli_amd::DecodeInfo& di, int64_t* info) {
+  if (!info) return;
+  info[0] = di.device_path ? 1 : 0;
+  info[1] = di.status;
+  info[2] = di.subsequences;
+  info[3] = di.sync_rounds;
+  info[4] = (int64_t)di.end_offset;
+  info[5] = di.rc;
+}
+static guetzli_amd::EntropyOptions EntropyFrom(const int* mode) {   // mode: device (0 / 1), subseq_bytes, max_sync_rounds
+  guetzli_amd::EntropyOptions e;
+  if (mode) {
+    e.device = mode[0] != 0;
+    e.subseq_bytes = mode[1];
+    e.max_sync_rounds = mode[2];
+  }
+  return e;
+}
+
+// gzh_decode_jpeg_device_sized with the entropy path chosen by mode[3] (EntropyFrom; NULL: the host) and reported in
+// info[6] (CopyDecodeInfo; may be NULL).
+long gzh_decode_jpeg_device_entropy(const uint8_t* data, long len, int device, const gz_device_output* out, int w, int h,
+                                    const int* mode, int64_t* info) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0 || w < 0 || h < 0) return -1;
+  if (!out || out->struct_size != (int)sizeof(gz_device_output)) {
+    fprintf(stderr, "guetzli_amd: gzh_decode_jpeg_device_entropy: not a gz_device_output of this library\n");
+    return -1;
+  }
+  guetzli_amd::DeviceOutput o;
+  o.dtype = out->dtype;
+  o.data = out->data;
+  o.stride_y = out->stride_y; o.stride_x = out->stride_x; o.stride_c = out->stride_c;
+  o.consumer_stream = out->consumer_stream;
+  guetzli_amd::DecodeInfo di;
+  const bool ok = guetzli_amd::DecodeJpegToRGB(std::string((const char*)data, (size_t)len), device, o, nullptr, nullptr, w, h,
+                                               EntropyFrom(mode), &di);
+  CopyDecodeInfo(di, info);
+  return ok ? 0 : -1;
+  GZH_GUARD_END
+}
+
+// The stream's dequantised coefficients in the frame layout (what DecodeJpegToRGB hands to the device) by either entropy
+// path: returns their count (copied if it fits `cap` elements), -1 if the stream is refused; whf[3] = width, height,
+// chroma factor; info as above.  meta (optional, meta_cap bytes): what the reader kept beside the coefficients -- every
+// APPn, COM and the tail, each behind its length as 8 decimal digits -- and *meta_len its size.  Test hook.
+long gzh_decode_jpeg_coeffs(const uint8_t* data, long len, int device, const int* mode, int* whf, int16_t* out, long cap,
+                            int64_t* info, uint8_t* meta, long meta_cap, long* meta_len) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0 || !whf) return -1;
+  std::vector<int16_t> coeffs;
+  guetzli_amd::DecodeInfo di;
+  guetzli_amd::JpegInput jpg;
+  const bool ok = guetzli_amd::DecodeJpegCoeffs(std::string((const char*)data, (size_t)len), device, EntropyFrom(mode), &whf[0],
+                                                &whf[1], &whf[2], &coeffs, &di, &jpg);
+  CopyDecodeInfo(di, info);
+  if (!ok) return -1;
+  if (out && (long)coeffs.size() <= cap) memcpy(out, coeffs.data(), coeffs.size() * sizeof(int16_t));
+  std::string m;
+  auto add = [&m](char tag, const std::string& s) {
+    char head[16];
+    snprintf(head, sizeof(head), "%c%08zu", tag, s.size());
+    m += head;
+    m += s;
+  };
+  for (const std::string& s : jpg.app_data) add('A', s);
+  for (const std::string& s : jpg.com_data) add('C', s);
+  add('T', jpg.tail_data);
+  if (meta_len) *meta_len = (long)m.size();
+  if (meta && (long)m.size() <= meta_cap) memcpy(meta, m.data(), m.size());
+  return (long)coeffs.size();
+  GZH_GUARD_END
+}
+
 double gzh_butteraugli_score_for_quality(double q) {
   return guetzli_amd::ButteraugliScoreForQuality(q);
 }

@@ -51,6 +51,7 @@ struct HuffTable {
   int mincode[17];
   uint8_t values[256];
   int num_values = 0;
+  uint8_t counts16[16];  // the DHT's counts, for a ScanRequest
   uint16_t fast[512];  // ((length) << 8 | symbol) + 1 for codes of <= 9 bits, 0 otherwise
 
   // A slot no DHT has filled decodes nothing: a sequential scan whose header names a band without DC passes the
@@ -59,6 +60,7 @@ struct HuffTable {
   HuffTable() {
     memset(fast, 0, sizeof(fast));
     memset(values, 0, sizeof(values));
+    memset(counts16, 0, sizeof(counts16));
     for (int l = 0; l < 18; ++l) maxcode[l] = -1;
     for (int l = 0; l < 17; ++l) { valptr[l] = 0; mincode[l] = 0; }
     maxcode[17] = 0x7fffffff;
@@ -67,6 +69,7 @@ struct HuffTable {
   void Build(const int* counts /*[1..16]*/, const uint8_t* vals, int n) {
     num_values = n;
     memcpy(values, vals, (size_t)n);
+    for (int l = 1; l <= 16; ++l) counts16[l - 1] = (uint8_t)counts[l];
     memset(fast, 0, sizeof(fast));
     int code = 0, k = 0;
     for (int len = 1; len <= 16; ++len) {
@@ -180,6 +183,7 @@ struct Decoder {
   size_t len;
   JpegInput* jpg;
   Fail fail;
+  const ScanDecoder* scan_decoder = nullptr;
   HuffTable dc_tables[4], ac_tables[4];
   bool found_sof = false;
   int tables_defined = 0;               // Huffman tables in all DHT segments (:1057-1069)
@@ -228,7 +232,7 @@ struct Decoder {
       c.height_in_blocks = jpg->mcu_rows * c.v_samp;
       const uint64_t nblocks = (uint64_t)c.width_in_blocks * c.height_in_blocks;
       if (nblocks > (1ull << 21)) return fail("image too large");
-      c.coeffs.assign((size_t)nblocks * 64, 0);
+      if (!scan_decoder) c.coeffs.assign((size_t)nblocks * 64, 0);   // (else: when a block loop runs, or at the end)
     }
     if (*pos + seg != p) return fail("bad SOF length");
     *pos = p;
@@ -433,6 +437,57 @@ struct Decoder {
     return true;
   }
 
+  // With a scan decoder the components' coefficients are allocated when the host first needs them.
+  void AllocateCoeffs() {
+    for (JpegComponentIn& c : jpg->components)
+      if (c.coeffs.empty()) c.coeffs.assign((size_t)c.width_in_blocks * c.height_in_blocks * 64, 0);
+  }
+
+  // The scan at *pos to the scan decoder, if it is eligible (jpeg_reader.h) and the decoder takes it.
+  bool OfferScan(const ScanComp* sc, int ns, size_t* pos) {
+    if (!scan_decoder || jpg->scan_decoded_elsewhere || jpg->progressive || jpg->restart_interval > 0) return false;
+    const int nc = (int)jpg->components.size();
+    if (ns != nc || (nc != 1 && nc != 3)) return false;
+    for (int i = 0; i < ns; ++i)
+      if (sc[i].comp != i) return false;
+    if (nc == 1 ? (jpg->components[0].h_samp != 1 || jpg->components[0].v_samp != 1) : !(jpg->Is444() || jpg->Is420())) return false;
+    for (const JpegComponentIn& c : jpg->components)
+      if (!c.coeffs.empty()) return false;   // (an earlier scan went through the block loop)
+    if (*pos > len) return false;
+    const size_t rest = len - *pos;
+    if (rest < 3 || rest >= ((size_t)1 << 28)) return false;
+    // a stuffed pair across BitReader's first stop: the one place where Finish does not undo NextByte
+    if (data[len - 3] == 0xff && data[len - 2] == 0) return false;
+    ScanRequest rq;
+    rq.width = jpg->width; rq.height = jpg->height; rq.ncomp = nc;
+    rq.chroma_factor = nc == 3 && jpg->Is420() ? 2 : 1;
+    rq.data = data + *pos;
+    rq.len = rest;
+    rq.so_far = jpg;
+    memset(rq.dc, 0, sizeof(rq.dc));
+    memset(rq.ac, 0, sizeof(rq.ac));
+    memset(rq.quant, 0, sizeof(rq.quant));
+    for (int i = 0; i < nc; ++i) {
+      const HuffTable& d = dc_tables[sc[i].dc_tbl];
+      const HuffTable& a = ac_tables[sc[i].ac_tbl];
+      memcpy(rq.dc[i].counts, d.counts16, 16);
+      memcpy(rq.dc[i].values, d.values, 256);
+      memcpy(rq.ac[i].counts, a.counts16, 16);
+      memcpy(rq.ac[i].values, a.values, 256);
+      // FixupIndexes' rule, now: the first table with the component's Tq (a later one with that id never comes first)
+      int found = -1;
+      for (size_t j = 0; j < jpg->quant.size() && found < 0; ++j)
+        if (jpg->quant[j].index == jpg->components[i].quant_idx) found = (int)j;
+      if (found < 0) return false;
+      memcpy(rq.quant[i], jpg->quant[found].values, sizeof(rq.quant[i]));
+    }
+    size_t end = 0;
+    if (!(*scan_decoder)(rq, &end) || end > rest) return false;
+    *pos += end;
+    jpg->scan_decoded_elsewhere = true;
+    return true;
+  }
+
   // SOS + its entropy-coded segment (ProcessSOS :168-259, ProcessScan :755-888).
   bool ProcessScan(size_t* pos) {
     if (*pos + 3 > len) return fail("truncated SOS");
@@ -481,6 +536,11 @@ struct Decoder {
         had |= planes;
       }
     if (al > 10) return fail("unsupported successive approximation position");
+    if (OfferScan(sc, ns, pos)) return true;
+    if (scan_decoder) {
+      if (jpg->scan_decoded_elsewhere) return fail("overlapping scans");   // (not reached: the bookkeeping above refuses it)
+      AllocateCoeffs();
+    }
 
     // geometry of the scan: interleaved = MCUs; single component = its own block grid
     const bool interleaved = ns > 1;
@@ -573,6 +633,7 @@ struct Decoder {
       if (!ok) return false;
     } while (marker != 0xd9);
     if (!found_sof) return fail("no SOF marker");
+    if (scan_decoder && !jpg->scan_decoded_elsewhere) AllocateCoeffs();
     if (pos < len) jpg->tail_data.assign((const char*)data + pos, len - pos);
     // FixupIndexes (:890-909): Tq -> position of the first table with that id
     for (size_t i = 0; i < jpg->components.size(); ++i) {
@@ -591,9 +652,10 @@ struct Decoder {
 
 }  // namespace
 
-bool ReadJpeg(const uint8_t* data, size_t len, JpegInput* jpg, std::string* error) {
+bool ReadJpeg(const uint8_t* data, size_t len, JpegInput* jpg, std::string* error, const ScanDecoder* scan_decoder) {
   *jpg = JpegInput();
   Decoder d;
+  d.scan_decoder = scan_decoder;
   d.data = data;
   d.len = len;
   d.jpg = jpg;

@@ -19,6 +19,9 @@ extern "C" int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img
 // ... and the device-output entries: a stand-in without them refuses DecodeJpegToRGB.
 extern "C" int gz_decode_coeffs_device(int device, const int16_t* coeffs, int w, int h, int chroma_factor, const gz_device_output* out) __attribute__((weak));
 extern "C" int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h, int chroma_factor, uint8_t* host_rgb_out) __attribute__((weak));
+// ... and the device's scan decoder: without it every scan is read by the host.
+extern "C" int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_scan_result* result) __attribute__((weak));
+extern "C" int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -475,12 +478,72 @@ namespace {
 // The stream's dequantised coefficients in the frame layout of include/guetzli_amd.h, as RunJpeg lays out its original
 // (RemoveOriginalQuantization; of a 4:2:0 input the blocks inside the image's grid, CopyFromJpegComponent).  A
 // one-component file gets two zero chroma components, as CopyFromJpegData leaves them.
-bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs) {
-  JpegInput jpg;
-  if (!ReadJpeg((const uint8_t*)data.data(), data.size(), &jpg)) {
+// What a decode with EntropyOptions::device gives the reader's hook: where the coefficients (or, with `out`, the pixels)
+// of a scan the device decodes go.
+struct DeviceScan {
+  int device = 0;
+  EntropyOptions opt;
+  const gz_device_output* out = nullptr;   // pixels straight into the caller's image ...
+  std::vector<int16_t>* coeffs = nullptr;  // ... or coefficients to the host
+  int expect_w = 0, expect_h = 0;
+  DecodeInfo info;
+  bool operator()(const ScanRequest& rq, size_t* end_offset) {
+    if (out ? !gz_decode_scan_device : !gz_decode_scan) return false;
+    if ((expect_w > 0 || expect_h > 0) && (rq.width != expect_w || rq.height != expect_h)) return false;   // (refused below)
+    if (rq.ncomp == 3 && !HasYCbCrColorSpace(*rq.so_far)) return false;
+    static thread_local gz_scan sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.struct_size = (int)sizeof(sc);
+    sc.w = rq.width; sc.h = rq.height; sc.ncomp = rq.ncomp; sc.chroma_factor = rq.chroma_factor;
+    sc.data = rq.data;
+    sc.len = rq.len;
+    for (int c = 0; c < rq.ncomp; ++c) {
+      memcpy(sc.dc[c].counts, rq.dc[c].counts, 16);
+      memcpy(sc.dc[c].values, rq.dc[c].values, 256);
+      memcpy(sc.ac[c].counts, rq.ac[c].counts, 16);
+      memcpy(sc.ac[c].values, rq.ac[c].values, 256);
+      memcpy(sc.quant[c], rq.quant[c], sizeof(sc.quant[c]));
+    }
+    sc.subseq_bytes = opt.subseq_bytes;
+    sc.max_sync_rounds = opt.max_sync_rounds;
+    gz_scan_result res;
+    memset(&res, 0, sizeof(res));
+    int rc;
+    if (out) {
+      rc = gz_decode_scan_device(device, &sc, out, &res);
+    } else {
+      const int f = rq.chroma_factor;
+      const size_t nb = (size_t)((rq.width + 7) / 8) * ((rq.height + 7) / 8);
+      const size_t nbc = (size_t)((rq.width + 8 * f - 1) / (8 * f)) * ((rq.height + 8 * f - 1) / (8 * f));
+      coeffs->resize((nb + 2 * nbc) * 64);
+      rc = gz_decode_scan(device, &sc, coeffs->data(), &res);
+    }
+    info.rc = rc;
+    if (rc != GZ_OK) {   // the host reads the scan: the call's failure costs the attempt, not the decode -- and is on record
+      fprintf(stderr, "guetzli_amd: the device's scan decoder failed (%s): the host reads the scan\n", gz_strerror(rc));
+      return false;
+    }
+    info.status = res.status;
+    info.subsequences = res.subsequences;
+    info.sync_rounds = res.sync_rounds;
+    info.end_offset = res.end_offset;
+    if (res.status != GZ_SCAN_DECODED) return false;
+    *end_offset = (size_t)res.end_offset;
+    return true;
+  }
+};
+
+bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs,
+                   DeviceScan* scan = nullptr, JpegInput* meta = nullptr) {
+  JpegInput local;
+  JpegInput& jpg = meta ? *meta : local;
+  ScanDecoder hook;
+  if (scan) hook = [scan](const ScanRequest& rq, size_t* end) { return (*scan)(rq, end); };
+  if (!ReadJpeg((const uint8_t*)data.data(), data.size(), &jpg, nullptr, scan ? &hook : nullptr)) {
     fprintf(stderr, "Can't read jpg data from input file\n");
     return false;
   }
+  if (scan) scan->info.device_path = jpg.scan_decoded_elsewhere;
   const size_t ncomp = jpg.components.size();
   if (!(ncomp == 1 || (ncomp == 3 && HasYCbCrColorSpace(jpg) && (jpg.Is420() || jpg.Is444())))) {   // DecodeJpegToRGB is empty
     fprintf(stderr, "Unsupported input JPEG file (e.g. unsupported downsampling mode).\n");
@@ -490,6 +553,10 @@ bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_
   const int factor = ncomp == 3 && jpg.Is420() ? 2 : 1;
   const int bw = (w + 7) / 8, bh = (h + 7) / 8, nb = bw * bh;
   const int cbw = (w + 8 * factor - 1) / (8 * factor), cbh = (h + 8 * factor - 1) / (8 * factor), nbc = cbw * cbh;
+  if (jpg.scan_decoded_elsewhere) {   // the device has dequantised, cropped and range-checked them (or made pixels of them)
+    *w_out = w; *h_out = h; *factor_out = factor;
+    return true;
+  }
   coeffs->resize(((size_t)nb + 2 * (size_t)nbc) * 64);
   if (ncomp == 1) std::fill(coeffs->begin() + (size_t)nb * 64, coeffs->end(), (int16_t)0);   // (every other block is written below)
   for (size_t c = 0; c < ncomp; ++c) {
@@ -550,16 +617,13 @@ bool JpegSize(const std::string& jpeg, int* w, int* h) {
 
 bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w_out, int* h_out, int expect_w,
                      int expect_h) {
+  return DecodeJpegToRGB(jpeg, device, out, w_out, h_out, expect_w, expect_h, EntropyOptions(), nullptr);
+}
+
+bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w_out, int* h_out, int expect_w,
+                     int expect_h, const EntropyOptions& entropy, DecodeInfo* info) {
   int w = 0, h = 0, factor = 1;
   std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
-  if (!DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs)) return false;
-  if (w_out) *w_out = w;
-  if (h_out) *h_out = h;
-  if ((expect_w > 0 || expect_h > 0) && (w != expect_w || h != expect_h)) {
-    fprintf(stderr, "guetzli_amd: the JPEG holds %d x %d pixels, the destination was made for %d x %d\n", w, h, expect_w, expect_h);
-    return false;
-  }
-  if (!gz_decode_coeffs_device) return DecodeFailed("device-resident output (not in this device library)", GZ_E_STATE);
   gz_device_output o;
   memset(&o, 0, sizeof(o));
   o.struct_size = (int)sizeof(o);
@@ -567,14 +631,46 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
   o.data = out.data;
   o.stride_y = out.stride_y; o.stride_x = out.stride_x; o.stride_c = out.stride_c;
   o.consumer_stream = out.consumer_stream;
+  DeviceScan scan;
+  scan.device = device;
+  scan.opt = entropy;
+  scan.out = &o;
+  scan.expect_w = expect_w; scan.expect_h = expect_h;
+  const bool ok = DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs, entropy.device ? &scan : nullptr);
+  if (info) *info = scan.info;
+  if (!ok) return false;
+  if (w_out) *w_out = w;
+  if (h_out) *h_out = h;
+  if (scan.info.device_path) return true;   // (the pixels are in `out`; the size was checked in front of the device call)
+  if ((expect_w > 0 || expect_h > 0) && (w != expect_w || h != expect_h)) {
+    fprintf(stderr, "guetzli_amd: the JPEG holds %d x %d pixels, the destination was made for %d x %d\n", w, h, expect_w, expect_h);
+    return false;
+  }
+  if (!gz_decode_coeffs_device) return DecodeFailed("device-resident output (not in this device library)", GZ_E_STATE);
   const int rc = gz_decode_coeffs_device(device, coeffs.data(), w, h, factor, &o);
   return rc == GZ_OK ? true : DecodeFailed("gz_decode_coeffs_device", rc);
 }
 
+bool DecodeJpegCoeffs(const std::string& jpeg, int device, const EntropyOptions& entropy, int* w, int* h, int* factor,
+                      std::vector<int16_t>* coeffs, DecodeInfo* info, JpegInput* meta) {
+  DeviceScan scan;
+  scan.device = device;
+  scan.opt = entropy;
+  scan.coeffs = coeffs;
+  const bool ok = DecodedCoeffs(jpeg, w, h, factor, coeffs, entropy.device ? &scan : nullptr, meta);
+  if (info) *info = scan.info;
+  return ok;
+}
+
 bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w_out, int* h_out) {
+  return DecodeJpegToRGB(jpeg, device, rgb, w_out, h_out, EntropyOptions(), nullptr);
+}
+
+bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w_out, int* h_out,
+                     const EntropyOptions& entropy, DecodeInfo* info) {
   int w = 0, h = 0, factor = 1;
   std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
-  if (!DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs)) return false;
+  if (!DecodeJpegCoeffs(jpeg, device, entropy, &w, &h, &factor, &coeffs, info)) return false;
   if (w_out) *w_out = w;
   if (h_out) *h_out = h;
   if (!gz_decode_coeffs) return DecodeFailed("gz_decode_coeffs (not in this device library)", GZ_E_STATE);

@@ -105,6 +105,34 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
                      int expect_h = 0);
 // The same into packed host bytes, rgb[(y * w + x) * 3 + c].
 bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w, int* h);
+
+// Who reads the entropy-coded scan.  device: an eligible scan (jpeg_reader.h: ScanRequest) is read by the device's
+// self-synchronising Huffman decoder (gz_decode_scan*), and only the stream's bytes go up instead of its coefficients;
+// every other scan, and every scan the device hands back (a status other than GZ_SCAN_DECODED, any error of the call), is
+// read by the host as if nothing had been tried.  Which streams are accepted, and what they decode to, does not
+// depend on it.  One difference: with a DeviceOutput, a stream that the reader refuses BEHIND a scan the device decoded
+// (garbage where a marker should be, an Adobe marker after the scan that makes the colour space RGB) is refused as always,
+// but the destination may have been written by then.
+struct EntropyOptions {
+  bool device = false;
+  int subseq_bytes = 0, max_sync_rounds = 0;   // gz_scan's; 0 = the library's defaults
+};
+struct DecodeInfo {
+  bool device_path = false;    // the device's coefficients were used
+  int status = -1;             // gz_scan_result's of the attempt; -1: no verdict (host asked for, no eligible scan, or rc != 0)
+  int rc = 0;                  // what gz_decode_scan* returned (GZ_OK, GZ_E_HIP, GZ_E_NOMEM ...): a failed call falls back too
+  int subsequences = 0, sync_rounds = 0;
+  uint64_t end_offset = 0;
+};
+bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w, int* h, int expect_w, int expect_h,
+                     const EntropyOptions& entropy, DecodeInfo* info = nullptr);
+bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w, int* h, const EntropyOptions& entropy,
+                     DecodeInfo* info = nullptr);
+// The stream's dequantised coefficients in the frame layout of include/guetzli_amd.h (what DecodeJpegToRGB hands to the
+// device), *factor the chroma subsampling factor; meta (optional) receives what the reader kept beside them.
+struct JpegInput;
+bool DecodeJpegCoeffs(const std::string& jpeg, int device, const EntropyOptions& entropy, int* w, int* h, int* factor,
+                      std::vector<int16_t>* coeffs, DecodeInfo* info = nullptr, JpegInput* meta = nullptr);
 // The size the frame header declares (of a stream ReadJpeg accepts).
 bool JpegSize(const std::string& jpeg, int* w, int* h);
 

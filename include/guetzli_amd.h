@@ -327,6 +327,64 @@ int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h, int chroma
 /* The candidate of a context, as gz_reconstruct's srgb, into out (the context's w and h). */
 int gz_reconstruct_device(gz_ctx* ctx, const gz_device_output* out);
 
+/* A baseline scan read on the device ----------------------------------------------------
+ * The entropy-coded segment of a sequential 8-bit JPEG whose ONE scan names all components in frame order -- one
+ * component, or three sampled 4:4:4 or 4:2:0 -- with no restart interval, decoded by a self-synchronising parallel
+ * Huffman decoder (gz_kernels_scandec.h) into DEQUANTISED coefficients in the frame layout of this
+ * header: what the host reader's block loop, its range checks and DecodedCoeffs' dequantisation produce, or a status
+ * that says the host must read the scan itself.
+ *   data / len: from the first byte behind the SOS header to the END OF THE FILE (the reader's view of where the
+ *     entropy-coded data end depends on it: the first 0xff that no 0x00 follows, or two bytes before the end);
+ *     3 <= len < 2^28.
+ *   dc[c] / ac[c]: component c's tables as a DHT holds them, 16 counts and the values; quant[c]: its quantisers in
+ *     natural (row-major) order, 1 .. 65535.  Only the first ncomp entries are read.
+ *   subseq_bytes: bytes of the stream per lane, a multiple of 4 in [16, 1024], 0 = 64; max_sync_rounds: launches of the
+ *     inter-workgroup synchronisation at the most, > 0, 0 = 16.
+ * A status other than GZ_SCAN_DECODED is not an error: the call returns GZ_OK, has written nothing, and the caller
+ * falls back.  GZ_E_ARG (before any device call): a wrong struct_size, NULL data, len, subseq_bytes or max_sync_rounds
+ * out of range, ncomp other than 1 or 3, chroma_factor other than 1 or 2 (2 with one component), w or h outside
+ * 1 .. 65535 or more than 2^21 blocks in a component, a quantiser outside 1 .. 65535, table counts the reader's
+ * ProcessDHT would refuse. */
+#define GZ_SCAN_DECODED 0
+#define GZ_SCAN_NOT_CONVERGED 1   /* the lanes' states still changed after max_sync_rounds launches */
+#define GZ_SCAN_BAD_SYMBOL 2      /* a code that does not exist, a DC category above 11, an end-of-band run */
+#define GZ_SCAN_RUN_PAST_BAND 3   /* an AC run past position 63 */
+#define GZ_SCAN_DC_RANGE 4        /* a DC value that is no int16 */
+#define GZ_SCAN_COEFF_RANGE 5     /* an AC category above 11, or a dequantised coefficient that is no int16 */
+#define GZ_SCAN_ENDS_EARLY 6      /* a bit consumed that the stream does not have */
+typedef struct gz_huffman_spec {
+  uint8_t counts[16];         /* codes of length 1 .. 16 */
+  uint8_t values[256];
+} gz_huffman_spec;
+typedef struct gz_scan {
+  int struct_size;            /* sizeof(gz_scan) */
+  int w, h, ncomp, chroma_factor;
+  const uint8_t* data;        /* host memory */
+  uint64_t len;
+  gz_huffman_spec dc[3], ac[3];
+  int quant[3][64];
+  int subseq_bytes, max_sync_rounds;
+} gz_scan;
+typedef struct gz_scan_result {
+  int status;                 /* GZ_SCAN_* */
+  int subsequences;           /* lanes */
+  int sync_rounds;            /* launches of the inter-workgroup synchronisation */
+  int reserved;
+  uint64_t end_offset;        /* GZ_SCAN_DECODED: where BitReader::Finish would leave the parser, from `data` (but see
+                                 below: data ending ff 00 xx) */
+} gz_scan_result;
+/* One exception to end_offset: where the third- and second-last bytes of `data` are ff 00 -- a stuffed pair across the
+ * reader's first stop, two bytes before the end of the file -- BitReader::Finish does not undo its NextByte and leaves the
+ * parser one byte further on than the data it consumed, or refuses a scan that consumed the ff.  The coefficients are
+ * right, end_offset is the end of the data consumed: a caller that needs the reader's own position reads such a stream
+ * on the host, as the library's own driver does (OfferScan, host/jpeg_reader.cc).
+ * host_coeffs: (nb + 2 * nbc) * 64 int16 on the host, written only on GZ_SCAN_DECODED (a one-component scan leaves the
+ * two chroma components zero). */
+int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_scan_result* result);
+/* ... and on GZ_SCAN_DECODED the pixels of those coefficients into `out`, the coefficients never leaving the device:
+ * gz_decode_coeffs_device's arithmetic, ownership, stream contract and argument checks. */
+int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result);
+
 /* Image pairs: the butteraugli distance of two images, and its map on the device --------
  * A context compares its original with JPEG candidates of it (gz_compare, below).  These entries compare it with ANY
  * image of its size: the context's original is the reference (butteraugli's rgb0), `other` the distorted image (rgb1).
