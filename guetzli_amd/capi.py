@@ -154,6 +154,7 @@ SIGNATURES = {
     "gz_reconstruct_device": (_I, [_P, _P]),
     "gz_decode_scan": (_I, [_I, _P, _P, _P]),
     "gz_decode_scan_device": (_I, [_I, _P, _P, _P]),
+    "gz_decode_scan_input": (_I, [_I, _P, _P, _P, _P]),
     "gz_compare_device_pixels": (_I, [_P, _P, _P, _P]),
     "gz_compare_rgb": (_I, [_P, _P, _P, _P]),
     "gz_distmap_device": (_I, [_P, _P]),
@@ -500,6 +501,27 @@ class Library:
         res = GzScanResult()
         self.check(self.lib.gz_decode_scan_device(device, C.byref(scan), C.byref(output), C.byref(res)))
         return self._scan_result(res)
+
+    def decode_scan_input(self, scan, device=0):
+        """gz_decode_scan_input: the scan as the host READER leaves it -> (per component the quantised coefficients int16
+        [height_in_blocks][width_in_blocks][64] on its grid padded to whole MCUs, or None where the status is not
+        "DECODED"; CheckJpegSanity's verdict, True = refused, or None; the gz_scan_result as a dict)."""
+        f = scan.chroma_factor if scan.chroma_factor in (1, 2) else 1
+        cols, rows = (scan.w + 8 * f - 1) // (8 * f), (scan.h + 8 * f - 1) // (8 * f)
+        grids = [(rows * f, cols * f)] + [(rows, cols)] * 2 if scan.ncomp == 3 else [(rows, cols)]
+        total = sum(gh * gw for gh, gw in grids)
+        out = np.full((max(total, 1), 64), 0x5a5a, np.int16)
+        res, large = GzScanResult(), C.c_int(-1)
+        self.check(self.lib.gz_decode_scan_input(device, C.byref(scan), _ptr(out), C.byref(large), C.byref(res)))
+        r = self._scan_result(res)
+        if r["status"] != "DECODED":
+            assert (out == 0x5a5a).all() and large.value == -1, "coefficients written without a verdict"
+            return None, None, r
+        comps, at = [], 0
+        for gh, gw in grids:
+            comps.append(out[at:at + gh * gw].reshape(gh, gw, 64))
+            at += gh * gw
+        return comps, bool(large.value), r
 
     def probe_emit_map(self, plane, dmap, device=0):
         """gz_probe_emit_map: the float32 [h][w] `plane` (any bit patterns) through the map's emit kernel alone, into

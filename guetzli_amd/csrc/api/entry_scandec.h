@@ -2,6 +2,8 @@
 // gz_kernels_scandec.h on one stream, the host reading one word per inter-workgroup round and the verdict at the end;
 // on GZ_SCAN_DECODED the coefficients go to the host, or through stage_reconstruct and k_emit_rgb into the caller's
 // image without leaving the device (entry_decode.h's DecodeScratch, stream contract and argument checks).
+// gz_decode_scan_input is the same call with passes 3 and 4 in their input mode: the reader's own result -- quantised
+// values on grids padded to whole MCUs -- and CheckJpegSanity's verdict, for an encode of JPEG input.
 // (part of the one translation unit gz_api.hip)
 #pragma once
 
@@ -66,8 +68,9 @@ ScanDecLayout scandec_layout(size_t upload, int nsub, int nwg, int rounds, int t
   return l;
 }
 
+// host_input (with large_coeff): the input mode, g.total * 64 values; otherwise `out` and / or host_coeffs.
 int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGeom g, int rounds, const gz_device_output* out,
-                int16_t* host_coeffs, gz_scan_result* result) {
+                int16_t* host_coeffs, int16_t* host_input, int* large_coeff, gz_scan_result* result) {
   const int w = sc->w, h = sc->h;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
   if (out && check_device_range(device, out->data, device_output_last(out, w, h), ingest_elem_size(out->dtype), "data", nullptr) != GZ_OK)
@@ -89,7 +92,10 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   const size_t upload = std::max<size_t>(end, 1);
   const ScanDecLayout l = scandec_layout(upload, g.nsub, nwg, rounds, g.total, scan_state_bytes(max_tiles));
   // the decoder's scratch and the coefficients, and for pixels what gz_decode_coeffs_device takes: all of them or none
-  if (!out) {
+  const size_t coeff_bytes = host_input ? (size_t)g.total * 128 : (size_t)c->nblk * 128;
+  if (host_input) {
+    TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&s.d_scan, l.total}, {(void**)&c->d_cand, coeff_bytes}}));
+  } else if (!out) {
     TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&s.d_scan, l.total}, {(void**)&c->d_cand, (size_t)c->nblk * 128}}));
   } else if (sc->chroma_factor == 2) {
     TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&s.d_scan, l.total}, {(void**)&c->d_cand, (size_t)c->nblk * 128},
@@ -122,7 +128,8 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   if (end > 0) HIPCHK(c, hipMemcpyAsync(d + l.data, sc->data, end, hipMemcpyHostToDevice, stream));
   HIPCHK(c, hipMemsetAsync(d + l.zeroed, 0, l.zeroed_end - l.zeroed, stream));
   HIPCHK(c, hipMemsetAsync(d_res, 0xff, 16, stream));
-  HIPCHK(c, hipMemsetAsync(c->d_cand, 0, (size_t)c->nblk * 128, stream));
+  if (host_input) HIPCHK(c, hipMemsetAsync(d_res + 2, 0, 8, stream));   // (the large-coefficient word)
+  HIPCHK(c, hipMemsetAsync(c->d_cand, 0, coeff_bytes, stream));
   // 1. synchronise
   launch_scandec_sync_first(stream, d_data, d_T, g, st, d_bnd);
   KCHK(c);
@@ -148,12 +155,14 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
             scan_state_at(d + l.scan_state, max_tiles), 1u);
   KCHK(c);
   // 3. write, 4. DC
-  launch_scandec_write(stream, d_data, d_T, g, st.entry, d_off, c->d_cand, d_dcd, d_res);
+  if (host_input) launch_scandec_write_input(stream, d_data, d_T, g, st.entry, d_off, c->d_cand, d_dcd, d_res);
+  else launch_scandec_write(stream, d_data, d_T, g, st.entry, d_off, c->d_cand, d_dcd, d_res);
   KCHK(c);
-  launch_scandec_dc(stream, sc->ncomp, d_dcd, d_T, g, c->d_cand, d_res);
+  if (host_input) launch_scandec_dc_input(stream, sc->ncomp, d_dcd, d_T, g, c->d_cand, d_res);
+  else launch_scandec_dc(stream, sc->ncomp, d_dcd, d_T, g, c->d_cand, d_res);
   KCHK(c);
-  unsigned res[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
+  unsigned res[3] = {0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(res, d_res, host_input ? 12 : 8, hipMemcpyDeviceToHost, stream));
   HIPCHK(c, hipStreamSynchronize(stream));
   s.idle = true;
   if (res[0] != 0xffffffffu) {
@@ -172,6 +181,7 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   result->end_offset = pos;
   s.idle = false;
   if (host_coeffs) HIPCHK(c, hipMemcpyAsync(host_coeffs, c->d_cand, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, stream));
+  if (host_input) HIPCHK(c, hipMemcpyAsync(host_input, c->d_cand, coeff_bytes, hipMemcpyDeviceToHost, stream));
   if (out) {
     if (out->consumer_stream) {
       TRY(own_event(c, &s.ev));
@@ -186,11 +196,13 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   }
   HIPCHK(c, hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind this)
   s.idle = true;
+  if (host_input) *large_coeff = res[2] != 0 ? 1 : 0;
   result->status = GZ_SCAN_DECODED;
   return GZ_OK;
 }
 
-int decode_scan_entry(int device, const gz_scan* sc, const gz_device_output* out, int16_t* host_coeffs, gz_scan_result* result) {
+int decode_scan_entry(int device, const gz_scan* sc, const gz_device_output* out, int16_t* host_coeffs, int16_t* host_input,
+                      int* large_coeff, gz_scan_result* result) {
   if (!result) return GZ_E_ARG;
   memset(result, 0, sizeof(*result));
   result->status = GZ_SCAN_NOT_CONVERGED;   // (until a verdict is reached)
@@ -203,7 +215,7 @@ int decode_scan_entry(int device, const gz_scan* sc, const gz_device_output* out
   if (out && check_device_output(out, sc->w, sc->h) != GZ_OK) return GZ_E_ARG;
   int prev = -1;
   if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  const int rc = decode_scan(device, sc, T, g, rounds, out, host_coeffs, result);
+  const int rc = decode_scan(device, sc, T, g, rounds, out, host_coeffs, host_input, large_coeff, result);
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
   return rc;
 }
@@ -213,12 +225,17 @@ extern "C" {
 
 int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_scan_result* result) {
   if (!host_coeffs) return GZ_E_ARG;
-  return decode_scan_entry(device, scan, nullptr, host_coeffs, result);
+  return decode_scan_entry(device, scan, nullptr, host_coeffs, nullptr, nullptr, result);
 }
 
 int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result) {
   if (!out) return GZ_E_ARG;
-  return decode_scan_entry(device, scan, out, nullptr, result);
+  return decode_scan_entry(device, scan, out, nullptr, nullptr, nullptr, result);
+}
+
+int gz_decode_scan_input(int device, const gz_scan* scan, int16_t* host_coeffs, int* large_coeff, gz_scan_result* result) {
+  if (!host_coeffs || !large_coeff) return GZ_E_ARG;
+  return decode_scan_entry(device, scan, nullptr, nullptr, host_coeffs, large_coeff, result);
 }
 
 }  // extern "C"

@@ -22,6 +22,11 @@
 //                             all blocks in scan order; the first error in scan order by atomicMin on block << 3 | reason.
 //   4. k_scandec_dc           per component the running sum of the differences, its range checks, coefficient 0.
 //
+// Passes 3 and 4 have a second store mode, INPUT (k_scandec_write_input, k_scandec_dc_input): what the host READER leaves
+// in JpegComponentIn::coeffs -- the values QUANTISED, as coded, on grids padded to whole MCUs, every block of the scan
+// stored (scandec_input_block_at) -- and CheckJpegSanity's verdict over them in res[2]: a word that is set where
+// |value * quantiser| > 4096 for any stored coefficient, the padding's included.
+//
 // Every loop is bounded by a launch-time quantity: a lane decodes at most 8 * subseq_bytes symbols (each takes a bit or
 // more and starts inside the subsequence), a workgroup settles in at most 256 rounds, the DC pass walks
 // ceil(blocks / 256) blocks per thread.  Nothing waits for another workgroup inside a launch.  Reads of the stream are
@@ -288,6 +293,29 @@ GZ_DEVFN long long scandec_block_at(const ScanDecGeom& g, int b, int* comp) {
   return (first + (long long)y * rw + x) * 64;
 }
 
+// The same in the reader's own layout: the components one after the other, each [height_in_blocks][width_in_blocks][64]
+// on its grid padded to whole MCUs -- of a 4:2:0 scan 2 mcu_cols x 2 mcu_rows for component 0, mcu_cols x mcu_rows
+// otherwise.  Every block b < total has an address below total * 64.
+GZ_DEVFN long long scandec_input_block_at(const ScanDecGeom& g, int b, int* comp) {
+  const int mcu = b / g.units, u = b - mcu * g.units;
+  const int my = mcu / g.mcu_cols, mx = mcu - my * g.mcu_cols;
+  const int c = scandec_comp(g.units, u);
+  *comp = c;
+  const long long mcus = g.total / g.units;
+  if (g.units == 6 && c == 0) return ((long long)(2 * my + (u >> 1)) * (2 * g.mcu_cols) + 2 * mx + (u & 1)) * 64;
+  const long long first = g.units == 6 ? (3 + c) * mcus : c * mcus;
+  return (first + mcu) * 64;
+}
+template <bool INPUT>
+GZ_DEVFN long long scandec_store_at(const ScanDecGeom& g, int b, int* comp) {
+  return INPUT ? scandec_input_block_at(g, b, comp) : scandec_block_at(g, b, comp);
+}
+// CheckJpegSanity's condition on one stored value (the product in 32 bits: |v| < 2^15, q < 2^16).
+GZ_DEVFN bool scandec_large(int v, int q) {
+  const int p = v * q;
+  return (p < 0 ? -p : p) > (1 << 12);
+}
+
 GZ_DEVFN void scandec_fail(unsigned* res, int b, int reason) { atomicMin(&res[0], ((unsigned)b << 3) | (unsigned)reason); }
 
 __constant__ unsigned char kScanDecNatural[64] = {
@@ -296,11 +324,12 @@ __constant__ unsigned char kScanDecNatural[64] = {
 };
 
 // Pass 3.  res[0]: the first error (block << 3 | reason, 0xffffffff: none), res[1]: the bit behind the last block's last
-// symbol (0xffffffff: the scan never got there).  coeffs and dcd are zero when the kernel starts.
-__global__ __launch_bounds__(256) void k_scandec_write(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T, ScanDecGeom g,
-                                                       const unsigned long long* __restrict__ entry,
-                                                       const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
-                                                       int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
+// symbol (0xffffffff: the scan never got there), INPUT: res[2] the large-coefficient word (zero when the kernel starts).
+// coeffs and dcd are zero when the kernel starts.
+template <bool INPUT>
+GZ_DEVFN void scandec_write_body(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T, const ScanDecGeom& g,
+                                 const unsigned long long* __restrict__ entry, const unsigned long long* __restrict__ off,
+                                 int16_t* __restrict__ coeffs, int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
   __shared__ uint16_t s_fast[kScanDecTables][512];
   scandec_load_fast(s_fast, T);
   __syncthreads();
@@ -318,7 +347,7 @@ __global__ __launch_bounds__(256) void k_scandec_write(const uint8_t* __restrict
   const unsigned lane_end = e < g.end_bits ? (unsigned)e : g.end_bits;
   const unsigned end = g.end_bits >> 3;
   int comp = 0;
-  long long at = scandec_block_at(g, b, &comp);
+  long long at = scandec_store_at<INPUT>(g, b, &comp);
   for (int it = 0; it < 8 * g.subseq_bytes && p < lane_end; ++it) {
     unsigned idx[5];
     const unsigned w = scandec_peek(data, end, p, idx);
@@ -331,20 +360,40 @@ __global__ __launch_bounds__(256) void k_scandec_write(const uint8_t* __restrict
       dcd[b] = (int16_t)s.value;
     } else if (s.pos > 0 && at >= 0) {
       const int nat = kScanDecNatural[s.pos];
-      const int v = s.value * T->quant[comp][nat];
-      if (v != (int)(int16_t)v) { scandec_fail(res, b, kScanErrCoeffRange); return; }
-      coeffs[at + nat] = (int16_t)v;
+      if (INPUT) {   // as coded (|value| <= 2047: an int16), and CheckJpegSanity where it is stored
+        if (scandec_large(s.value, T->quant[comp][nat])) atomicOr(&res[2], 1u);
+        coeffs[at + nat] = (int16_t)s.value;
+      } else {
+        const int v = s.value * T->quant[comp][nat];
+        if (v != (int)(int16_t)v) { scandec_fail(res, b, kScanErrCoeffRange); return; }
+        coeffs[at + nat] = (int16_t)v;
+      }
     }
     if (s.done) {
       if (++b == g.total) { res[1] = p; return; }
-      at = scandec_block_at(g, b, &comp);
+      at = scandec_store_at<INPUT>(g, b, &comp);
     }
   }
 }
 
+__global__ __launch_bounds__(256) void k_scandec_write(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T, ScanDecGeom g,
+                                                       const unsigned long long* __restrict__ entry,
+                                                       const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
+                                                       int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
+  scandec_write_body<false>(data, T, g, entry, off, coeffs, dcd, res);
+}
+__global__ __launch_bounds__(256) void k_scandec_write_input(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
+                                                             ScanDecGeom g, const unsigned long long* __restrict__ entry,
+                                                             const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
+                                                             int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
+  scandec_write_body<true>(data, T, g, entry, off, coeffs, dcd, res);
+}
+
 // Pass 4: one workgroup per component; a thread sums a run of ceil(n / 256) of the component's blocks in scan order.
-__global__ __launch_bounds__(256) void k_scandec_dc(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T, ScanDecGeom g,
-                                                    int16_t* __restrict__ coeffs, unsigned* __restrict__ res) {
+// INPUT: the sum itself is stored, of every block, and checked as CheckJpegSanity checks it.
+template <bool INPUT>
+GZ_DEVFN void scandec_dc_body(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T, const ScanDecGeom& g,
+                              int16_t* __restrict__ coeffs, unsigned* __restrict__ res) {
   __shared__ long long s_sum[kScanDecLanes];   // (2^21 blocks of +-2047 leave 32 bits)
   const int t = threadIdx.x, c = (int)blockIdx.x;
   const int per = g.units == 6 && c == 0 ? 4 : 1;           // the component's blocks in an MCU
@@ -369,12 +418,25 @@ __global__ __launch_bounds__(256) void k_scandec_dc(const int16_t* __restrict__ 
     run += dcd[b];
     if (run != (long long)(int16_t)run) { scandec_fail(res, b, kScanErrDcRange); return; }
     int comp;
-    const long long at = scandec_block_at(g, b, &comp);
+    const long long at = scandec_store_at<INPUT>(g, b, &comp);
     if (at < 0) continue;
-    const int v = (int)run * q;
-    if (v != (int)(int16_t)v) { scandec_fail(res, b, kScanErrCoeffRange); return; }
-    coeffs[at] = (int16_t)v;
+    if (INPUT) {
+      if (scandec_large((int)run, q)) atomicOr(&res[2], 1u);
+      coeffs[at] = (int16_t)run;
+    } else {
+      const int v = (int)run * q;
+      if (v != (int)(int16_t)v) { scandec_fail(res, b, kScanErrCoeffRange); return; }
+      coeffs[at] = (int16_t)v;
+    }
   }
+}
+__global__ __launch_bounds__(256) void k_scandec_dc(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T, ScanDecGeom g,
+                                                    int16_t* __restrict__ coeffs, unsigned* __restrict__ res) {
+  scandec_dc_body<false>(dcd, T, g, coeffs, res);
+}
+__global__ __launch_bounds__(256) void k_scandec_dc_input(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T, ScanDecGeom g,
+                                                          int16_t* __restrict__ coeffs, unsigned* __restrict__ res) {
+  scandec_dc_body<true>(dcd, T, g, coeffs, res);
 }
 
 // ---------------------------------------------------------------------------------------------- host side ----
@@ -444,6 +506,16 @@ inline void launch_scandec_write(hipStream_t stream, const uint8_t* data, const 
 inline void launch_scandec_dc(hipStream_t stream, int ncomp, const int16_t* dcd, const ScanDecTables* T, const ScanDecGeom& g, int16_t* coeffs,
                               unsigned* res) {
   GZ_LAUNCH(k_scandec_dc, dim3(ncomp), dim3(kScanDecLanes), stream, dcd, T, g, coeffs, res);
+}
+// The input mode: coeffs holds g.total * 64 elements, res four words of which res[2] is zero.
+inline void launch_scandec_write_input(hipStream_t stream, const uint8_t* data, const ScanDecTables* T, const ScanDecGeom& g,
+                                       const unsigned long long* entry, const unsigned long long* off, int16_t* coeffs, int16_t* dcd,
+                                       unsigned* res) {
+  GZ_LAUNCH(k_scandec_write_input, dim3(gz_div_up(g.nsub, kScanDecLanes)), dim3(kScanDecLanes), stream, data, T, g, entry, off, coeffs, dcd, res);
+}
+inline void launch_scandec_dc_input(hipStream_t stream, int ncomp, const int16_t* dcd, const ScanDecTables* T, const ScanDecGeom& g,
+                                    int16_t* coeffs, unsigned* res) {
+  GZ_LAUNCH(k_scandec_dc_input, dim3(ncomp), dim3(kScanDecLanes), stream, dcd, T, g, coeffs, res);
 }
 
 }  // namespace gz

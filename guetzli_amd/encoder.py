@@ -83,13 +83,20 @@ class HostLibrary:
             if hasattr(self.lib, name):   # (a host library built before the device's scan decoder has neither)
                 getattr(self.lib, name).restype = C.c_long
                 getattr(self.lib, name).argtypes = args
+        for name, args in (("gzh_process_jpeg_entropy", [C.c_void_p, C.c_long, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long]),
+                           ("gzh_read_jpeg_entropy", [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long])):
+            if hasattr(self.lib, name):   # (... and one built before JPEG input could come from it has neither of these)
+                getattr(self.lib, name).restype = C.c_long
+                getattr(self.lib, name).argtypes = args
         self.lib.gzh_butteraugli_score_for_quality.restype = C.c_double
         self.lib.gzh_butteraugli_score_for_quality.argtypes = [C.c_double]
 
     def _process(self, data, w, h, quality, target, device, clear_metadata, try_420, force_420,
-                 use_silver_screen, lookahead, new_model, want_trace):
+                 use_silver_screen, lookahead, new_model, want_trace, entropy_mode=None):
         """gzh_process_params -- or, for a capi.GzDevicePixels / GzDeviceImage, gzh_process_device_pixels /
-        gzh_process_device -- with a buffer that grows to what the library asks for."""
+        gzh_process_device; for JPEG bytes with an entropy_mode (_entropy_mode), gzh_process_jpeg_entropy, and the
+        info gets "input" -- with a buffer that grows to what the library asks for."""
         is_jpeg = isinstance(data, (bytes, bytearray))
         on_device = not is_jpeg and not isinstance(data, np.ndarray)
         buf = np.frombuffer(data, np.uint8) if is_jpeg else data
@@ -106,10 +113,14 @@ class HostLibrary:
                            int(use_silver_screen), int(lookahead), int(new_model))
         tr = C.create_string_buffer(1 << 24) if want_trace else None
         tm = C.create_string_buffer(1 << 12)
+        einfo = (C.c_int64 * 6)()
         for _ in range(2):
             out = np.empty(cap, np.uint8)
             qt = (-1.0 if target is not None else float(quality), float(target or 0.0))
-            if on_device:
+            if entropy_mode is not None:
+                n = self.lib.gzh_process_jpeg_entropy(buf.ctypes.data if len(data) else None, len(data), *qt, ip, entropy_mode, einfo,
+                                                      out.ctypes.data, cap, tr, len(tr) if tr else 0, tm, len(tm))
+            elif on_device:
                 entry = self.lib.gzh_process_device_pixels if isinstance(data, GzDevicePixels) else self.lib.gzh_process_device
                 n = entry(C.addressof(data), w, h, *qt, ip, out.ctypes.data, cap, tr, len(tr) if tr else 0, tm, len(tm))
             else:
@@ -131,8 +142,10 @@ class HostLibrary:
                     counters[k[1:]] = int(v)
                 else:
                     timers[k] = float(v)
-        return out[:n].tobytes(), {"trace": tr.value.decode() if tr else None,
-                                   "timers": timers, "counters": counters}
+        info = {"trace": tr.value.decode() if tr else None, "timers": timers, "counters": counters}
+        if entropy_mode is not None:
+            info["input"] = self._entropy_info(einfo)
+        return out[:n].tobytes(), info
 
     def process(self, rgb, quality=95.0, target=None, device=0, want_trace=False, try_420=False,
                 force_420=False, use_silver_screen=False, lookahead=3, new_model=True):
@@ -267,13 +280,48 @@ class HostLibrary:
 
     def process_jpeg(self, data, quality=95.0, target=None, device=0, clear_metadata=True,
                      want_trace=False, try_420=False, force_420=False, use_silver_screen=False,
-                     lookahead=3, new_model=True):
+                     lookahead=3, new_model=True, entropy="host", subseq_bytes=0, max_sync_rounds=0):
         """guetzli::Process(params, stats, jpeg_data, &out) for a YUV 4:4:4 or 4:2:0 JPEG.
-        Returns (jpeg_bytes, trace) or raises if the input is refused (message on stderr)."""
-        jpg, info = self._process(bytes(data), 0, 0, quality, target, device, clear_metadata,
-                                  try_420, force_420, use_silver_screen, lookahead, new_model,
-                                  want_trace)
+        Returns (jpeg_bytes, trace) or raises if the input is refused (message on stderr).  entropy="device": the
+        input's scan is read by the device's Huffman decoder where it is eligible and the decoder reaches a verdict,
+        by the host otherwise, silently -- the same bytes and trace either way (process_jpeg_info says which)."""
+        if entropy == "host" and not subseq_bytes and not max_sync_rounds:   # (the call every encode made before there was a choice)
+            jpg, info = self._process(bytes(data), 0, 0, quality, target, device, clear_metadata,
+                                      try_420, force_420, use_silver_screen, lookahead, new_model,
+                                      want_trace)
+        else:
+            jpg, info = self.process_jpeg_info(data, quality, target, device, clear_metadata, want_trace, try_420, force_420,
+                                               use_silver_screen, lookahead, new_model, entropy, subseq_bytes, max_sync_rounds)
         return jpg, info["trace"]
+
+    def process_jpeg_info(self, data, quality=95.0, target=None, device=0, clear_metadata=True,
+                          want_trace=False, try_420=False, force_420=False, use_silver_screen=False,
+                          lookahead=3, new_model=True, entropy="host", subseq_bytes=0, max_sync_rounds=0):
+        """process_jpeg with the whole record: (jpeg_bytes, info) with process()'s 'trace', 'timers', 'counters' and
+        'input', what the read of the input says of its entropy path: 'path' ("device" | "host"), 'status' (the
+        gz_scan_result's of the attempt, None: none was made), 'subsequences', 'sync_rounds', 'end_offset', 'rc'."""
+        mode = self._entropy_mode(entropy, subseq_bytes, max_sync_rounds)
+        return self._process(bytes(data), 0, 0, quality, target, device, clear_metadata, try_420, force_420,
+                             use_silver_screen, lookahead, new_model, want_trace, entropy_mode=mode)
+
+    def read_jpeg_dump(self, data, entropy="host", device=0, subseq_bytes=0, max_sync_rounds=0):
+        """The reader's result as an encode of JPEG input gets it, as the canonical dump of host/reader_dump.h:
+        (bytes, or None where the stream is refused; the entropy info as process_jpeg_info's 'input').  Test hook."""
+        buf = np.frombuffer(data, np.uint8)
+        mode = self._entropy_mode(entropy, subseq_bytes, max_sync_rounds)
+        info = (C.c_int64 * 6)()
+        # room for four components on grids padded to the largest MCU (32 x 32 pixels) and the metadata: one read as a rule
+        w, h = _jpeg_dimensions(data)
+        cap = (0 if w * h > (1 << 28) else 8 * (w + 32) * (h + 32)) + 2 * len(data) + 4096
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            n = self.lib.gzh_read_jpeg_entropy(buf.ctypes.data if len(data) else None, len(data), device, mode, info, out.ctypes.data, cap)
+            if n < 0:
+                return None, self._entropy_info(info)
+            if n <= cap:
+                break
+            cap = n
+        return out[:n].tobytes(), self._entropy_info(info)
 
     def write_jpeg(self, coeffs, w, h, q=None, factor=1):
         """WriteJpeg of dequantised coefficients (frame layout of include/guetzli_amd.h:
@@ -672,6 +720,15 @@ def read_png(data):
 def process_png(data, quality=95.0, **kw):
     """`guetzli --quality Q in.png out.jpg`: ReadPNG + Process.  Returns (jpeg_bytes, info)."""
     return load_host().process(load_host().read_png(data), quality=quality, **kw)
+
+
+def process_jpeg(data, quality=95.0, entropy="host", **kw):
+    """`guetzli --quality Q in.jpg out.jpg`: Process(params, stats, jpeg_data, &out) for a YUV 4:4:4 or 4:2:0 JPEG.
+    Returns (jpeg_bytes, info); info["input"] says who read the input's scan.  entropy="device": the GPU's Huffman
+    decoder reads it where the scan is eligible (baseline, one scan, no restart interval) and the decoder reaches a
+    verdict; every other stream is read by the host as with entropy="host", silently -- the same streams are accepted
+    and the same bytes written either way.  The keywords are HostLibrary.process_jpeg_info's."""
+    return load_host().process_jpeg_info(data, quality=quality, entropy=entropy, **kw)
 
 
 # ---- the butteraugli distance of two images (capi: gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device) ----

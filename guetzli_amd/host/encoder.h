@@ -161,7 +161,8 @@ class Encoder {
   ~Encoder();
   bool Run(const std::vector<uint8_t>& rgb, int w, int h, std::string* out);
   bool RunDevice(const DeviceImage& image, int w, int h, std::string* out);
-  bool RunJpeg(const std::string& jpeg_data, std::string* out);
+  bool RunJpeg(const std::string& jpeg_data, std::string* out, const EntropyOptions& entropy = EntropyOptions(),
+               DecodeInfo* info = nullptr);
 
  private:
   // ---- processor.cc ----

@@ -279,6 +279,26 @@ long gzh_decode_jpeg_coeffs(const uint8_t* data, long len, int device, const int
   GZH_GUARD_END
 }
 
+// Process(params, stats, jpeg_data, &out, EntropyOptions, &info): gzh_process_jpeg with every field of Params
+// (iparams as gzh_process_params'), the input's entropy path chosen by mode[3] (EntropyFrom; NULL: the host) and
+// reported in info[6] (CopyDecodeInfo; may be NULL; written whether the encode succeeds or not).
+long gzh_process_jpeg_entropy(const uint8_t* data, long len, double quality, float target, const int* iparams, const int* mode,
+                              int64_t* info, uint8_t* out, long cap, char* trace, long trace_cap, char* timers, long timers_cap) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0 || !iparams) return -1;
+  const guetzli_amd::Params params = ParamsFrom(quality, target, iparams);
+  guetzli_amd::ProcessStats stats;
+  std::string dbg;
+  if (trace) stats.debug_output = &dbg;
+  std::string jpg;
+  guetzli_amd::DecodeInfo di;
+  const bool ok = guetzli_amd::Process(params, &stats, std::string((const char*)data, (size_t)len), &jpg, EntropyFrom(mode), &di);
+  CopyDecodeInfo(di, info);
+  if (!ok) return -1;
+  return Deliver(jpg, dbg, stats, out, cap, trace, trace_cap, timers, timers_cap);
+  GZH_GUARD_END
+}
+
 double gzh_butteraugli_score_for_quality(double q) {
   return guetzli_amd::ButteraugliScoreForQuality(q);
 }
@@ -302,6 +322,22 @@ long gzh_read_jpeg(const uint8_t* data, long len, uint8_t* out, long cap) {
   if (!guetzli_amd::ReadJpeg(data, (size_t)len, &jpg, &err)) return -1;
   const std::string d = guetzli_amd::DumpJpegInput(jpg);
   if ((long)d.size() <= cap) memcpy(out, d.data(), d.size());
+  return (long)d.size();
+  GZH_GUARD_END
+}
+
+// The same from the reader as an encode of JPEG input calls it (ReadJpegInput), the scan read as mode[3] says on GPU
+// `device`; info[6] as above (may be NULL).  Test hook, the twin of gzh_read_jpeg.
+long gzh_read_jpeg_entropy(const uint8_t* data, long len, int device, const int* mode, int64_t* info, uint8_t* out, long cap) {
+  GZH_GUARD_BEGIN
+  if (!data || len < 0) return -1;
+  guetzli_amd::JpegInput jpg;
+  guetzli_amd::DecodeInfo di;
+  const bool ok = guetzli_amd::ReadJpegInput(std::string((const char*)data, (size_t)len), device, EntropyFrom(mode), &jpg, nullptr, &di);
+  CopyDecodeInfo(di, info);
+  if (!ok) return -1;
+  const std::string d = guetzli_amd::DumpJpegInput(jpg);
+  if (out && (long)d.size() <= cap) memcpy(out, d.data(), d.size());
   return (long)d.size();
   GZH_GUARD_END
 }

@@ -22,6 +22,7 @@ extern "C" int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h,
 // ... and the device's scan decoder: without it every scan is read by the host.
 extern "C" int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_scan_result* result) __attribute__((weak));
 extern "C" int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result) __attribute__((weak));
+extern "C" int gz_decode_scan_input(int device, const gz_scan* scan, int16_t* host_coeffs, int* large_coeff, gz_scan_result* result) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -292,21 +293,124 @@ static bool HasYCbCrColorSpace(const JpegInput& jpg) {
   return jpg.components[0].id != 'R' || jpg.components[1].id != 'G' || jpg.components[2].id != 'B';
 }
 
+// A ScanRequest as the gz_scan the device's scan decoder takes.
+static void ScanFromRequest(const ScanRequest& rq, const EntropyOptions& opt, gz_scan* sc) {
+  memset(sc, 0, sizeof(*sc));
+  sc->struct_size = (int)sizeof(*sc);
+  sc->w = rq.width; sc->h = rq.height; sc->ncomp = rq.ncomp; sc->chroma_factor = rq.chroma_factor;
+  sc->data = rq.data;
+  sc->len = rq.len;
+  for (int c = 0; c < rq.ncomp; ++c) {
+    memcpy(sc->dc[c].counts, rq.dc[c].counts, 16);
+    memcpy(sc->dc[c].values, rq.dc[c].values, 256);
+    memcpy(sc->ac[c].counts, rq.ac[c].counts, 16);
+    memcpy(sc->ac[c].values, rq.ac[c].values, 256);
+    memcpy(sc->quant[c], rq.quant[c], sizeof(sc->quant[c]));
+  }
+  sc->subseq_bytes = opt.subseq_bytes;
+  sc->max_sync_rounds = opt.max_sync_rounds;
+}
+
+namespace {
+// What an encode of JPEG input with EntropyOptions::device gives the reader's hook: the scan as the READER leaves it
+// (gz_decode_scan_input: quantised values on the grids padded to whole MCUs, and CheckJpegSanity's verdict over them),
+// kept until ReadJpeg has returned and the components' `coeffs` can be filled from it.  It takes every scan the reader
+// offers -- grey, 4:4:4, 4:2:0: no pixels are made here, so the colour space is not its business.
+struct InputScan {
+  int device = 0;
+  EntropyOptions opt;
+  DecodeInfo info;
+  bool large_coeff = false;
+  std::vector<int16_t>* coeffs = nullptr;   // the components one after the other
+  bool operator()(const ScanRequest& rq, size_t* end_offset) {
+    if (!gz_decode_scan_input) return false;
+    static thread_local gz_scan sc;
+    ScanFromRequest(rq, opt, &sc);
+    const int f = rq.chroma_factor;
+    const size_t mcus = (size_t)((rq.width + 8 * f - 1) / (8 * f)) * ((rq.height + 8 * f - 1) / (8 * f));
+    coeffs->resize(mcus * (rq.ncomp == 1 ? 1 : f == 2 ? 6 : 3) * 64);
+    gz_scan_result res;
+    memset(&res, 0, sizeof(res));
+    int large = 0;
+    const int rc = gz_decode_scan_input(device, &sc, coeffs->data(), &large, &res);
+    info.rc = rc;
+    if (rc != GZ_OK) {   // the host reads the scan: the call's failure costs the attempt, not the encode -- and is on record
+      fprintf(stderr, "guetzli_amd: the device's scan decoder failed (%s): the host reads the scan\n", gz_strerror(rc));
+      return false;
+    }
+    info.status = res.status;
+    info.subsequences = res.subsequences;
+    info.sync_rounds = res.sync_rounds;
+    info.end_offset = res.end_offset;
+    if (res.status != GZ_SCAN_DECODED) return false;
+    large_coeff = large != 0;
+    *end_offset = (size_t)res.end_offset;
+    return true;
+  }
+};
+
+// The coefficients between the device and the components, kept per thread: a read after the first of a size touches no
+// fresh pages (50 MB at 4K).
+std::vector<int16_t>& InputScratchCoeffs() {
+  static thread_local std::vector<int16_t> v;
+  return v;
+}
+}  // namespace
+
+bool ReadJpegInput(const std::string& data, int device, const EntropyOptions& entropy, JpegInput* jpg, bool* large_coeff,
+                   DecodeInfo* info) {
+  if (info) *info = DecodeInfo();
+  if (large_coeff) *large_coeff = false;
+  if (!entropy.device) return ReadJpeg((const uint8_t*)data.data(), data.size(), jpg);
+  InputScan scan;
+  scan.device = device;
+  scan.opt = entropy;
+  scan.coeffs = &InputScratchCoeffs();
+  const ScanDecoder hook = [&scan](const ScanRequest& rq, size_t* end) { return scan(rq, end); };
+  const bool ok = ReadJpeg((const uint8_t*)data.data(), data.size(), jpg, nullptr, &hook);
+  if (info) *info = scan.info;
+  if (!ok) return false;
+  if (!jpg->scan_decoded_elsewhere) return true;   // (the block loop ran: nothing was offered, or the device handed it back)
+  // ... as the block loop would have left it: `coeffs` of every component filled, everything else the parser's
+  const int16_t* src = scan.coeffs->data();
+  size_t at = 0;
+  for (JpegComponentIn& c : jpg->components) {
+    const size_t n = (size_t)c.width_in_blocks * c.height_in_blocks * 64;
+    if (at + n > scan.coeffs->size()) {
+      fprintf(stderr, "guetzli_amd: the device's scan holds fewer blocks than the frame\n");
+      return false;
+    }
+    c.coeffs.assign(src + at, src + at + n);
+    at += n;
+  }
+  jpg->scan_decoded_elsewhere = false;
+  if (info) info->device_path = true;
+  if (large_coeff) *large_coeff = scan.large_coeff;
+  return true;
+}
+
 // guetzli::Process(params, stats, jpeg_data, &out) (processor.cc:890-924) for YUV 4:4:4 input.
-bool Encoder::RunJpeg(const std::string& data, std::string* out) {
+bool Encoder::RunJpeg(const std::string& data, std::string* out, const EntropyOptions& entropy, DecodeInfo* info) {
   const Stopwatch start;
   JpegInput jpg;
-  if (!ReadJpeg((const uint8_t*)data.data(), data.size(), &jpg)) {
+  bool large_coeff = false;
+  DecodeInfo read_info;
+  const bool read = ReadJpegInput(data, params_.device, entropy, &jpg, &large_coeff, &read_info);
+  if (info) *info = read_info;
+  if (!read) {
     fprintf(stderr, "Can't read jpg data from input file\n");
     return false;
   }
-  for (const JpegComponentIn& comp : jpg.components) {   // CheckJpegSanity, :117-131
-    const int* q = jpg.quant[comp.quant_idx].values;
-    for (size_t i = 0; i < comp.coeffs.size(); ++i)
-      if (std::abs((int64_t)comp.coeffs[i] * q[i % 64]) > (1 << 12)) {
-        fprintf(stderr, "Unsupported input JPEG (unexpectedly large coefficient values).\n");
-        return false;
-      }
+  if (!read_info.device_path) {   // (the device has looked at every coefficient it stored)
+    for (const JpegComponentIn& comp : jpg.components) {   // CheckJpegSanity, :117-131
+      const int* q = jpg.quant[comp.quant_idx].values;
+      for (size_t i = 0; i < comp.coeffs.size() && !large_coeff; ++i)
+        large_coeff = std::abs((int64_t)comp.coeffs[i] * q[i % 64]) > (1 << 12);
+    }
+  }
+  if (large_coeff) {
+    fprintf(stderr, "Unsupported input JPEG (unexpectedly large coefficient values).\n");
+    return false;
   }
   const size_t ncomp = jpg.components.size();
   const bool ycbcr3 = ncomp == 3 && HasYCbCrColorSpace(jpg);
@@ -492,20 +596,7 @@ struct DeviceScan {
     if ((expect_w > 0 || expect_h > 0) && (rq.width != expect_w || rq.height != expect_h)) return false;   // (refused below)
     if (rq.ncomp == 3 && !HasYCbCrColorSpace(*rq.so_far)) return false;
     static thread_local gz_scan sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.struct_size = (int)sizeof(sc);
-    sc.w = rq.width; sc.h = rq.height; sc.ncomp = rq.ncomp; sc.chroma_factor = rq.chroma_factor;
-    sc.data = rq.data;
-    sc.len = rq.len;
-    for (int c = 0; c < rq.ncomp; ++c) {
-      memcpy(sc.dc[c].counts, rq.dc[c].counts, 16);
-      memcpy(sc.dc[c].values, rq.dc[c].values, 256);
-      memcpy(sc.ac[c].counts, rq.ac[c].counts, 16);
-      memcpy(sc.ac[c].values, rq.ac[c].values, 256);
-      memcpy(sc.quant[c], rq.quant[c], sizeof(sc.quant[c]));
-    }
-    sc.subseq_bytes = opt.subseq_bytes;
-    sc.max_sync_rounds = opt.max_sync_rounds;
+    ScanFromRequest(rq, opt, &sc);
     gz_scan_result res;
     memset(&res, 0, sizeof(res));
     int rc;
@@ -697,10 +788,15 @@ bool Process(const Params& params, ProcessStats* stats, const DeviceImage& image
 
 bool Process(const Params& params, ProcessStats* stats, const std::string& jpeg_data,
              std::string* out) {
+  return Process(params, stats, jpeg_data, out, EntropyOptions(), nullptr);
+}
+
+bool Process(const Params& params, ProcessStats* stats, const std::string& jpeg_data, std::string* out,
+             const EntropyOptions& entropy, DecodeInfo* info) {
   ProcessStats dummy;
   if (stats == nullptr) stats = &dummy;
   Encoder enc(params, stats);
-  return enc.RunJpeg(jpeg_data, out);
+  return enc.RunJpeg(jpeg_data, out, entropy, info);
 }
 
 }  // namespace guetzli_amd

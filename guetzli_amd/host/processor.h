@@ -133,6 +133,19 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* 
 struct JpegInput;
 bool DecodeJpegCoeffs(const std::string& jpeg, int device, const EntropyOptions& entropy, int* w, int* h, int* factor,
                       std::vector<int16_t>* coeffs, DecodeInfo* info = nullptr, JpegInput* meta = nullptr);
+// Process(params, stats, jpeg_data, &out) with the input's scan read as `entropy` says.  device: an eligible scan --
+// grey, 4:4:4 or 4:2:0, whatever its colour space -- is read by the device's decoder in its input mode
+// (gz_decode_scan_input: the READER's result, quantised values on the grids padded to whole MCUs), and CheckJpegSanity's
+// verdict comes from the device too; any other scan, any status other than GZ_SCAN_DECODED and any failing call (one
+// line on stderr) leave the scan to the host's block loop, silently.  Verdict, messages, output bytes and trace do not
+// depend on it; *info (optional) says which path the input took.  The overload above is this one with EntropyOptions().
+bool Process(const Params& params, ProcessStats* stats, const std::string& jpeg_data, std::string* out,
+             const EntropyOptions& entropy, DecodeInfo* info = nullptr);
+// ReadJpeg as that encode calls it: *jpg as the host's block loop leaves it by either path (`coeffs` of every component
+// filled, scan_decoded_elsewhere false); *large_coeff (optional): CheckJpegSanity's verdict where the device path ran
+// (info->device_path), false otherwise -- the caller then runs the check itself.
+bool ReadJpegInput(const std::string& jpeg, int device, const EntropyOptions& entropy, JpegInput* jpg, bool* large_coeff = nullptr,
+                   DecodeInfo* info = nullptr);
 // The size the frame header declares (of a stream ReadJpeg accepts).
 bool JpegSize(const std::string& jpeg, int* w, int* h);
 

@@ -384,6 +384,19 @@ int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_sca
 /* ... and on GZ_SCAN_DECODED the pixels of those coefficients into `out`, the coefficients never leaving the device:
  * gz_decode_coeffs_device's arithmetic, ownership, stream contract and argument checks. */
 int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result);
+/* The reader's own result, for an encode of JPEG input (host/processor.h: Process(..., EntropyOptions)): the same
+ * decoder with its last two passes in their INPUT mode.  The values are QUANTISED, as coded -- no multiplication, so
+ * GZ_SCAN_COEFF_RANGE is left for an AC category above 11 -- and EVERY block of the scan is stored, the MCU padding
+ * included.  total = mcu_cols * mcu_rows * (1, 3 or 6 blocks an MCU); the components lie one after the other, each
+ * [height_in_blocks][width_in_blocks][64] in natural order on its grid padded to whole MCUs: of a 4:2:0 scan
+ * (2 mcu_cols) x (2 mcu_rows) blocks for component 0 and mcu_cols x mcu_rows for the other two, otherwise mcu_cols x
+ * mcu_rows for each (mcu_cols = ceil(w / (8 chroma_factor)), mcu_rows likewise).  A one-component scan stores one
+ * component.
+ * host_coeffs: total * 64 int16 on the host, written only on GZ_SCAN_DECODED; *large_coeff = 1 if CheckJpegSanity would
+ * refuse the stream -- |value * quant[c][k]| > 4096 for any stored coefficient, the padding's included; 4096 passes --
+ * else 0, written only on GZ_SCAN_DECODED.  Arguments, statuses, end_offset, ownership and stream contract are
+ * gz_decode_scan's; GZ_E_ARG also for a NULL host_coeffs or large_coeff. */
+int gz_decode_scan_input(int device, const gz_scan* scan, int16_t* host_coeffs, int* large_coeff, gz_scan_result* result);
 
 /* Image pairs: the butteraugli distance of two images, and its map on the device --------
  * A context compares its original with JPEG candidates of it (gz_compare, below).  These entries compare it with ANY
