@@ -129,6 +129,32 @@ def device_map(ptr, dtype, strides, stream=0):
     return GzDeviceMap(C.sizeof(GzDeviceMap), int(dtype), int(ptr) or None, sy, sx, int(stream) or None)
 
 
+class GzDeviceBatch(C.Structure):
+    """gz_device_batch of include/guetzli_amd.h: n strided images of one size in device memory."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_n", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64), ("stride_c", C.c_int64), ("producer_stream", _P)]
+
+
+def device_batch(ptr, dtype, strides, stream=0):
+    """A GzDeviceBatch: ptr = device address of element (0, 0, 0, 0), dtype = GZ_DT_U8 / F32 / F16 / BF16, strides =
+    (n, y, x, c) in elements, stream = the hipStream_t whose work produced the data (0: none to wait for)."""
+    sn, sy, sx, sc = (int(v) for v in strides)
+    return GzDeviceBatch(C.sizeof(GzDeviceBatch), int(dtype), int(ptr) or None, sn, sy, sx, sc, int(stream) or None)
+
+
+class GzDeviceMapBatch(C.Structure):
+    """gz_device_map_batch of include/guetzli_amd.h: where n distance maps go."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_n", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64), ("consumer_stream", _P)]
+
+
+def device_map_batch(ptr, dtype, strides, stream=0):
+    """A GzDeviceMapBatch: ptr = device address of element (0, 0, 0), dtype = GZ_DT_F32 / F16 / BF16, strides = (n, y, x)
+    in elements, stream = the hipStream_t that used the memory before and reads it afterwards (0: none)."""
+    sn, sy, sx = (int(v) for v in strides)
+    return GzDeviceMapBatch(C.sizeof(GzDeviceMapBatch), int(dtype), int(ptr) or None, sn, sy, sx, int(stream) or None)
+
+
 # name -> (restype, argtypes); mirrors include/guetzli_amd.h one to one
 SIGNATURES = {
     "gz_abi_version": (_I, []),
@@ -171,6 +197,7 @@ SIGNATURES = {
     "gz_compare_device_linear": (_I, [_P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
     "gz_butteraugli_linear": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.c_double, C.c_double, _P]),
     "gz_probe_linear_planes": (_I, [_P, _P]),
+    "gz_butteraugli_batch": (_I, [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, C.c_size_t]),
     "gz_opsin_device": (_I, [_I, _I, _I, _P, _I, C.c_float, _P, _P]),
     "gz_mask_device": (_I, [_I, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P]),
     "gz_adaptive_quantization": (_I, [_I, _I, _I, _P, C.c_float, _P, _P]),
@@ -430,6 +457,16 @@ class Library:
                                                   None if dmap is None else C.byref(dmap), None if heat is None else C.byref(heat),
                                                   good, bad, C.byref(clamped)))
         return float(dist[0]), clamped.value
+
+    def butteraugli_batch(self, ref, other, w, h, n, distances, n_ref=None, maps=None, scratch_bytes=0, device=0):
+        """gz_butteraugli_batch: n pairs of w x h images (device_batch(...); ref holds n_ref = n or 1 images) through one
+        chain.  distances = device address of n float32; maps = device_map_batch(...) or None -> the n distances as a
+        float32 array on the host."""
+        host = np.zeros(n, np.float32)
+        self.check(self.lib.gz_butteraugli_batch(device, w, h, n, C.byref(ref), n if n_ref is None else n_ref, C.byref(other),
+                                                 int(distances) or None, _ptr(host), None if maps is None else C.byref(maps),
+                                                 int(scratch_bytes)))
+        return host
 
     def opsin_device(self, image, w, h, xyb, samples=GZ_SAMPLES_SRGB8, scale=1.0, device=0):
         """gz_opsin_device: OpsinDynamicsImage of `image` (device_pixels(...), read as `samples` say) into `xyb`

@@ -19,7 +19,10 @@ namespace {
 // column pass and fused kernels, 64-row tiles, the epilogue without 16-byte accesses and the row
 // pass with LDS bank conflicts (GZ_BLUR_OPT), the three-plane LF passes, the unpaired mask blurs.
 // Every dispatcher and stage below launches on the stream it is given.
+// A batched chain (c->batch.n > 0, entry_batch.h) has ONE configuration, whatever the context's gz_config says: the
+// unpacked passes and 16-row tiles everywhere -- what an image under 1.5 MPix gets by default.
 static bool packed_blur(const gz_ctx* c) {
+  if (c->batch.n) return false;
   if (c->cfg.blur_packed >= 0) return c->cfg.blur_packed != 0;
   // (round 5, with 16-row tiles: 1080p 0.3356 -> 0.3290 ms, 2560 x 1440 0.487 -> 0.466, 3200 x 1800 0.719 -> 0.684;
   // 720p equal -- profiles/r05_chain_experiments.log, section 8)
@@ -28,6 +31,7 @@ static bool packed_blur(const gz_ctx* c) {
 constexpr int kTileRows = 32;
 constexpr int kSmallTileRows = 16;
 static bool small_tiles(const gz_ctx* c) {
+  if (c->batch.n) return true;
   if (c->cfg.tile_rows == 16) return true;
   if (c->cfg.tile_rows == 32) return false;
   // (round 5: 16-row tiles win or tie up to 3200 x 1800 -- 1080p chain 0.343 -> 0.330 ms, sixteen 1080p images
@@ -37,10 +41,15 @@ static bool small_tiles(const gz_ctx* c) {
 
 // PAIR (with `second`): two blurs of equal radius and different sigma on two independent planes as ONE launch per
 // pass (grid z = plane; plane 1 takes the second tap set): the mask's radius-20 pair (butteraugli.cc:1780-1790).
-template <int R, class Src, int NC, bool PAIR = false>
+// MAYBATCH (all three dispatchers): the Compare chain's calls, which a batched chain makes too -- c->batch.n images per
+// launch, the image index in the grid's z (gz_common.h, BatchIdx).  false (blur_plane: the probes) carries no batched
+// instantiation.
+static int no_batched_form(gz_ctx* c) { c->err = "this launch has no batched form"; return GZ_E_STATE; }
+template <int R, class Src, int NC, bool PAIR = false, bool MAYBATCH = true>
 int blur_h(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const PlanePack<NC>& dst,
            const BlurCfg& cfg, const BlurCfg* second = nullptr) {
   if (PAIR != (second != nullptr)) { c->err = "blur pair mismatch"; return GZ_E_STATE; }
+  if (!MAYBATCH && c->batch.n) return no_batched_form(c);
   const BlurCfg& cfg1 = PAIR ? *second : cfg;
   if (cfg.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
   const Taps<R> t0 = taps_of<R>(cfg), t1 = taps_of<R>(cfg1);
@@ -51,16 +60,26 @@ int blur_h(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const Pla
     GZ_LAUNCH((k_blur_h_pk<R, Src, NC, PAIR>), grid, dim3(256), stream, src, dst, w, h, pitch, t0, b0, t1, b1);
   } else {
     dim3 grid(gz_div_up(c->w, HW), gz_div_up(c->h, HH), NC);
+    if constexpr (MAYBATCH) {
+      if (c->batch.n) {
+        grid.z *= c->batch.n;
+        const BatchIdx bi = c->batch.idx;
+        GZ_LAUNCH((k_blur_h<R, Src, NC, PAIR, BatchIdx>), grid, dim3(256), stream, src, dst, w, h, pitch, t0, b0, t1, b1, bi);
+        KCHK(c);
+        return GZ_OK;
+      }
+    }
     GZ_LAUNCH((k_blur_h<R, Src, NC, PAIR>), grid, dim3(256), stream, src, dst, w, h, pitch, t0, b0, t1, b1);
   }
   KCHK(c);
   return GZ_OK;
 }
 
-template <int R, int NC, class Post, bool PAIR = false>
+template <int R, int NC, class Post, bool PAIR = false, bool MAYBATCH = true>
 int blur_v(gz_ctx* c, hipStream_t stream, const CPlanePack<NC>& src, const Post& post, const BlurCfg& cfg,
            const BlurCfg* second = nullptr) {
   if (PAIR != (second != nullptr)) { c->err = "blur pair mismatch"; return GZ_E_STATE; }
+  if (!MAYBATCH && c->batch.n) return no_batched_form(c);
   const BlurCfg& cfg1 = PAIR ? *second : cfg;
   if (cfg.r != R || cfg1.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
   const Taps<R> t0 = taps_of<R>(cfg), t1 = taps_of<R>(cfg1);
@@ -68,6 +87,15 @@ int blur_v(gz_ctx* c, hipStream_t stream, const CPlanePack<NC>& src, const Post&
   const int w = c->w, h = c->h, pitch = c->pitch;
   const bool small = small_tiles(c);
   dim3 grid(gz_div_up(c->w, VW), gz_div_up(c->h, small ? kSmallTileRows : kTileRows), PAIR ? 2 : 1);
+  if constexpr (MAYBATCH) {
+    if (c->batch.n) {   // (unpacked, 16-row tiles: packed_blur, small_tiles)
+      grid.z *= c->batch.n;
+      const BatchIdx bi = c->batch.idx;
+      GZ_LAUNCH((k_blur_v_compact<R, NC, Post, kSmallTileRows, PAIR, BatchIdx>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1, bi);
+      KCHK(c);
+      return GZ_OK;
+    }
+  }
   if (packed_blur(c)) {
     if (small) GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kSmallTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
     else GZ_LAUNCH((k_blur_v_pk<R, NC, Post, kTileRows, PAIR>), grid, dim3(256), stream, src, post, w, h, pitch, t0, b0, t1, b1);
@@ -82,10 +110,12 @@ int blur_v(gz_ctx* c, hipStream_t stream, const CPlanePack<NC>& src, const Post&
 // BM = true (the chain's last blur): the Post functor's results are also reduced to the per-block
 // maxima and the image maximum; that kernel keeps its results in registers (always 32-row tiles).
 // bm.tiles + n_tiles: the listed tiles only (tile ids of the grid this function would launch).
-template <int R, int NC, class Src, class Post, bool BM = false>
+// A batched launch: no tile list and no block maxima; bm.image_max_bits is the first of c->batch.n words, one per image.
+template <int R, int NC, class Src, class Post, bool BM = false, bool MAYBATCH = true>
 int blur2d(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const Post& post, const BlurCfg& cfg,
            BlockMaxOut bm = BlockMaxOut{nullptr, nullptr, 0, nullptr}, int n_tiles = 0) {
   if (cfg.r != R) { c->err = "blur radius mismatch"; return GZ_E_STATE; }
+  if (c->batch.n && (!MAYBATCH || bm.tiles || bm.block_max)) return no_batched_form(c);
   const Taps<R> tp = taps_of<R>(cfg);
   const BorderScale bx = cfg.bx, by = cfg.by;
   const int w = c->w, h = c->h, pitch = c->pitch;
@@ -94,6 +124,15 @@ int blur2d(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const Pos
   // (a tile list: always the 16-row tiles -- a handful of workgroups, whose time is one workgroup's latency)
   const bool small = bm.tiles || (BM ? small_tiles(c) && (size_t)c->w * c->h < 1500000 : small_tiles(c));
   const dim3 grid = bm.tiles ? dim3(n_tiles) : dim3(gz_div_up(c->w, T2), gz_div_up(c->h, small ? kSmallTileRows : kTileRows));
+  if constexpr (MAYBATCH) {
+    if (c->batch.n) {   // (16-row tiles, the last blur included: small_tiles, and a batch's images are under 1.5 MPix)
+      const dim3 bgrid(grid.x, grid.y, c->batch.n);
+      const BatchIdx bi = c->batch.idx;
+      GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kSmallTileRows, BatchIdx>), bgrid, dim3(256), stream, src, post, w, h, pitch, tp, bx, by, bm, bi);
+      KCHK(c);
+      return GZ_OK;
+    }
+  }
   if (small) GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kSmallTileRows>), grid, dim3(256), stream, src, post, w, h, pitch, tp, bx, by, bm);
   else GZ_LAUNCH((k_blur2d<R, NC, Src, Post, BM, kTileRows>), grid, dim3(256), stream, src, post, w, h, pitch, tp, bx, by, bm);
   KCHK(c);
@@ -108,12 +147,12 @@ int blur2d(gz_ctx* c, hipStream_t stream, const SrcPack<Src, NC>& src, const Pos
 template <int R, class Post>
 int blur_plane_r(gz_ctx* c, hipStream_t stream, const SrcPack<SrcPlain, 1>& src, float* tmp, const Post& post, const BlurCfg& cfg) {
   if constexpr (R < 16) {
-    return blur2d<R, 1, SrcPlain, Post>(c, stream, src, post, cfg);
+    return blur2d<R, 1, SrcPlain, Post, false, false>(c, stream, src, post, cfg);
   } else {
     PlanePack<1> t; CPlanePack<1> ct;
     t.p[0] = tmp; ct.p[0] = tmp;
-    TRY((blur_h<R, SrcPlain, 1>(c, stream, src, t, cfg)));
-    return blur_v<R, 1, Post>(c, stream, ct, post, cfg);
+    TRY((blur_h<R, SrcPlain, 1, false, false>(c, stream, src, t, cfg)));
+    return blur_v<R, 1, Post, false, false>(c, stream, ct, post, cfg);
   }
 }
 template <class Post>
@@ -272,7 +311,12 @@ int stage_separate(gz_ctx* c, const ChainStreams& cs, Psycho* ps) {
 // whatever is queued there (the SameNoise blur, the shorter of the two side branches).
 int stage_mask_blurs(gz_ctx* c, hipStream_t stream, hipStream_t small_stream, const MaskPrePack& pk) {
   dim3 grid(gz_div_up(c->w, 1024), c->h, 2);
-  GZ_LAUNCH(k_mask_pre, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
+  if (c->batch.n) {
+    grid.z *= c->batch.n;
+    GZ_LAUNCH((k_mask_pre<BatchIdx>), grid, dim3(256), stream, pk, c->w, c->h, c->pitch, c->batch.idx);
+  } else {
+    GZ_LAUNCH(k_mask_pre, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
+  }
   KCHK(c);
   TRY(fork(c, stream, small_stream, c->ev_mask_pre));
   {
@@ -308,7 +352,12 @@ int stage_mask_sup(gz_ctx* c, hipStream_t stream, const MaskIn in[2], float* con
   MaskSupPack pk;
   for (int i = 0; i < 2; ++i) { pk.in[i] = in[i]; pk.out[i] = out[i]; }
   dim3 grid(gz_div_up(c->w, 1024), c->h, 2);
-  GZ_LAUNCH(k_mask_sup, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
+  if (c->batch.n) {
+    grid.z *= c->batch.n;
+    GZ_LAUNCH((k_mask_sup<BatchIdx>), grid, dim3(256), stream, pk, c->w, c->h, c->pitch, c->batch.idx);
+  } else {
+    GZ_LAUNCH(k_mask_sup, grid, dim3(256), stream, pk, c->w, c->h, c->pitch);
+  }
   KCHK(c);
   return GZ_OK;
 }
@@ -354,7 +403,12 @@ static CombineArgs combine_mask_args(const gz_ctx* c, float* const mask_out[3], 
 }
 static int launch_combine(gz_ctx* c, hipStream_t stream, const CombineArgs& a) {
   dim3 grid(gz_div_up(c->w, 1024), c->h);   // (4 pixels per thread)
-  GZ_LAUNCH(k_combine, grid, dim3(256), stream, a, c->w, c->h, c->pitch);
+  if (c->batch.n) {
+    grid.z = c->batch.n;
+    GZ_LAUNCH((k_combine<BatchIdx>), grid, dim3(256), stream, a, c->w, c->h, c->pitch, c->batch.idx);
+  } else {
+    GZ_LAUNCH(k_combine, grid, dim3(256), stream, a, c->w, c->h, c->pitch);
+  }
   KCHK(c);
   return GZ_OK;
 }
@@ -406,7 +460,13 @@ int stage_diffmap(gz_ctx* c, const ChainStreams& cs, const Psycho& p0, const Psy
     a.pass[2] = {p0.mf[ch], p1.mf[ch], ms[ch][2].nm, ms[ch][2].lf};
     a.out = c->ac[ch];
   }
-  GZ_LAUNCH((k_malta_rolled<3>), mgrid, dim3(256), cs.main, ay, ax, c->w, c->h, c->pitch);
+  if (!c->batch.n) {
+    GZ_LAUNCH((k_malta_rolled<3>), mgrid, dim3(256), cs.main, ay, ax, c->w, c->h, c->pitch);
+  } else {
+    mgrid.z *= c->batch.n;
+    const BatchIdx bi = c->batch.idx;
+    GZ_LAUNCH((k_malta_rolled_batch<3>), mgrid, dim3(256), cs.main, ay, ax, c->w, c->h, c->pitch, bi);
+  }
   KCHK(c);
   TRY(wait_for(c, cs.side, cs.main, c->ev_join));
   TRY(wait_for(c, cs.side2, cs.main, c->ev_join2));
@@ -429,8 +489,10 @@ int stage_diffmap(gz_ctx* c, const ChainStreams& cs, const Psycho& p0, const Psy
   {  // CalculateDiffmap second half: blur(sigma 1.725, border_ratio 1.0) + mix
     SrcPack<SrcPlain, 1> s; s.s[0].p = c->dsq;
     PostDiffmapMix post; post.d = c->dsq; post.out = (want & kWantDistmap) ? c->distmap : nullptr;
-    if (clear == ClearMax::kMemset) HIPCHK(c, hipMemsetAsync(c->d_max_bits, 0, sizeof(unsigned), cs.main));
-    BlockMaxOut bm{(want & kWantBlockMax) ? c->d_block_max : nullptr, c->d_max_bits, c->bw, nullptr};
+    // (a batched chain: one image-maximum word per image, c->batch.max_bits, and no block maxima)
+    unsigned* const max_bits = c->batch.n ? c->batch.max_bits : c->d_max_bits;
+    if (clear == ClearMax::kMemset) HIPCHK(c, hipMemsetAsync(max_bits, 0, sizeof(unsigned) * (size_t)std::max(1, c->batch.n), cs.main));
+    BlockMaxOut bm{(want & kWantBlockMax) ? c->d_block_max : nullptr, max_bits, c->bw, nullptr};
     TRY((blur2d<3, 1, SrcPlain, PostDiffmapMix, true>(c, cs.main, s, post, c->blur[B_FINAL], bm)));
   }
   return GZ_OK;

@@ -339,6 +339,10 @@ struct gz_ctx {
 
   float* arena = nullptr;
   float* extra_arena = nullptr;   // probe-only planes (ensure_pip)
+  // A batched chain (entry_batch.h; n == 0: none, the state of every context the other entries make).  The context's plane
+  // pointers are then image 0's of n arenas laid out back to back, and every launch of the chain's dispatchers (chain.h)
+  // covers the n images: idx moves the kernels' pointers, max_bits are the n image-maximum words.
+  struct Batch { int n = 0; BatchIdx idx = {0, 0}; unsigned* max_bits = nullptr; } batch;
   std::vector<float*> free_planes;
   BlurCfg blur[B_COUNT];
 
@@ -572,6 +576,9 @@ static int result_buffer(gz_ctx* c, size_t bytes, void** out) {
 }
 
 const int kNumPlanes = 9 + 9 + 3 + 3 + 3 + 2 + 2 + 10 + 2;   // pi0, pi1, lin, tmp, xyb, lf_raw, hfp, 10 singles, sup0[2]
+// Floats from one image's arena to the next in a batched context: the planes, rounded up to a multiple of 4 floats (an
+// image's planes are then 16-byte aligned exactly where image 0's are).
+inline size_t batch_arena_stride(size_t plane) { return (plane * kNumPlanes + 3) & ~(size_t)3; }
 
 // A new frame layout: the candidate, the search and whatever was pending or kept belonged to the old one (a stale
 // gz_order_build_auto_end / gz_order_descend_end / gz_compare_end / gz_jpeg_scan_end must fail, not return its data).

@@ -236,7 +236,7 @@ struct LinearSource;
 static int check_linear_pointer(int device, const LinearSource* src, std::string* why);
 static int set_linear_device(gz_ctx* c, const LinearSource* src);
 static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err,
-                              const LinearSource* linear = nullptr);
+                              const LinearSource* linear = nullptr, int batch_arenas = 0);
 gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
   int prev = -1;
   if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
@@ -265,12 +265,15 @@ gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* i
 }
 // The original from host pixels (rgb), from a device-resident image (img, checked by the caller) or from a linear float
 // image (linear, checked by the caller; w x h is then the canvas it is extended to): one of the three.
+// Or none of them, with batch_arenas > 0 (entry_batch.h): a context without an original, whose arena is that many images'
+// arenas back to back (batch_arena_stride() apart) and, behind them, one result word per image -- one allocation.  Its
+// plane pointers are the first arena's; the coefficient buffers, which nothing of a pixel comparison touches, stay empty.
 static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err,
-                              const LinearSource* linear) {
+                              const LinearSource* linear, int batch_arenas) {
   int dummy;
   if (!err) err = &dummy;
   *err = GZ_OK;
-  if ((!rgb && !img && !linear) || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
+  if ((!rgb && !img && !linear && batch_arenas <= 0) || w < 8 || h < 8 || w >= (1 << 16) || h >= (1 << 16)) { *err = GZ_E_ARG; return nullptr; }
   // coefficient positions (3 x blocks x 64) and candidate offsets (blocks x 189) are 32-bit
   // on both sides of the ABI: 11.18 M blocks = 715 MPix is the largest image (tested: 268 MPix)
   if ((uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8) * 192u > 0x7fffffffull) { *err = GZ_E_ARG; return nullptr; }
@@ -317,13 +320,15 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
   }
   for (hipEvent_t* e : {&c->ev_candidate, &c->ev_fork, &c->ev_join, &c->ev_join2, &c->ev_mask_pre, &c->ev_next_cand, &c->ev_xyb, &c->ev_lfy})
     if (const int rc = own_event(c, e)) return fail(rc);
-  const size_t ncoef = (size_t)3 * c->nb * 64;
+  const size_t ncoef = batch_arenas > 0 ? 1 : (size_t)3 * c->nb * 64;
+  const size_t arena_bytes = batch_arenas > 0 ? (sizeof(float) * batch_arena_stride(c->plane) + sizeof(unsigned)) * (size_t)batch_arenas
+                                              : sizeof(float) * c->plane * kNumPlanes;
   if (const int rc = regrow(c, nullptr, nullptr, 0,
                             {{(void**)&c->d_rgb, (size_t)3 * w * h}, {(void**)&c->d_orig, ncoef * 2}, {(void**)&c->d_cand, ncoef * 2},
                              {(void**)&c->d_q, sizeof(int) * 192}, {(void**)&c->d_srgb_lut, sizeof(float) * 256},
                              {(void**)&c->d_mask_luts, sizeof(double) * 2048}, {(void**)&c->d_block_max, sizeof(float) * c->nb},
                              {(void**)&c->d_max_bits, sizeof(unsigned) * gz_ctx::kResultWords}, {(void**)&c->d_srgb_out, (size_t)3 * w * h},
-                             {(void**)&c->arena, sizeof(float) * c->plane * kNumPlanes}}))
+                             {(void**)&c->arena, arena_bytes}}))
     return fail(rc);
   for (int i = kNumPlanes - 1; i >= 0; --i) c->free_planes.push_back(c->arena + (size_t)i * c->plane);
   alloc_psycho(c, &c->pi0);
@@ -362,7 +367,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
     if (rc != GZ_OK) return fail(rc);
     if (c->blur[b].r != kBlurSpecs[b].r) return fail(GZ_E_STATE);
   }
-  {
+  if (linear || img || rgb) {
     const int rc = linear ? set_linear_device(c, linear) : img ? set_rgb_device(c, img) : gz_set_rgb(c, rgb);
     if (rc != GZ_OK) return fail(rc);
   }

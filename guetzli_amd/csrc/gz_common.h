@@ -239,3 +239,33 @@ GZ_DEVFN GzTile gz_xcd_tile() {
   o.z = t / (gx * gy);
   return o;
 }
+
+// ---- batched launches (api/entry_batch.h) ------------------------------------------------
+// One launch over N images of one size: the kernels of a pixel-pair comparison take a trailing parameter PACK, empty
+// in every launch of one image -- that instantiation is the kernel as it was, argument for argument -- and ONE
+// BatchIdx in the batched form.  There the grid carries the image index, image-major: gridDim.z = N x the planes of
+// the launch (gz_xcd_tile()'s z), or N alone in the kernels whose grid is flat; gz_batch_image() splits it off, and
+// every plane pointer of the launch moves by image x stride floats before its first use (the gz_batch_shift overloads
+// beside the argument structs).  Two strides: the per-image arena's (scratch and the distorted image's planes; a
+// multiple of 4 floats, so that the 16-byte paths' alignment conditions hold for image i exactly when they hold for
+// image 0), and the reference's planes' -- 0 when one reference is compared with N images.  Tables do not move.
+struct BatchIdx {
+  size_t stride;       // floats between two images' arenas
+  size_t ref_stride;   // floats between two images' reference planes (pi0, sup0); 0: one reference for all
+};
+// The same for the two kernels at the caller's tensors (k_ingest_rgb, k_emit_map; flat grids: gridDim.y = N): image i
+// of the tensor starts stride_n ELEMENTS behind image i - 1, its planes plane_stride floats behind.
+struct BatchTensor {
+  long long stride_n;
+  size_t plane_stride;
+};
+template <class P>
+GZ_DEVFN void gz_batch_move(P*& p, size_t off) {
+  if (p) p += off;
+}
+// The image of this workgroup; z becomes the plane index of a launch of one image.  planes = gridDim.z of that launch.
+GZ_DEVFN int gz_batch_image(GzTile* t, int planes) {
+  const int img = t->z / planes;
+  t->z -= img * planes;
+  return img;
+}

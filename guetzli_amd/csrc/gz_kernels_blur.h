@@ -72,6 +72,32 @@ template <int NC>
 struct CPlanePack {
   const float* p[NC];
 };
+// The batched launches (gz_common.h, BatchIdx): every plane pointer of an argument struct moves to image `img`.  Of the
+// sources only SrcSameNoise reads the reference (its `a`: pi0's HF-Y), which moves by the reference's stride.
+GZ_DEVFN void gz_batch_shift(SrcPlain& s, int img, const BatchIdx& b) { gz_batch_move(s.p, img * b.stride); }
+GZ_DEVFN void gz_batch_shift(SrcDiff& s, int img, const BatchIdx& b) {
+  gz_batch_move(s.a, img * b.stride);
+  gz_batch_move(s.b, img * b.stride);
+}
+GZ_DEVFN void gz_batch_shift(SrcSameNoise& s, int img, const BatchIdx& b) {
+  gz_batch_move(s.a, img * b.ref_stride);
+  gz_batch_move(s.b, img * b.stride);
+}
+template <class Src, int NC>
+GZ_DEVFN void gz_batch_shift(SrcPack<Src, NC>& s, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int i = 0; i < NC; ++i) gz_batch_shift(s.s[i], img, b);
+}
+template <int NC>
+GZ_DEVFN void gz_batch_shift(PlanePack<NC>& s, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int i = 0; i < NC; ++i) gz_batch_move(s.p[i], img * b.stride);
+}
+template <int NC>
+GZ_DEVFN void gz_batch_shift(CPlanePack<NC>& s, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int i = 0; i < NC; ++i) gz_batch_move(s.p[i], img * b.stride);
+}
 
 // ------------------------------------------------------------------------ row pass --
 // grid = (ceil(w/HW), ceil(h/HH), NC); block = 256 threads; thread = one x, HH rows.
@@ -80,15 +106,22 @@ constexpr int HH = 4;
 
 // TWO = true (NC == 2): the second plane has its own taps and border scales (taps1, bs1) -- two
 // blurs of different sigma but equal radius in one launch (the mask's radius-20 pair).
-template <int R, class Src, int NC, bool TWO = false>
+// B... (empty, or one BatchIdx: gz_common.h): the batched form, grid z = image x NC + plane.
+template <int R, class Src, int NC, bool TWO = false, class... B>
 __global__ __launch_bounds__(256) void k_blur_h(SrcPack<Src, NC> src, PlanePack<NC> dst,
                                                 int w, int h, int pitch, Taps<R> taps0,
-                                                BorderScale bs0, Taps<R> taps1, BorderScale bs1) {
+                                                BorderScale bs0, Taps<R> taps1, BorderScale bs1, B... batch) {
   constexpr int RA = (R + 3) & ~3;      // halo rounded up to whole 16-byte vectors
   constexpr int TP = HW + 2 * RA;       // staged columns (multiple of 4)
   constexpr int OFF = RA - R;
   __shared__ __attribute__((aligned(16))) float tile[HH][TP];
-  const GzTile bid = gz_xcd_tile();
+  GzTile bid_ = gz_xcd_tile();
+  if constexpr (sizeof...(B) > 0) {
+    const int img = gz_batch_image(&bid_, NC);
+    gz_batch_shift(src, img, batch...);
+    gz_batch_shift(dst, img, batch...);
+  }
+  const GzTile bid = bid_;
   const int c = bid.z;
   // constant indices into the kernel arguments (a dynamic one would make the pointers generic)
   Src s = src.s[0];
@@ -393,17 +426,24 @@ GZ_DEVFN void block_max_from_half_columns(const float* res, int tx, int tg, int 
 
 // ZCH = true (NC == 2, Post = PostStore<2>): the two planes are independent blurs with their own
 // taps (taps1 / bs1 for the second); the grid's z index picks the plane, each workgroup does one.
-template <int R, int NC, class Post, int TH, bool ZCH = false>
+// B... (empty, or one BatchIdx: gz_common.h): the batched form, grid z = image x (ZCH ? 2 : 1) + plane.
+template <int R, int NC, class Post, int TH, bool ZCH = false, class... B>
 __global__ __launch_bounds__(256) void k_blur_v_compact(CPlanePack<NC> src, Post post, int w, int h,
                                                 int pitch, Taps<R> taps0, BorderScale bs0,
-                                                Taps<R> taps1, BorderScale bs1) {
+                                                Taps<R> taps1, BorderScale bs1, B... batch) {
   // TH = tile height (32, or 16 for small images: twice the workgroups to fill the chip)
   constexpr int VHt = TH, VPTt = TH / 4;
   constexpr int NCL = ZCH ? 1 : NC;   // planes per workgroup
   static_assert(!ZCH || NC == 2, "independent planes: two of them");
   __shared__ __attribute__((aligned(16))) float tile[VHt + 2 * R][VW];
   const int tx = threadIdx.x & 63, tg = threadIdx.x >> 6;
-  const GzTile bid = gz_xcd_tile();
+  GzTile bid_ = gz_xcd_tile();
+  if constexpr (sizeof...(B) > 0) {
+    const int img = gz_batch_image(&bid_, ZCH ? 2 : 1);
+    gz_batch_shift(src, img, batch...);
+    gz_batch_shift(post, img, batch...);
+  }
+  const GzTile bid = bid_;
   const Taps<R>& taps = (ZCH && bid.z == 1) ? taps1 : taps0;
   const BorderScale& bs = (ZCH && bid.z == 1) ? bs1 : bs0;
   const int x0 = bid.x * VW, y0 = bid.y * VHt;
@@ -672,10 +712,12 @@ constexpr int T2 = 64;   // tile edge
 // (256, 4): registers for four wavefronts per SIMD -- the MF instance (PostMF's quad epilogue) took
 // 143 VGPRs = three per SIMD without the bound; 1080p chain 0.358-0.362 -> 0.350 ms, 4K -0.4 %
 // (profiles/r04_occupancy_experiments.log; five per SIMD: no further gain).
-template <int R, int NC, class Src, class Post, bool BM, int TH>
+// B... (empty, or one BatchIdx: gz_common.h): the batched form, grid z = image; the image maximum of image i goes to
+// word i of bm.image_max_bits (no block maxima, no tile list there).
+template <int R, int NC, class Src, class Post, bool BM, int TH, class... B>
 __global__ __launch_bounds__(256, 4) void k_blur2d(SrcPack<Src, NC> src, Post post, int w, int h,
                                                 int pitch, Taps<R> taps, BorderScale bsx,
-                                                BorderScale bsy, BlockMaxOut bm) {
+                                                BorderScale bsy, BlockMaxOut bm, B... batch) {
   constexpr bool ROLL = !BM;
   constexpr int RA = (R + 3) & ~3;
   constexpr int IW = T2 + 2 * RA;   // staged columns, multiple of 4
@@ -690,6 +732,12 @@ __global__ __launch_bounds__(256, 4) void k_blur2d(SrcPack<Src, NC> src, Post po
     bid.x = t % gx; bid.y = t / gx; bid.z = 0;
   } else {
     bid = gz_xcd_tile();
+  }
+  if constexpr (sizeof...(B) > 0) {
+    const int img = gz_batch_image(&bid, 1);
+    gz_batch_shift(src, img, batch...);
+    gz_batch_shift(post, img, batch...);
+    bm.image_max_bits += img;
   }
   const int x0 = bid.x * T2, y0 = bid.y * TH;
   const bool interior = x0 >= RA && x0 + T2 + RA <= w && y0 >= R && y0 + TH + R <= h &&
@@ -1140,6 +1188,44 @@ struct PostDiffmapMix {
     for (int i = 0; i < 4; ++i) { float one[1] = {v[0].v[i]}; (void)(*this)(idx + i, one); }
   }
 };
+
+// The batched launches (gz_common.h, BatchIdx): the functors' planes are all per-image ones -- a launch whose functor
+// writes the reference's planes (the reference pass) runs with the arena's stride for both.
+template <int NC>
+GZ_DEVFN void gz_batch_shift(PostStore<NC>& p, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gz_batch_move(p.out[c], img * b.stride);
+}
+GZ_DEVFN void gz_batch_shift(PostOpsin& p, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { gz_batch_move(p.lin[c], img * b.stride); gz_batch_move(p.xyb[c], img * b.stride); }
+}
+GZ_DEVFN void gz_batch_shift(PostLFxy& p, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) { gz_batch_move(p.lf_raw[c], img * b.stride); gz_batch_move(p.lf_vals[c], img * b.stride); }
+}
+GZ_DEVFN void gz_batch_shift(PostLFb& p, int img, const BatchIdx& b) {
+  gz_batch_move(p.lf_raw_y, img * b.stride);
+  gz_batch_move(p.lf_vals_b, img * b.stride);
+}
+GZ_DEVFN void gz_batch_shift(PostMF& p, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    gz_batch_move(p.xyb[c], img * b.stride); gz_batch_move(p.lf_raw[c], img * b.stride);
+    gz_batch_move(p.mf[c], img * b.stride); gz_batch_move(p.hf_pre[c], img * b.stride);
+  }
+}
+GZ_DEVFN void gz_batch_shift(PostHF& p, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    gz_batch_move(p.hf_pre[c], img * b.stride); gz_batch_move(p.hf[c], img * b.stride); gz_batch_move(p.uhf[c], img * b.stride);
+  }
+  gz_batch_move(p.lf_raw_y, img * b.stride);
+}
+GZ_DEVFN void gz_batch_shift(PostDiffmapMix& p, int img, const BatchIdx& b) {
+  gz_batch_move(p.d, img * b.stride);
+  gz_batch_move(p.out, img * b.stride);   // (may be null: stays null)
+}
 
 // Mask Y blur pair (butteraugli.cc:1780-1790): v[0] = blur(diffY, r0=2.377) arrives from
 // an earlier pass in `b1`; this one (sigma r1) combines them.  Kept as plain stores: the

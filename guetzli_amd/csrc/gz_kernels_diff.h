@@ -77,8 +77,31 @@ GZ_DEVFN MaskQuad mask_quad(const MaskIn& a, int x, int y, int w, int h, int pit
 // the row and of the row below, one 16-byte store -- when the row pitch allows it.  Rows in
 // XCD-aware order: row y + 1 (read by this row's workgroups and by the next row's) then comes
 // from the same L2.
-__global__ __launch_bounds__(256) void k_mask_sup(MaskSupPack pk, int w, int h, int pitch) {
-  const GzTile bid = gz_xcd_tile();
+// B... (empty, or one BatchIdx: gz_common.h) in both kernels: the batched form, grid z = image x 2 + plane.  The planes of
+// a MaskSupPack are one image's own (the reference pass runs with the arena's stride); of a MaskPrePack sup0 is the
+// reference's.
+GZ_DEVFN void gz_batch_shift(MaskIn& m, int img, const BatchIdx& b) {
+  gz_batch_move(m.uhf, img * b.stride);   // (may be null: stays null)
+  gz_batch_move(m.hf, img * b.stride);
+}
+GZ_DEVFN void gz_batch_shift(MaskSupPack& pk, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) { gz_batch_shift(pk.in[i], img, b); gz_batch_move(pk.out[i], img * b.stride); }
+}
+GZ_DEVFN void gz_batch_shift(MaskPrePack& pk, int img, const BatchIdx& b) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    gz_batch_move(pk.sup0[i], img * b.ref_stride);
+    gz_batch_shift(pk.in1[i], img, b);
+    gz_batch_move(pk.out[i], img * b.stride);
+  }
+}
+
+template <class... B>
+__global__ __launch_bounds__(256) void k_mask_sup(MaskSupPack pk, int w, int h, int pitch, B... batch) {
+  GzTile bid_ = gz_xcd_tile();
+  if constexpr (sizeof...(B) > 0) gz_batch_shift(pk, gz_batch_image(&bid_, 2), batch...);
+  const GzTile bid = bid_;
   const int x = (bid.x * (int)blockDim.x + (int)threadIdx.x) * 4, y = bid.y;
   if (x >= w || y >= h) return;
   const int c = bid.z;
@@ -102,8 +125,11 @@ __global__ __launch_bounds__(256) void k_mask_sup(MaskSupPack pk, int w, int h, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_mask_pre(MaskPrePack pk, int w, int h, int pitch) {
-  const GzTile bid = gz_xcd_tile();
+template <class... B>
+__global__ __launch_bounds__(256) void k_mask_pre(MaskPrePack pk, int w, int h, int pitch, B... batch) {
+  GzTile bid_ = gz_xcd_tile();
+  if constexpr (sizeof...(B) > 0) gz_batch_shift(pk, gz_batch_image(&bid_, 2), batch...);
+  const GzTile bid = bid_;
   const int x = (bid.x * (int)blockDim.x + (int)threadIdx.x) * 4, y = bid.y;
   if (x >= w || y >= h) return;
   const int c = bid.z;
@@ -192,76 +218,17 @@ struct MaltaArgs {
 template <int NPASS>
 __global__ __launch_bounds__(256, 8) void k_malta_rolled(MaltaArgs<NPASS> a0, MaltaArgs<NPASS> a1, int w,
                                                int h, int pitch) {
-  const GzTile bid = gz_xcd_tile();
-  const MaltaArgs<NPASS>& a = bid.z ? a1 : a0;
-  __shared__ __attribute__((aligned(16))) float tile[MH + 8][MW + 8];
-  const int tx = threadIdx.x & 63, tg = threadIdx.x >> 6;
-  const int x0 = bid.x * MW, y0 = bid.y * MH;
-  __shared__ float accs[MPT][256];
-#pragma unroll
-  for (int i = 0; i < MPT; ++i) accs[i][threadIdx.x] = 0.0f;   // (own slots: no barrier needed)
-  // the haloed tile starts at x0 - 4: rows can be staged with aligned 16-byte loads when the
-  // tile lies inside the image horizontally and the pitch allows it
-  const bool vec = x0 >= 4 && x0 + MW + 4 <= w && (pitch & 3) == 0;
-  for (int ps = 0; ps < NPASS; ++ps) {
-    const MaltaPass P = a.pass[ps];
-    // the pass's three constants in vector registers: malta_diff adds / multiplies them into every
-    // staged sample, and a scalar-register operand makes those 4-cycle instructions (GZ_IN_VGPR)
-    MaltaNorm nm = P.nm;
-    nm.norm1f = GZ_IN_VGPR(nm.norm1f);
-    nm.norm2_0gt1 = GZ_IN_VGPR(nm.norm2_0gt1);
-    nm.norm2_0lt1 = GZ_IN_VGPR(nm.norm2_0lt1);
-    if (ps > 0) __syncthreads();
-    if (vec) {
-      constexpr int NV = (MH + 8) * ((MW + 8) / 4);   // 16-byte vectors in the tile
-#pragma unroll 1
-      for (int k = 0; k < (NV + 255) / 256; ++k) {
-        const int i = 256 * k + (int)threadIdx.x;
-        if (i < NV) {
-          const int ry = i / ((MW + 8) / 4), q = i - ry * ((MW + 8) / 4);
-          const int y = y0 - 4 + ry;
-          gz_f4 v;
-          v.v[0] = v.v[1] = v.v[2] = v.v[3] = 0.0f;
-          if (y >= 0 && y < h) {
-            const size_t idx = (size_t)y * pitch + (x0 - 4 + 4 * q);
-            const gz_f4 u0 = GZ_LDG4(P.p0, idx), u1 = GZ_LDG4(P.p1, idx);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v.v[e] = malta_diff(u0.v[e], u1.v[e], nm);
-          }
-          *reinterpret_cast<gz_f4*>(&tile[ry][4 * q]) = v;
-        }
-      }
-    } else {
-      for (int i = threadIdx.x; i < (MH + 8) * (MW + 8); i += 256) {
-        const int ry = i / (MW + 8), rx = i - ry * (MW + 8);
-        const int x = x0 - 4 + rx, y = y0 - 4 + ry;
-        float v = 0.0f;
-        if (x >= 0 && x < w && y >= 0 && y < h) {
-          const size_t idx = (size_t)y * pitch + x;
-          v = malta_diff(GZ_LDG(P.p0, idx), GZ_LDG(P.p1, idx), nm);
-        }
-        tile[ry][rx] = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int i = 0; i < MPT; ++i) {
-      const int ly = tg * MPT + i;
-      const float r = P.lf ? malta_unit<true>(tile, ly + 4, tx + 4)
-                           : malta_unit<false>(tile, ly + 4, tx + 4);
-      accs[i][threadIdx.x] += r;
-    }
-  }
-  const int x = x0 + tx;
-  if (x >= w) return;
-#pragma unroll
-  for (int i = 0; i < MPT; ++i) {
-    const int y = y0 + tg * MPT + i;
-    if (y >= h) break;
-    const size_t idx = (size_t)y * pitch + x;
-    const float v = accs[i][threadIdx.x];
-    GZ_STG(a.out, idx, v);
-  }
+#define GZ_MALTA_BATCHED 0
+#include "gz_kernels_malta_body.inc"
+#undef GZ_MALTA_BATCHED
+}
+// The batched form (gz_common.h, BatchIdx): grid z = image x 2 + channel; p0 of a pass is the reference's plane.
+template <int NPASS>
+__global__ __launch_bounds__(256, 8) void k_malta_rolled_batch(MaltaArgs<NPASS> a0, MaltaArgs<NPASS> a1, int w,
+                                                     int h, int pitch, BatchIdx batch) {
+#define GZ_MALTA_BATCHED 1
+#include "gz_kernels_malta_body.inc"
+#undef GZ_MALTA_BATCHED
 }
 
 // -------------------------------------------------- mask LUTs + combine + sqrt stage --
@@ -352,7 +319,23 @@ GZ_DEVFN float combine_px(const CombineArgs& a, size_t i, float mxb, float myb1,
 
 // grid = (ceil(w / (4 * 256)), h): a thread takes 4 consecutive pixels of a row -- the twelve
 // input planes and the output move as 16-byte accesses -- when the pitch allows it.
-__global__ __launch_bounds__(256) void k_combine(CombineArgs a, int w, int h, int pitch) {
+// B... (empty, or one BatchIdx: gz_common.h): the batched form, grid z = image.  The reference's planes are lf0_x, lf0_b
+// and hf0_y; the tables and clear_word do not move.
+GZ_DEVFN void gz_batch_shift(CombineArgs& a, int img, const BatchIdx& b) {
+  const size_t o = img * b.stride, r = img * b.ref_stride;
+  gz_batch_move(a.mask_x_blur, o); gz_batch_move(a.mask_y_blur1, o); gz_batch_move(a.mask_y_blur2, o);
+  gz_batch_move(a.ac0, o); gz_batch_move(a.ac1, o);
+  gz_batch_move(a.lf0_x, r); gz_batch_move(a.lf1_x, o);
+  gz_batch_move(a.lf0_b, r); gz_batch_move(a.lf1_b, o);
+  gz_batch_move(a.sn_blur, o);
+  gz_batch_move(a.hf0_y, r); gz_batch_move(a.hf1_y, o);
+  gz_batch_move(a.out, o);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { gz_batch_move(a.mask_out[i], o); gz_batch_move(a.mask_dc_out[i], o); }
+}
+template <class... B>
+__global__ __launch_bounds__(256) void k_combine(CombineArgs a, int w, int h, int pitch, B... batch) {
+  if constexpr (sizeof...(B) > 0) gz_batch_shift(a, (int)blockIdx.z, batch...);
   const int x = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
   if (a.clear_word && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.clear_word = 0u;
   if (x >= w || y >= h) return;

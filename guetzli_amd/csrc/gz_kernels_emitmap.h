@@ -52,10 +52,17 @@ GZ_DEVFN void emit_map_value(float f, ingest_bf16* out) { out->bits = emit_map_b
 // group at the end of a row in either instantiation, goes element by element.
 // No path writes an element other than the (y, x) it converts: the destination may be a crop inside a larger tensor,
 // and its neighbours stay as they are.
-template <class T, bool WIDE>
+// B... (empty, or one BatchTensor: gz_common.h): the batched form, gridDim.y = N arenas' planes into N images of the
+// caller's tensor; WIDE is the caller's word for every one of them.
+template <class T, bool WIDE, class... B>
 __global__ __launch_bounds__(256) void k_emit_map(const float* __restrict__ map, int w, int h, int pitch, T* __restrict__ out,
-                                                  long long sy, long long sx) {
+                                                  long long sy, long long sx, B... batch) {
   constexpr int P = 16 / (int)sizeof(T);
+  if constexpr (sizeof...(B) > 0) {
+    const BatchTensor bt = (batch, ...);
+    map += (size_t)blockIdx.y * bt.plane_stride;
+    out += (long long)blockIdx.y * bt.stride_n;
+  }
   const unsigned gpr = (unsigned)(w + P - 1) / P;                  // groups per row
   const unsigned g = blockIdx.x * 256u + threadIdx.x;              // (gpr * h <= 16384 * 65535)
   if (g >= gpr * (unsigned)h) return;

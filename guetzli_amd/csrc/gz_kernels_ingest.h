@@ -66,12 +66,20 @@ enum { kIngestElementwise = 0, kIngestPlanarRows = 1, kIngestInterleavedRows = 2
 // Output: rgb[(y * w + x) * 3 + c], a full group as 3 P / 4 dwords when its first byte is dword-aligned (every group
 // when w is a multiple of 4) and byte by byte otherwise; and, if lin != nullptr, lin[c * pstride + y * pitch + x] =
 // lut[byte], a full group as 16-byte stores when the address allows it.  The 1 KB table is staged in LDS.
-template <class T>
+// B... (empty, or one BatchTensor: gz_common.h): the batched form, gridDim.y = N images of the caller's tensor into N
+// arenas' linear planes.  It writes no packed bytes (rgb is not used: a comparison reads the planes alone), and `wide`
+// is the CALLER's word for every image of the batch (stride_n must keep the vectors' alignment too).
+template <class T, class... B>
 __global__ __launch_bounds__(256) void k_ingest_rgb(const T* __restrict__ data, long long sy, long long sx,
                                                     long long sc, int w, int h, int wide,
                                                     uint8_t* __restrict__ rgb, const float* __restrict__ lut,
-                                                    float* __restrict__ lin, int pitch, size_t pstride) {
+                                                    float* __restrict__ lin, int pitch, size_t pstride, B... batch) {
   constexpr int P = 16 / (int)sizeof(T);
+  if constexpr (sizeof...(B) > 0) {
+    const BatchTensor bt = (batch, ...);
+    data += (long long)blockIdx.y * bt.stride_n;
+    lin += (size_t)blockIdx.y * bt.plane_stride;
+  }
   __shared__ float s_lut[256];
   if (lin != nullptr) {   // (uniform: every thread of the block gets here)
     s_lut[threadIdx.x] = lut[threadIdx.x];
@@ -105,6 +113,7 @@ __global__ __launch_bounds__(256) void k_ingest_rgb(const T* __restrict__ data, 
       for (int c = 0; c < 3; ++c)
         b[3 * i + c] = i < n ? ingest_byte(src[(long long)i * sx + (long long)c * sc]) : (uint8_t)0;
   }
+  if constexpr (sizeof...(B) == 0) {
   uint8_t* dst = rgb + ((size_t)y * w + x0) * 3;
   if (n == P && ((uintptr_t)dst & 3u) == 0) {
     uint32_t* dst4 = reinterpret_cast<uint32_t*>(dst);
@@ -115,6 +124,7 @@ __global__ __launch_bounds__(256) void k_ingest_rgb(const T* __restrict__ data, 
 #pragma unroll
     for (int j = 0; j < 3 * P; ++j)
       if (j < 3 * n) dst[j] = b[j];
+  }
   }
   if (lin == nullptr) return;
   float* out = lin + ((size_t)y * pitch + x0);

@@ -10,7 +10,7 @@ import numpy as np
 
 import time
 
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_map, device_output, device_pixels
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_batch, device_map, device_map_batch, device_output, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -1086,6 +1086,121 @@ def butteraugli(reference, distorted, distmap=None, layout=None, device=None, st
         heat = cmp._heat_destination(heatmap, good, bad, consumer)
         out, dmap = cmp._destination(distmap, consumer)
         return cmp._compare(other, out, dmap, heat)
+
+
+BATCH_MAX_PIXELS = 1500000   # gz_butteraugli_batch: w * h below this
+BATCH_DTYPES = ("uint8", "float32", "float16", "bfloat16")
+
+
+def _device_array(x, device, what):
+    """(ptr, shape, element strides, dtype name, the stream it was made on, device ordinal, read-only) of a GPU tensor or
+    __cuda_array_interface__ object."""
+    if getattr(x, "is_cuda", False):   # a torch tensor
+        import torch
+        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        if device is not None and device != ordinal:
+            raise ValueError(f"{what} lives on device {ordinal}, device {device} was asked for")
+        return (x.data_ptr(), tuple(x.shape), tuple(x.stride()), str(x.dtype).replace("torch.", ""),
+                torch.cuda.current_stream(x.device).cuda_stream, ordinal, False)
+    cai = x.__cuda_array_interface__
+    dt, shape = np.dtype(cai["typestr"]), tuple(cai["shape"])
+    if cai.get("strides") is None:
+        byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
+    else:
+        byte_strides = tuple(cai["strides"])
+    if any(b % dt.itemsize for b in byte_strides):
+        raise ValueError("strides that are no multiple of the element size")
+    stream = cai.get("stream") or 0   # (as _device_source reads it)
+    return (cai["data"][0], shape, tuple(b // dt.itemsize for b in byte_strides), dt.name, 0 if stream == 1 else stream,
+            0 if device is None else device, bool(cai["data"][1]))
+
+
+def _batch_images(x, layout, device, stream, what, one_image_too=False):
+    """A batch [N,3,H,W] / [N,H,W,3] (with one_image_too also one image, 2-D or 3-D: n = 1) -> (capi.GzDeviceBatch, n, w, h, ordinal, keep).
+    Host arrays are uploaded first, on the calling thread's current stream."""
+    if not is_device_resident(x):
+        x = _upload_linear(np.asarray(x), 0 if device is None else device)
+    ptr, shape, strides, dtype, producer, ordinal, _ = _device_array(x, device, what)
+    if dtype not in BATCH_DTYPES:
+        raise ValueError(f"{what} has dtype {dtype}: a batch takes uint8, float32, float16 or bfloat16 (16-bit integer samples: "
+                         "compare the images one by one with butteraugli())")
+    if len(shape) == 4:
+        n, sn, shape, strides = shape[0], strides[0], shape[1:], strides[1:]
+        if n < 1:
+            raise ValueError(f"{what} is an empty batch")
+    elif len(shape) in (2, 3) and one_image_too:
+        n, sn = 1, 0
+    else:
+        raise ValueError(f"{what} has {len(shape)} dimensions: a batch is [N,3,H,W] or [N,H,W,3]")
+    try:
+        w, h, (sy, sx, sc), _ = _layout_strides(shape, strides, layout)
+    except ValueError as e:
+        if "alpha" not in str(e):
+            raise
+        raise ValueError(f"{what} of shape {tuple(shape)}: a batch takes 3 channels, or 1 (grey) -- no alpha; blend the images "
+                         "first, or compare them one by one with butteraugli(background=)") from None
+    if min(sn, sy, sx, sc) < 0:
+        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    if stream is not None:
+        producer = int(stream)
+    return device_batch(ptr, DTYPE_CODES[dtype], (sn, sy, sx, sc), producer), n, w, h, ordinal, x
+
+
+def _new_batch_tensor(shape, ordinal):
+    """A fresh float32 torch tensor of `shape` on GPU `ordinal`, from the calling thread's current stream."""
+    import torch
+    return torch.empty(shape, dtype=torch.float32, device=f"cuda:{ordinal}")
+
+
+def butteraugli_batch(reference, distorted, distmap=None, layout=None, device=None, stream=None, scratch_bytes=0):
+    """The butteraugli distances of N image pairs of one size with the kernel launches of ONE comparison -> a float32 [N]
+    tensor on the GPU, or with distmap= -> (distances, maps).  Pair i is, bit for bit, butteraugli(reference[i],
+    distorted[i]).
+    distorted: a 4-D GPU tensor [N,3,H,W] or [N,H,W,3] (or [N,1,H,W] / [N,H,W,1]: grey) of uint8, float32, float16 or
+    bfloat16 under ANY non-negative strides -- a slice x[::2], crop views, an expanded image; layout= ("CHW" / "HWC",
+    per image) where the shape does not say.  A host array is uploaded first.  reference: the same shape, or ONE 3-D
+    image that all N are compared with (its half of the work is done once).  The metric is ASYMMETRIC, as butteraugli()'s.
+    distmap=True: float32 [N,H,W]; distmap=tensor: that 3-D float32 / float16 / bfloat16 tensor is filled under its own
+    strides (a view inside a larger tensor keeps its surroundings) and returned.  stream= overrides the producer's
+    stream of both batches and the consumer's of the maps.  The call waits for its own work: the distances are complete
+    when it returns, and work on the calling thread's current stream sees the maps.
+    scratch_bytes= caps the device memory of the call's image arenas (172 bytes per pixel and image; default 2 GiB):
+    a batch that needs more runs in chunks, with the same results.
+    ValueError, before anything is computed: sizes that differ, sizes under 8 x 8, images of 1.5 MPix and more (they
+    gain nothing: Comparator keeps one reference for many images), alpha or 2 / 4 channels, 16-bit integer samples."""
+    other, n, w, h, ordinal, keep1 = _batch_images(distorted, layout, device, stream, "distorted")
+    ref, n_ref, rw, rh, _, keep0 = _batch_images(reference, layout, ordinal, stream, "reference", one_image_too=True)
+    if (rw, rh) != (w, h):
+        raise ValueError(f"the images differ in size: {rw} x {rh} against {w} x {h}")
+    if n_ref not in (1, n):
+        raise ValueError(f"{n_ref} reference images against {n} distorted ones: as many, or one for all")
+    if min(w, h) < 8:
+        raise ValueError(f"a {w} x {h} image: butteraugli needs at least 8 x 8")
+    if w * h >= BATCH_MAX_PIXELS:
+        raise ValueError(f"{w} x {h} images: a batch takes images under {BATCH_MAX_PIXELS} pixels -- larger ones fill the GPU alone; "
+                         "use Comparator (one reference, many images) or butteraugli()")
+    maps = out = None
+    if distmap is not None and distmap is not False:
+        out = _new_batch_tensor((n, h, w), ordinal) if distmap is True else distmap
+        if not is_device_resident(out):
+            raise TypeError("distmap=: True, or a device-resident [N,H,W] tensor to fill")
+        ptr, shape, strides, dtype, consumer, _, readonly = _device_array(out, ordinal, "distmap=")
+        if readonly:
+            raise ValueError("distmap= is read-only (its __cuda_array_interface__ says so)")
+        if dtype not in MAP_DTYPES:
+            raise TypeError(f"distmap= has dtype {dtype}: float32, float16 or bfloat16")
+        if shape != (n, h, w):
+            raise ValueError(f"distmap= has shape {shape}, the batch's maps are {(n, h, w)}")
+        if min(strides) < 0:
+            raise ValueError("negative strides (a flipped view): make it contiguous first")
+        if _strides_alias(strides, (n, h, w)):
+            raise ValueError(f"distmap= has strides {strides} under which two of its elements share an address (an expanded view?)")
+        maps = device_map_batch(ptr, DTYPE_CODES[dtype], strides, consumer if stream is None else int(stream))
+    dist = _new_batch_tensor((n,), ordinal)
+    dptr = _device_array(dist, ordinal, "distances")[0]
+    _pair_library().butteraugli_batch(ref, other, w, h, n, dptr, n_ref=n_ref, maps=maps, scratch_bytes=int(scratch_bytes), device=ordinal)
+    del keep0, keep1
+    return dist if out is None else (dist, out)
 
 
 def butteraugli_linear(reference, distorted, scale=1.0, distmap=None, heatmap=None, good=None, bad=None, layout=None, device=None,

@@ -508,6 +508,49 @@ int gz_butteraugli_linear(int device, int w, int h, const gz_device_pixels* ref,
                           float scale, float* distance, const gz_device_map* map, const gz_device_output* heat,
                           double good, double bad, uint64_t* clamped);
 
+/* Batches: N image pairs of one size through ONE Compare chain --------------------------
+ * gz_compare_device_pixels answers one pair per call and enqueues the chain's ~18 launches for it; below 0.25 MPix
+ * those launches cost more than their work.  gz_butteraugli_batch compares n pairs of w x h images with the launches of
+ * one: every kernel of the chain has a batched form whose grid carries the image index.  Context-free,
+ * as gz_butteraugli_linear: a context lives for the call, temporaries come from the pools and go back to them, the
+ * caller's current device stays current, and the call waits for its own work before it returns.
+ * gz_device_batch: n strided images in device memory, element (i, y, x, c) at data[i*stride_n + y*stride_y + x*stride_x
+ * + c*stride_c], strides in ELEMENTS and >= 0 (stride_n = 0: the same image n times; stride_c = 0: grey).  The byte of an
+ * element is gz_device_image's (integers pass, floats x 255 rounded to nearest even and clamped): the bytes compared
+ * are the bytes an encode would read.  producer_stream is waited for on the device.
+ * gz_device_map_batch: n strided maps, element (i, y, x) at data[i*stride_n + y*stride_y + x*stride_x], gz_device_map's
+ * value rule; exactly the n*h*w elements are written.  consumer_stream as gz_device_map's, in both directions.
+ * ref holds n_ref images: n (pair i is ref i against other i), or 1 -- ONE reference for all, whose planes are computed
+ * once.  distances: n contiguous float32 in DEVICE memory, 4-byte aligned; host_distances (may be NULL) receives them too.
+ * maps may be NULL.  Distance and map of pair i are, bit for bit, what gz_create_from_device(ref i) followed by
+ * gz_compare_device_pixels(other i, map i) gives.
+ * scratch_cap_bytes (0: 2 GiB): the most device memory the call's image arenas may take -- 43 float planes per image,
+ * 172 bytes per pixel.  More images than fit (or than 21845, the grid's limit) run as chunks of as many as fit, one at
+ * the least; no result depends on the chunking.
+ * GZ_E_ARG (before any device call): a NULL ref, other or distances, a wrong struct_size, n < 1, n_ref not 1 or n, w or
+ * h < 8 or >= 65536, w*h >= 1500000 (larger images gain nothing: use a context per reference), an unknown dtype, a
+ * negative stride, an extent beyond 62 bits, a misaligned distances; for maps, strides under which two of the n*h*w
+ * elements share an address (stride_n = 0 with n > 1 among them).  Memory the device cannot reach: GZ_E_ARG, as for the
+ * other entries.  After a failed call the caller's tensors hold unspecified values in their elements, and what lies
+ * between their elements is untouched. */
+typedef struct gz_device_batch {
+  int struct_size;            /* sizeof(gz_device_batch) */
+  int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 */
+  const void* data;           /* device address of element (0,0,0,0) */
+  int64_t stride_n, stride_y, stride_x, stride_c;   /* elements, >= 0 */
+  void* producer_stream;      /* hipStream_t that wrote the data; NULL = it is complete when the call starts */
+} gz_device_batch;
+typedef struct gz_device_map_batch {
+  int struct_size;            /* sizeof(gz_device_map_batch) */
+  int dtype;                  /* GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 */
+  void* data;                 /* device address of element (0,0,0) */
+  int64_t stride_n, stride_y, stride_x;   /* elements, >= 0, no two elements at one address */
+  void* consumer_stream;      /* hipStream_t that used the memory before and reads it after; NULL = none */
+} gz_device_map_batch;
+int gz_butteraugli_batch(int device, int w, int h, int n, const gz_device_batch* ref, int n_ref,
+                         const gz_device_batch* other, float* distances, float* host_distances,
+                         const gz_device_map_batch* maps, size_t scratch_cap_bytes);
+
 /* Masking: Mask, the opsin image and the quantisation field, on the device ---------------
  * What butteraugli.h offers beside the distance: OpsinDynamicsImage(rgb), the XYB image; Mask(xyb0, xyb1, &mask,
  * &mask_dc) (butteraugli.cc:1741-1817), the visual-masking images that say where an error of a given size is visible;
