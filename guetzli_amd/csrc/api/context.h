@@ -473,6 +473,26 @@ struct DeviceScope {
   DeviceScope(const DeviceScope&) = delete;
   DeviceScope& operator=(const DeviceScope&) = delete;
 };
+// Its counterpart for the entries without a context, which make `device` current on their way (create_context,
+// probe_device): the caller's device stays current.  It is remembered here -- if it cannot be asked for, there is
+// nothing to restore -- and restored at the end of the scope if it is another one than `device`.
+struct CallerDevice {
+  int device, prev = -1;
+  explicit CallerDevice(int device_) : device(device_) {
+    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  }
+  ~CallerDevice() { if (prev >= 0 && prev != device) (void)hipSetDevice(prev); }
+  CallerDevice(const CallerDevice&) = delete;
+  CallerDevice& operator=(const CallerDevice&) = delete;
+};
+// A context that lives for one call (declared behind the call's CallerDevice: destroyed before the device is restored).
+struct CallContext {
+  gz_ctx* c;
+  explicit CallContext(gz_ctx* c_) : c(c_) {}
+  ~CallContext() { gz_destroy(c); }   // (synchronises the streams whatever was enqueued, then everything goes back to the pools)
+  CallContext(const CallContext&) = delete;
+  CallContext& operator=(const CallContext&) = delete;
+};
 
 namespace {
 

@@ -13,99 +13,43 @@ constexpr size_t kBatchDefaultScratch = (size_t)2 << 30;   // scratch_cap_bytes 
 constexpr int kBatchMaxGridImages = 65535 / 3;              // gridDim.z = images x planes of the launch, 3 at the most
 constexpr uint64_t kBatchMaxPixels = 1500000;               // (chain.h: below it a lone image gets the configuration the batch has)
 
-// The arguments alone: no device call.  The images of a batch are n gz_device_pixels without alpha.
-int check_device_batch(const gz_device_batch* b, int w, int h, int n) {
-  if (!b || b->struct_size != (int)sizeof(gz_device_batch) || !b->data) return GZ_E_ARG;
-  if (b->dtype < GZ_DT_U8 || b->dtype > GZ_DT_BF16) return GZ_E_ARG;
-  if (b->stride_n < 0) return GZ_E_ARG;
-  gz_device_pixels px;
-  memset(&px, 0, sizeof(px));
-  px.struct_size = (int)sizeof(px);
-  px.dtype = b->dtype; px.data = b->data;
-  px.stride_y = b->stride_y; px.stride_x = b->stride_x; px.stride_c = b->stride_c;
-  if (check_device_pixels(&px, w, h) != GZ_OK) return GZ_E_ARG;
-  // ... and the last image's last element in 62 bits
-  const uint64_t lim = (1ull << 62) - 1, sn = (uint64_t)b->stride_n;
-  const uint64_t one = (uint64_t)b->stride_y * (uint64_t)(h - 1) + (uint64_t)b->stride_x * (uint64_t)(w - 1) + (uint64_t)b->stride_c * 2;
-  if (n > 1 && sn > lim / (uint64_t)(n - 1)) return GZ_E_ARG;
-  if (sn * (uint64_t)(n - 1) + one > lim) return GZ_E_ARG;
-  return GZ_OK;
-}
-uint64_t device_batch_last(const gz_device_batch* b, int w, int h, int n) {
-  return (uint64_t)b->stride_n * (uint64_t)(n - 1) + (uint64_t)b->stride_y * (uint64_t)(h - 1) + (uint64_t)b->stride_x * (uint64_t)(w - 1) +
-         (uint64_t)b->stride_c * 2;
-}
-
-// check_device_map's rules over three dimensions: no two of the n * h * w elements at one address.
-int check_device_map_batch(const gz_device_map_batch* m, int w, int h, int n) {
-  if (!m || m->struct_size != (int)sizeof(gz_device_map_batch) || !m->data) return GZ_E_ARG;
-  if (m->dtype != GZ_DT_F32 && m->dtype != GZ_DT_F16 && m->dtype != GZ_DT_BF16) return GZ_E_ARG;
-  if (m->stride_n < 0 || m->stride_y < 0 || m->stride_x < 0) return GZ_E_ARG;
-  const uint64_t lim = (1ull << 62) - 1;
-  const uint64_t sn = (uint64_t)m->stride_n, sy = (uint64_t)m->stride_y, sx = (uint64_t)m->stride_x;
-  if ((n > 1 && sn > lim / (uint64_t)(n - 1)) || (h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1))) return GZ_E_ARG;
-  const uint64_t tn = sn * (uint64_t)(n - 1), ty = sy * (uint64_t)(h - 1), tx = sx * (uint64_t)(w - 1);   // each <= lim < 2^62
-  if (tn + ty > lim || tn + ty + tx > lim) return GZ_E_ARG;
-  std::pair<uint64_t, uint64_t> dim[3] = {{sn, (uint64_t)n}, {sy, (uint64_t)h}, {sx, (uint64_t)w}};
-  std::sort(dim, dim + 3);
-  uint64_t least = 1;
-  for (const auto& d : dim) {
-    if (d.second == 1) continue;
-    if (d.first < least) return GZ_E_ARG;
-    least = d.first * d.second;
-  }
-  return GZ_OK;
-}
-uint64_t device_map_batch_last(const gz_device_map_batch* m, int w, int h, int n) {
-  return (uint64_t)m->stride_n * (uint64_t)(n - 1) + (uint64_t)m->stride_y * (uint64_t)(h - 1) + (uint64_t)m->stride_x * (uint64_t)(w - 1);
-}
+// (the arguments alone -- check_device_batch, check_device_map_batch: tensor.h)
 
 // k_ingest_rgb's batched form on `stream`: images first .. first + count - 1 of b -> the linear planes of `count` arenas.
 // The 16-byte reads need every image's base aligned: the first one's, and stride_n a multiple of the vector's elements.
-template <class T>
-void launch_ingest_batch_t(hipStream_t stream, const gz_device_batch* b, int first, int count, int w, int h, const float* lut, float* lin,
-                           int pitch, size_t pstride, size_t arena_stride) {
-  const long long sn = b->stride_n, sy = b->stride_y, sx = b->stride_x, sc = b->stride_c;
-  const T* data = (const T*)b->data + (long long)first * sn;
-  constexpr int P = 16 / (int)sizeof(T);
-  const int wide = sn % P == 0 ? ingest_wide_mode(data, sizeof(T), sy, sx, sc) : (int)kIngestElementwise;
-  const dim3 grid((unsigned)(((size_t)gz_div_up(w, P) * h + 255) / 256), (unsigned)count), block(256);
-  const BatchTensor bt = {sn, arena_stride};
-  uint8_t* const no_bytes = nullptr;
-  GZ_LAUNCH((k_ingest_rgb<T, BatchTensor>), grid, block, stream, data, sy, sx, sc, w, h, wide, no_bytes, lut, lin, pitch, pstride, bt);
-}
 void launch_ingest_batch(hipStream_t stream, const gz_device_batch* b, int first, int count, int w, int h, const float* lut, float* lin,
                          int pitch, size_t pstride, size_t arena_stride) {
-  switch (b->dtype) {
-    case GZ_DT_U8: launch_ingest_batch_t<uint8_t>(stream, b, first, count, w, h, lut, lin, pitch, pstride, arena_stride); break;
-    case GZ_DT_F32: launch_ingest_batch_t<float>(stream, b, first, count, w, h, lut, lin, pitch, pstride, arena_stride); break;
-    case GZ_DT_F16: launch_ingest_batch_t<ingest_f16>(stream, b, first, count, w, h, lut, lin, pitch, pstride, arena_stride); break;
-    default: launch_ingest_batch_t<ingest_bf16>(stream, b, first, count, w, h, lut, lin, pitch, pstride, arena_stride); break;
-  }
+  const long long sn = b->stride_n, sy = b->stride_y, sx = b->stride_x, sc = b->stride_c;
+  with_sample_type(b->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (!std::is_same<T, uint16_t>::value) {   // (a batch holds no GZ_DT_U16, and the kernel has no batched form of it)
+      const T* data = (const T*)b->data + (long long)first * sn;
+      constexpr int P = 16 / (int)sizeof(T);
+      const int wide = sn % P == 0 ? ingest_wide_mode(data, sizeof(T), sy, sx, sc) : (int)kIngestElementwise;
+      const dim3 grid((unsigned)(((size_t)gz_div_up(w, P) * h + 255) / 256), (unsigned)count), block(256);
+      const BatchTensor bt = {sn, arena_stride};
+      uint8_t* const no_bytes = nullptr;
+      GZ_LAUNCH((k_ingest_rgb<T, BatchTensor>), grid, block, stream, data, sy, sx, sc, w, h, wide, no_bytes, lut, lin, pitch, pstride, bt);
+    }
+  });
 }
 
 // k_emit_map's batched form: the `count` arenas' map planes -> maps first .. first + count - 1 of m.
-template <class T>
-void launch_emit_map_batch_t(hipStream_t stream, const float* plane, size_t arena_stride, int w, int h, int pitch, const gz_device_map_batch* m,
-                             int first, int count) {
-  const long long sn = m->stride_n, sy = m->stride_y, sx = m->stride_x;
-  T* out = (T*)m->data + (long long)first * sn;
-  constexpr int P = 16 / (int)sizeof(T);
-  const dim3 grid((unsigned)(((size_t)((w + P - 1) / P) * h + 255) / 256), (unsigned)count), block(256);
-  const BatchTensor bt = {sn, arena_stride};
-  if (sn % P == 0 && emit_map_wide(out, sizeof(T), sy, sx)) {
-    GZ_LAUNCH((k_emit_map<T, true, BatchTensor>), grid, block, stream, plane, w, h, pitch, out, sy, sx, bt);
-  } else {
-    GZ_LAUNCH((k_emit_map<T, false, BatchTensor>), grid, block, stream, plane, w, h, pitch, out, sy, sx, bt);
-  }
-}
 void launch_emit_map_batch(hipStream_t stream, const float* plane, size_t arena_stride, int w, int h, int pitch, const gz_device_map_batch* m,
                            int first, int count) {
-  switch (m->dtype) {
-    case GZ_DT_F32: launch_emit_map_batch_t<float>(stream, plane, arena_stride, w, h, pitch, m, first, count); break;
-    case GZ_DT_F16: launch_emit_map_batch_t<ingest_f16>(stream, plane, arena_stride, w, h, pitch, m, first, count); break;
-    default: launch_emit_map_batch_t<ingest_bf16>(stream, plane, arena_stride, w, h, pitch, m, first, count); break;
-  }
+  const long long sn = m->stride_n, sy = m->stride_y, sx = m->stride_x;
+  with_float_type(m->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    T* out = (T*)m->data + (long long)first * sn;
+    constexpr int P = 16 / (int)sizeof(T);
+    const dim3 grid((unsigned)(((size_t)((w + P - 1) / P) * h + 255) / 256), (unsigned)count), block(256);
+    const BatchTensor bt = {sn, arena_stride};
+    if (sn % P == 0 && emit_map_wide(out, sizeof(T), sy, sx)) {
+      GZ_LAUNCH((k_emit_map<T, true, BatchTensor>), grid, block, stream, plane, w, h, pitch, out, sy, sx, bt);
+    } else {
+      GZ_LAUNCH((k_emit_map<T, false, BatchTensor>), grid, block, stream, plane, w, h, pitch, out, sy, sx, bt);
+    }
+  });
 }
 
 // The batch's own state in the context: on for the launches of a chunk, off again on every path out.
@@ -120,14 +64,6 @@ struct BatchScope {
   BatchScope& operator=(const BatchScope&) = delete;
 };
 
-int wait_for_stream(gz_ctx* c, void* producer) {
-  if (!producer) return GZ_OK;
-  if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
-  HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)producer));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
-  return GZ_OK;
-}
-
 // (the context's device is current, every argument is checked; c has `per_chunk` arenas)
 int butteraugli_batch(gz_ctx* c, int n, const gz_device_batch* ref, int n_ref, const gz_device_batch* other, float* distances,
                       float* host_distances, const gz_device_map_batch* maps, int per_chunk) {
@@ -136,16 +72,11 @@ int butteraugli_batch(gz_ctx* c, int n, const gz_device_batch* ref, int n_ref, c
   const hipStream_t stream = c->stream;
   const ChainStreams cs = chain_streams(c, false);   // ONE stream: the batch supplies the parallelism
   c->batch.max_bits = (unsigned*)(c->arena + stride * (size_t)per_chunk);
-  TRY(wait_for_stream(c, ref->producer_stream));
-  if (other->producer_stream != ref->producer_stream) TRY(wait_for_stream(c, other->producer_stream));
+  TRY(wait_for_producer(c, ref->producer_stream));
+  if (other->producer_stream != ref->producer_stream) TRY(wait_for_producer(c, other->producer_stream));
   if (n_ref == 1) {
     // one reference for all: its planes once, in the first arena, by the kernels of a lone image (batch.n == 0)
-    gz_device_pixels px;
-    memset(&px, 0, sizeof(px));
-    px.struct_size = (int)sizeof(px);
-    px.dtype = ref->dtype; px.data = ref->data;
-    px.stride_y = ref->stride_y; px.stride_x = ref->stride_x; px.stride_c = ref->stride_c;
-    launch_ingest(stream, &px, w, h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+    launch_ingest(stream, tensor_select(tensor_view(ref, w, h, 1), 0, 0), nullptr, w, h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
     KCHK(c);
     TRY(stage_opsin(c, stream));
     TRY(stage_separate(c, cs, &c->pi0));
@@ -153,7 +84,7 @@ int butteraugli_batch(gz_ctx* c, int n, const gz_device_batch* ref, int n_ref, c
     mask_in_psycho(c->pi0, in0);
     TRY(stage_mask_sup(c, stream, in0, c->sup0));
   }
-  if (maps && maps->consumer_stream && !c->ev_emit) TRY(own_event(c, &c->ev_emit));
+  if (maps && maps->consumer_stream && !c->ev_emit) TRY(own_event(c, &c->ev_emit));   // (in front of the chunks: outputs_after_consumers finds it)
   for (int first = 0; first < n; first += per_chunk) {
     const int m = std::min(per_chunk, n - first);
     BatchScope scope(c, m, stride, n_ref == 1 ? 0 : stride);
@@ -173,13 +104,13 @@ int butteraugli_batch(gz_ctx* c, int n, const gz_device_batch* ref, int n_ref, c
     TRY(stage_diffmap(c, cs, c->pi0, c->pi1, maps ? kWantDistmap : 0u, ClearMax::kMemset));
     if (maps) {
       // the consumer's stream: waited for in front of the first emit kernel, and it waits behind the last one
-      if (first == 0 && maps->consumer_stream) HIPCHK(c, emit_after_consumer(stream, c->ev_emit, maps->consumer_stream));
+      if (first == 0) TRY(outputs_after_consumers(c, stream, &c->ev_emit, {maps->consumer_stream}));
       launch_emit_map_batch(stream, c->distmap, stride, w, h, c->pitch, maps, first, m);
       KCHK(c);
     }
     HIPCHK(c, hipMemcpyAsync(distances + first, c->batch.max_bits, sizeof(float) * (size_t)m, hipMemcpyDeviceToDevice, stream));
   }
-  if (maps && maps->consumer_stream) HIPCHK(c, consumer_after_emit(stream, c->ev_emit, maps->consumer_stream));
+  if (maps) TRY(consumers_after_outputs(c, stream, c->ev_emit, {maps->consumer_stream}));
   if (host_distances) HIPCHK(c, hipMemcpyAsync(host_distances, distances, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, stream));
   HIPCHK(c, hipStreamSynchronize(stream));   // (the arenas go back to the pool behind this; the tensors are read and written)
   return GZ_OK;
@@ -201,24 +132,15 @@ int gz_butteraugli_batch(int device, int w, int h, int n, const gz_device_batch*
   const size_t cap = scratch_cap_bytes ? scratch_cap_bytes : kBatchDefaultScratch;
   const size_t per_image = sizeof(float) * batch_arena_stride((size_t)w * h) + sizeof(unsigned);
   const int per_chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n, cap / per_image, (size_t)kBatchMaxGridImages}));
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  int rc = probe_device(device);
-  if (rc == GZ_OK) {
-    rc = check_device_range(device, ref->data, device_batch_last(ref, w, h, n_ref), ingest_elem_size(ref->dtype), "reference batch", nullptr);
-    if (rc == GZ_OK) rc = check_device_range(device, other->data, device_batch_last(other, w, h, n), ingest_elem_size(other->dtype), "batch", nullptr);
-    if (rc == GZ_OK) rc = check_device_range(device, distances, (uint64_t)(n - 1), sizeof(float), "distances", nullptr);
-    if (rc == GZ_OK && maps) rc = check_device_range(device, maps->data, device_map_batch_last(maps, w, h, n), ingest_elem_size(maps->dtype), "maps", nullptr);
-  }
-  if (rc == GZ_OK) {
-    gz_ctx* c = create_context(device, w, h, nullptr, nullptr, 1.0f, &rc, nullptr, per_chunk);
-    if (c) {
-      rc = butteraugli_batch(c, n, ref, n_ref, other, distances, host_distances, maps, per_chunk);
-      gz_destroy(c);   // (synchronises the stream whatever was enqueued, then everything goes back to the pools)
-    }
-  }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return rc;
+  CallerDevice keep(device);
+  TRY(probe_device(device));
+  TRY(check_tensor_memory(device, tensor_view(ref, w, h, n_ref), "reference batch", nullptr));
+  TRY(check_tensor_memory(device, tensor_view(other, w, h, n), "batch", nullptr));
+  TRY(check_device_range(device, distances, (uint64_t)(n - 1), sizeof(float), "distances", nullptr));
+  if (maps) TRY(check_tensor_memory(device, tensor_view(maps, w, h, n), "maps", nullptr));
+  int rc = GZ_OK;
+  const CallContext ctx(create_context(device, w, h, nullptr, nullptr, 1.0f, &rc, nullptr, per_chunk));
+  return ctx.c ? butteraugli_batch(ctx.c, n, ref, n_ref, other, distances, host_distances, maps, per_chunk) : rc;
 }
 
 }  // extern "C"

@@ -3,6 +3,26 @@
 // concern in round 5 -- no declaration here is visible outside libguetzli_amd.so but the C ABI)
 #pragma once
 
+// The element type of a dtype as a tag: f(TypeTag<T>()) -- for the five sample types of pixels and outputs, and for the
+// three float types of maps and linear images (a family that takes floats only instantiates nothing else).
+template <class T> struct TypeTag { using type = T; };
+template <class F> static void with_sample_type(int dtype, F&& f) {
+  switch (dtype) {
+    case GZ_DT_U8: f(TypeTag<uint8_t>()); break;
+    case GZ_DT_F32: f(TypeTag<float>()); break;
+    case GZ_DT_F16: f(TypeTag<ingest_f16>()); break;
+    case GZ_DT_BF16: f(TypeTag<ingest_bf16>()); break;
+    default: f(TypeTag<uint16_t>()); break;
+  }
+}
+template <class F> static void with_float_type(int dtype, F&& f) {
+  switch (dtype) {
+    case GZ_DT_F32: f(TypeTag<float>()); break;
+    case GZ_DT_F16: f(TypeTag<ingest_f16>()); break;
+    default: f(TypeTag<ingest_bf16>()); break;
+  }
+}
+
 extern "C" {
 
 
@@ -118,35 +138,46 @@ const char* gz_strerror(int code) {
 
 const char* gz_last_error(const gz_ctx* ctx) { return ctx ? ctx->err.c_str() : ""; }
 
+// ---- the stream contracts of the callers' tensors ----
+// An input's producer_stream: c->stream goes on behind what the producer has enqueued so far, without waiting for it on
+// the host.
+static int wait_for_producer(gz_ctx* c, void* producer) {
+  if (!producer) return GZ_OK;
+  if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
+  HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)producer));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
+  return GZ_OK;
+}
+// An output's consumer_stream, around the emit kernels on `stream`, with the event `ev`:
+// before: `stream` waits for what the consumer's stream has been given so far (a caching allocator may have handed the
+// memory out while earlier work of that stream still uses it); behind: the consumer's stream waits for the kernels.
+static hipError_t emit_after_consumer(hipStream_t stream, hipEvent_t ev, void* consumer) {
+  const hipError_t e = hipEventRecord(ev, (hipStream_t)consumer);
+  return e != hipSuccess ? e : hipStreamWaitEvent(stream, ev, 0);
+}
+static hipError_t consumer_after_emit(hipStream_t stream, hipEvent_t ev, void* consumer) {
+  const hipError_t e = hipEventRecord(ev, stream);
+  return e != hipSuccess ? e : hipStreamWaitEvent((hipStream_t)consumer, ev, 0);
+}
+// ... for every consumer of `consumers` that is one (NULL: none).  *ev: the holder's slot for the event -- a context's
+// ev_emit, a DecodeScratch's ev -- entered into c's record when the first consumer needs it, unless it is there already
+// (a caller that emits in several rounds makes it in front of them).
+static int outputs_after_consumers(gz_ctx* c, hipStream_t stream, hipEvent_t* ev, std::initializer_list<void*> consumers) {
+  for (void* s : consumers) {
+    if (!s) continue;
+    if (!*ev) TRY(own_event(c, ev));
+    HIPCHK(c, emit_after_consumer(stream, *ev, s));
+  }
+  return GZ_OK;
+}
+static int consumers_after_outputs(gz_ctx* c, hipStream_t stream, hipEvent_t ev, std::initializer_list<void*> consumers) {
+  for (void* s : consumers)
+    if (s) HIPCHK(c, consumer_after_emit(stream, ev, s));
+  return GZ_OK;
+}
+
 // ---- device-resident input (gz_kernels_ingest.h) ----
-static size_t ingest_elem_size(int dtype) { return dtype == GZ_DT_U8 ? 1 : dtype == GZ_DT_F32 ? 4 : 2; }
-// The arguments alone: no device call (the library answers these without a GPU).
-static int check_device_pixels(const gz_device_pixels* img, int w, int h) {
-  if (!img || img->struct_size != (int)sizeof(gz_device_pixels) || !img->data) return GZ_E_ARG;
-  if (img->dtype < GZ_DT_U8 || img->dtype > GZ_DT_U16) return GZ_E_ARG;
-  if (img->stride_y < 0 || img->stride_x < 0 || img->stride_c < 0) return GZ_E_ARG;
-  if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) return GZ_E_ARG;
-  // the last element's offset (h-1) sy + (w-1) sx + 2 sc in 62 bits: every term is bounded before it is formed
-  // (alpha's last offset is (h-1) sy + (w-1) sx, the ty + tx below)
-  const uint64_t lim = (1ull << 62) - 1;
-  const uint64_t sy = (uint64_t)img->stride_y, sx = (uint64_t)img->stride_x, sc = (uint64_t)img->stride_c;
-  if ((h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1)) || sc > lim / 2) return GZ_E_ARG;
-  const uint64_t ty = sy * (uint64_t)(h - 1), tx = sx * (uint64_t)(w - 1), tc = sc * 2;   // each <= lim < 2^62
-  if (ty + tx > lim || ty + tx + tc > lim) return GZ_E_ARG;
-  return GZ_OK;
-}
-// gz_device_image is gz_device_pixels without alpha: what the three older entries accept stays what it was (their
-// struct_size, no GZ_DT_U16), the rest is the code behind the newer ones.
-static int pixels_of_image(const gz_device_image* img, gz_device_pixels* px) {
-  if (!img || img->struct_size != (int)sizeof(gz_device_image) || img->dtype > GZ_DT_BF16) return GZ_E_ARG;
-  memset(px, 0, sizeof(*px));
-  px->struct_size = (int)sizeof(*px);
-  px->dtype = img->dtype;
-  px->data = img->data;
-  px->stride_y = img->stride_y; px->stride_x = img->stride_x; px->stride_c = img->stride_c;
-  px->producer_stream = img->producer_stream;
-  return GZ_OK;
-}
+// (the arguments alone -- check_device_pixels and its siblings, pixels_of_image: tensor.h)
 // Where the memory lives: it must be readable by `device` (the current one).  An ordinary host pointer, memory of
 // another GPU or an extent that leaves its allocation is an argument error here, not a fault in the kernel.
 // `last` = the offset of the last element read from p, `what` = "data" or "alpha".
@@ -185,49 +216,32 @@ static int check_device_range(int device, const void* p, uint64_t last, size_t e
 #endif
   return GZ_OK;
 }
-static int check_device_pointer(int device, const gz_device_pixels* img, int w, int h, std::string* why) {
-  const size_t elem = ingest_elem_size(img->dtype);
-  const uint64_t plane = (uint64_t)img->stride_y * (uint64_t)(h - 1) + (uint64_t)img->stride_x * (uint64_t)(w - 1);
-  if (const int rc = check_device_range(device, img->data, plane + (uint64_t)img->stride_c * 2, elem, "data", why)) return rc;
-  return img->alpha ? check_device_range(device, img->alpha, plane, elem, "alpha", why) : GZ_OK;
+// ... for a view: its data and, where it has one, its alpha.  `what` names the data in gz_last_error.
+static int check_tensor_memory(int device, const TensorView& v, const char* what, std::string* why) {
+  const size_t elem = tensor_elem_size(v.dtype);
+  if (const int rc = check_device_range(device, v.data, tensor_last(v, v.nd), elem, what, why)) return rc;
+  return v.alpha ? check_device_range(device, v.alpha, tensor_last(v, v.alpha_nd), elem, "alpha", why) : GZ_OK;
 }
-// The ingest kernel on `stream`: img (w x h) -> rgb [h][w][3] and, with lin != nullptr, the three linear planes.
-// Opaque pixels take k_ingest_rgb, pixels with alpha k_ingest_rgba: same grid, one launch either way.
-static void launch_ingest(hipStream_t stream, const gz_device_pixels* img, int w, int h, uint8_t* rgb, const float* lut,
-                          float* lin, int pitch, size_t pstride) {
-  const size_t elem = ingest_elem_size(img->dtype);
-  const long long sy = img->stride_y, sx = img->stride_x, sc = img->stride_c;
+
+// The ingest kernel on `stream`: img (y, x, c: w x h x 3, checked by the caller) -> rgb [h][w][3] and, with lin != nullptr,
+// the three linear planes.  Opaque pixels take k_ingest_rgb, pixels with alpha -- over `background`, gz_device_pixels' --
+// k_ingest_rgba: same grid, one launch either way.
+static void launch_ingest(hipStream_t stream, const TensorView& img, const uint8_t* background, int w, int h, uint8_t* rgb,
+                          const float* lut, float* lin, int pitch, size_t pstride) {
+  const size_t elem = tensor_elem_size(img.dtype);
+  const long long sy = img.dim[0].stride, sx = img.dim[1].stride, sc = img.dim[2].stride;
   const int per_lane = (int)(16 / elem);
   const dim3 grid((unsigned)(((size_t)gz_div_up(w, per_lane) * h + 255) / 256)), block(256);
-  if (img->alpha) {
-    const unsigned bg = (unsigned)img->background[0] | ((unsigned)img->background[1] << 8) | ((unsigned)img->background[2] << 16);
-    switch (img->dtype) {
-      case GZ_DT_U8: launch_ingest_rgba(stream, grid, block, (const uint8_t*)img->data, (const uint8_t*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
-      case GZ_DT_F32: launch_ingest_rgba(stream, grid, block, (const float*)img->data, (const float*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
-      case GZ_DT_F16: launch_ingest_rgba(stream, grid, block, (const ingest_f16*)img->data, (const ingest_f16*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
-      case GZ_DT_BF16: launch_ingest_rgba(stream, grid, block, (const ingest_bf16*)img->data, (const ingest_bf16*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
-      default: launch_ingest_rgba(stream, grid, block, (const uint16_t*)img->data, (const uint16_t*)img->alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride); break;
+  with_sample_type(img.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (img.alpha) {
+      const unsigned bg = (unsigned)background[0] | ((unsigned)background[1] << 8) | ((unsigned)background[2] << 16);
+      launch_ingest_rgba(stream, grid, block, (const T*)img.data, (const T*)img.alpha, sy, sx, sc, w, h, bg, rgb, lut, lin, pitch, pstride);
+    } else {
+      const int wide = ingest_wide_mode(img.data, elem, sy, sx, sc);
+      GZ_LAUNCH((k_ingest_rgb<T>), grid, block, stream, (const T*)img.data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
     }
-    return;
-  }
-  const int wide = ingest_wide_mode(img->data, elem, sy, sx, sc);
-  switch (img->dtype) {
-    case GZ_DT_U8:
-      GZ_LAUNCH((k_ingest_rgb<uint8_t>), grid, block, stream, (const uint8_t*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
-      break;
-    case GZ_DT_F32:
-      GZ_LAUNCH((k_ingest_rgb<float>), grid, block, stream, (const float*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
-      break;
-    case GZ_DT_F16:
-      GZ_LAUNCH((k_ingest_rgb<ingest_f16>), grid, block, stream, (const ingest_f16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
-      break;
-    case GZ_DT_BF16:
-      GZ_LAUNCH((k_ingest_rgb<ingest_bf16>), grid, block, stream, (const ingest_bf16*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
-      break;
-    default:
-      GZ_LAUNCH((k_ingest_rgb<uint16_t>), grid, block, stream, (const uint16_t*)img->data, sy, sx, sc, w, h, wide, rgb, lut, lin, pitch, pstride);
-      break;
-  }
+  });
 }
 
 static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img);
@@ -238,22 +252,16 @@ static int set_linear_device(gz_ctx* c, const LinearSource* src);
 static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, const gz_device_pixels* img, float target, int* err,
                               const LinearSource* linear = nullptr, int batch_arenas = 0);
 gz_ctx* gz_create(int device, int w, int h, const uint8_t* rgb, float target, int* err) {
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  gz_ctx* c = create_context(device, w, h, rgb, nullptr, target, err);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return c;
+  CallerDevice keep(device);
+  return create_context(device, w, h, rgb, nullptr, target, err);
 }
 gz_ctx* gz_create_from_device_pixels(int device, int w, int h, const gz_device_pixels* img, float target, int* err) {
   if (check_device_pixels(img, w, h) != GZ_OK) {   // (before any device call)
     if (err) *err = GZ_E_ARG;
     return nullptr;
   }
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  gz_ctx* c = create_context(device, w, h, nullptr, img, target, err);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-  return c;
+  CallerDevice keep(device);
+  return create_context(device, w, h, nullptr, img, target, err);
 }
 gz_ctx* gz_create_from_device(int device, int w, int h, const gz_device_image* img, float target, int* err) {
   gz_device_pixels px;
@@ -283,7 +291,7 @@ static gz_ctx* create_context(int device, int w, int h, const uint8_t* rgb, cons
     *err = GZ_E_NO_DEVICE;
     return nullptr;
   }
-  if (img && check_device_pointer(device, img, w, h, nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
+  if (img && check_tensor_memory(device, tensor_view(img, w, h), "data", nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
   if (linear && check_linear_pointer(device, linear, nullptr) != GZ_OK) { *err = GZ_E_ARG; return nullptr; }
   gz_ctx* c = new gz_ctx;
   c->device = device;
@@ -405,16 +413,12 @@ int gz_set_rgb(gz_ctx* c, const uint8_t* rgb) {
   return GZ_OK;
 }
 
-// (the context's device is current, img has passed check_device_pixels and check_device_pointer)
+// (the context's device is current, img has passed check_device_pixels and check_tensor_memory)
 static int set_rgb_device(gz_ctx* c, const gz_device_pixels* img) {
   c->lin_is_cand = c->xyb_is_cand = false;
   c->have_block_mask = c->have_distmap = false;
-  if (img->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
-    if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
-    HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)img->producer_stream));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
-  }
-  launch_ingest(c->stream, img, c->w, c->h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+  TRY(wait_for_producer(c, img->producer_stream));
+  launch_ingest(c->stream, tensor_view(img, c->w, c->h), img->background, c->w, c->h, c->d_rgb, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
   KCHK(c);
   TRY(original_from_lin(c));   // (its synchronise: the source is read when the call returns)
   c->orig_linear = false;      // (d_rgb is the original's again)
@@ -425,7 +429,7 @@ int gz_set_rgb_device_pixels(gz_ctx* c, const gz_device_pixels* img) {
   if (!c) return GZ_E_ARG;
   if (check_device_pixels(img, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   DeviceScope ds_(c);
-  if (const int rc = check_device_pointer(c->device, img, c->w, c->h, &c->err)) return rc;
+  if (const int rc = check_tensor_memory(c->device, tensor_view(img, c->w, c->h), "data", &c->err)) return rc;
   return set_rgb_device(c, img);
 }
 int gz_set_rgb_device(gz_ctx* c, const gz_device_image* img) {

@@ -46,7 +46,7 @@ int gz_encode_rgb_only(int device, const uint8_t* rgb, int w, int h, int16_t* co
 int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, int h, uint8_t* host_rgb_out) {
   if (!host_rgb_out || check_device_pixels(img, w, h) != GZ_OK) return GZ_E_ARG;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
-  if (check_device_pointer(device, img, w, h, nullptr) != GZ_OK) return GZ_E_ARG;
+  if (check_tensor_memory(device, tensor_view(img, w, h), "data", nullptr) != GZ_OK) return GZ_E_ARG;
   DevBuf drgb;
   if (!drgb.alloc((size_t)3 * w * h)) return GZ_E_NOMEM;
   hipEvent_t ev = nullptr;
@@ -56,7 +56,7 @@ int gz_pack_rgb_device_pixels(int device, const gz_device_pixels* img, int w, in
                     hipStreamWaitEvent((hipStream_t)0, ev, 0) == hipSuccess;
     if (!ok) { (void)hipEventDestroy(ev); return GZ_E_HIP; }
   }
-  launch_ingest((hipStream_t)0, img, w, h, (uint8_t*)drgb.p, nullptr, nullptr, w, 0);
+  launch_ingest((hipStream_t)0, tensor_view(img, w, h), img->background, w, h, (uint8_t*)drgb.p, nullptr, nullptr, w, 0);
   const bool launched = hipGetLastError() == hipSuccess;
   // (a blocking copy on the null stream: behind the kernel, and complete when it returns)
   const bool copied = launched && hipMemcpy(host_rgb_out, drgb.p, (size_t)3 * w * h, hipMemcpyDeviceToHost) == hipSuccess;

@@ -63,13 +63,10 @@ static void launch_heat(hipStream_t stream, const float* plane, int w, int h, in
   const long long sy = out->stride_y, sx = out->stride_x, sc = out->stride_c;
   const double* thr = heat_tab_thresholds(tab);
   const HeatScale hs = heat_scale(heat.good, heat.bad);
-  switch (out->dtype) {
-    case GZ_DT_U8: launch_emit_heat(stream, plane, w, h, pitch, (uint8_t*)out->data, sy, sx, sc, tab, thr, hs); break;
-    case GZ_DT_F32: launch_emit_heat(stream, plane, w, h, pitch, (float*)out->data, sy, sx, sc, tab, thr, hs); break;
-    case GZ_DT_F16: launch_emit_heat(stream, plane, w, h, pitch, (ingest_f16*)out->data, sy, sx, sc, tab, thr, hs); break;
-    case GZ_DT_BF16: launch_emit_heat(stream, plane, w, h, pitch, (ingest_bf16*)out->data, sy, sx, sc, tab, thr, hs); break;
-    default: launch_emit_heat(stream, plane, w, h, pitch, (uint16_t*)out->data, sy, sx, sc, tab, thr, hs); break;
-  }
+  with_sample_type(out->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_emit_heat(stream, plane, w, h, pitch, (T*)out->data, sy, sx, sc, tab, thr, hs);
+  });
 }
 
 // A window of the context's map plane: w x h from (x0, y0) on.  What a map and its heat map are emitted from where the
@@ -88,14 +85,11 @@ static int emit_heat(gz_ctx* c, const HeatRequest& heat, const MapWindow* win = 
     HIPCHK(c, upload_heat_tab(c->d_heat_tab, c->stream));
     c->made.heat = true;
   }
-  if (heat.out->consumer_stream) {
-    if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
-    HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, heat.out->consumer_stream));
-  }
+  TRY(outputs_after_consumers(c, c->stream, &c->ev_emit, {heat.out->consumer_stream}));
   if (win) launch_heat(c->stream, c->distmap + ((size_t)win->y0 * c->pitch + win->x0), win->w, win->h, c->pitch, heat, c->d_heat_tab);
   else launch_heat(c->stream, c->distmap, c->w, c->h, c->pitch, heat, c->d_heat_tab);
   KCHK(c);
-  if (heat.out->consumer_stream) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, heat.out->consumer_stream));
+  TRY(consumers_after_outputs(c, c->stream, c->ev_emit, {heat.out->consumer_stream}));
   return GZ_OK;
 }
 
@@ -106,7 +100,7 @@ int gz_heatmap_device(gz_ctx* c, double good, double bad, const gz_device_output
   if (c->pending.busy()) { c->err = "gz_heatmap_device while a Compare or phase-B work of the context is in flight"; return GZ_E_STATE; }
   if (!c->have_map_plane) { c->err = "the last comparison stored no distance map"; return GZ_E_STATE; }
   DeviceScope ds_(c);
-  if (const int rc = check_device_range(c->device, out->data, device_output_last(out, c->w, c->h), ingest_elem_size(out->dtype), "data", &c->err)) return rc;
+  if (const int rc = check_tensor_memory(c->device, tensor_view(out, c->w, c->h), "data", &c->err)) return rc;
   TRY(emit_heat(c, heat));
   if (out->consumer_stream) return GZ_OK;   // (ordered on the device: nothing to wait for here)
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -121,7 +115,7 @@ namespace {
 int heat_of_plane(int device, const float* device_plane, const float* host_plane, int w, int h, int pitch, const HeatRequest& heat) {
   const gz_device_output* out = heat.out;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
-  if (check_device_range(device, out->data, device_output_last(out, w, h), ingest_elem_size(out->dtype), "data", nullptr) != GZ_OK) return GZ_E_ARG;
+  if (check_tensor_memory(device, tensor_view(out, w, h), "data", nullptr) != GZ_OK) return GZ_E_ARG;
   if (device_plane && check_device_range(device, device_plane, (uint64_t)(h - 1) * (uint64_t)pitch + (uint64_t)(w - 1), sizeof(float), "map", nullptr) != GZ_OK)
     return GZ_E_ARG;
   if (!heat_thresholds().ok) return GZ_E_STATE;
@@ -134,22 +128,15 @@ int heat_of_plane(int device, const float* device_plane, const float* host_plane
   } else {
     TRY(regrow(c, nullptr, nullptr, 0, {{(void**)&s.d_lut, kHeatTabBytes}}));
   }
-  {
-    const hipError_t e = pool_stream_set_create(&s.ss, false, 0);
-    s.have_streams = e == hipSuccess;
-    if (e != hipSuccess) { stream_set_teardown(s.ss); s.ss = StreamSet(); (void)hipGetLastError(); return e == hipErrorOutOfMemory ? GZ_E_NOMEM : GZ_E_HIP; }
-  }
-  const hipStream_t stream = s.ss.own;
-  s.idle = false;
-  if (out->consumer_stream) {   // (a plane of the caller's is complete where the destination is free: on this stream)
-    TRY(own_event(c, &s.ev));
-    HIPCHK(c, emit_after_consumer(stream, s.ev, out->consumer_stream));
-  }
+  hipStream_t stream = nullptr;
+  TRY(s.open_streams(&stream));
+  // (a plane of the caller's is complete where the destination is free: on this stream)
+  TRY(outputs_after_consumers(c, stream, &s.ev, {out->consumer_stream}));
   HIPCHK(c, upload_heat_tab(s.d_lut, stream));
   if (host_plane) HIPCHK(c, hipMemcpyAsync(uploaded, host_plane, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice, stream));
   launch_heat(stream, host_plane ? uploaded : device_plane, w, h, pitch, heat, s.d_lut);
   KCHK(c);
-  if (out->consumer_stream) HIPCHK(c, consumer_after_emit(stream, s.ev, out->consumer_stream));
+  TRY(consumers_after_outputs(c, stream, s.ev, {out->consumer_stream}));
   HIPCHK(c, hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind this)
   s.idle = true;
   return GZ_OK;
@@ -157,11 +144,8 @@ int heat_of_plane(int device, const float* device_plane, const float* host_plane
 
 int heat_of_plane_entry(int device, const float* device_plane, const float* host_plane, int w, int h, int pitch, const HeatRequest& heat) {
   if ((!device_plane && !host_plane) || check_heat_request(heat, w, h) != GZ_OK || pitch < w) return GZ_E_ARG;   // (before any device call)
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  const int rc = heat_of_plane(device, device_plane, host_plane, w, h, pitch, heat);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return rc;
+  CallerDevice keep(device);
+  return heat_of_plane(device, device_plane, host_plane, w, h, pitch, heat);
 }
 }  // namespace
 

@@ -22,8 +22,7 @@ extern "C" {
 // The arguments alone: no device call (the library answers these without a GPU).
 static int check_linear_pixels(const gz_device_pixels* img, int w, int h, float scale) {
   if (check_device_pixels(img, w, h) != GZ_OK) return GZ_E_ARG;
-  if (img->dtype != GZ_DT_F32 && img->dtype != GZ_DT_F16 && img->dtype != GZ_DT_BF16) return GZ_E_ARG;
-  if (img->alpha) return GZ_E_ARG;
+  if (!tensor_float_dtype(img->dtype) || img->alpha) return GZ_E_ARG;
   if (!(scale > 0.0f && scale < INFINITY)) return GZ_E_ARG;   // (NaN fails every comparison)
   return GZ_OK;
 }
@@ -41,7 +40,7 @@ static LinearSource linear_source(const gz_device_pixels* img, float scale, int 
 
 // (the image's own extent: the extension reads no element outside it)
 static int check_linear_pointer(int device, const LinearSource* src, std::string* why) {
-  return check_device_pointer(device, src->img, src->w, src->h, why);
+  return check_tensor_memory(device, tensor_view(src->img, src->w, src->h), "data", why);
 }
 
 // k_ingest_linear on `stream`: src -> the three planes of a cw x ch canvas (the image's own size unless extended),
@@ -53,21 +52,11 @@ static hipError_t ingest_linear(hipStream_t stream, const LinearSource* src, int
   const gz_device_pixels* img = src->img;
   const long long sy = img->stride_y, sx = img->stride_x, sc = img->stride_c;
   const IngestExtent* ext = src->extended ? &src->ext : nullptr;
-  switch (img->dtype) {
-    case GZ_DT_F32: launch_ingest_linear(stream, (const float*)img->data, sy, sx, sc, cw, ch, src->scale, ext, lin, pitch, pstride, altered); break;
-    case GZ_DT_F16: launch_ingest_linear(stream, (const ingest_f16*)img->data, sy, sx, sc, cw, ch, src->scale, ext, lin, pitch, pstride, altered); break;
-    default: launch_ingest_linear(stream, (const ingest_bf16*)img->data, sy, sx, sc, cw, ch, src->scale, ext, lin, pitch, pstride, altered); break;
-  }
+  with_float_type(img->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_ingest_linear(stream, (const T*)img->data, sy, sx, sc, cw, ch, src->scale, ext, lin, pitch, pstride, altered);
+  });
   return hipSuccess;
-}
-
-// The producer's stream of a source: the context's stream goes on behind what it has enqueued so far.
-static int wait_for_producer(gz_ctx* c, const gz_device_pixels* img) {
-  if (!img->producer_stream) return GZ_OK;
-  if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
-  HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)img->producer_stream));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
-  return GZ_OK;
 }
 
 // (the context's device is current, src has passed check_linear_pixels and check_linear_pointer)
@@ -78,7 +67,7 @@ static int set_linear_device(gz_ctx* c, const LinearSource* src) {
   c->have_block_mask = c->have_distmap = false;
   c->orig_linear = true;
   c->orig_clamped = 0;
-  TRY(wait_for_producer(c, src->img));
+  TRY(wait_for_producer(c, src->img->producer_stream));
   void* res = nullptr;
   TRY(result_buffer(c, sizeof(unsigned), &res));
   unsigned* altered = c->d_max_bits + gz_ctx::kWordClamped;
@@ -96,11 +85,8 @@ gz_ctx* gz_create_from_device_linear(int device, int w, int h, const gz_device_p
     return nullptr;
   }
   const LinearSource src = linear_source(img, scale, w, h);
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  gz_ctx* c = create_context(device, w, h, nullptr, nullptr, 1.0f, err, &src);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return c;
+  CallerDevice keep(device);
+  return create_context(device, w, h, nullptr, nullptr, 1.0f, err, &src);
 }
 
 int gz_set_linear_device(gz_ctx* c, const gz_device_pixels* img, float scale) {
@@ -121,12 +107,12 @@ static int compare_device_linear(gz_ctx* c, const LinearSource* src, float* dist
   const MapWindow* win = src->extended ? &window : nullptr;
   if (const int rc = check_linear_pointer(c->device, src, &c->err)) return rc;
   if (map)
-    if (const int rc = check_device_range(c->device, map->data, device_map_last(map, src->w, src->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
+    if (const int rc = check_tensor_memory(c->device, tensor_view(map, src->w, src->h), "map", &c->err)) return rc;
   if (heat)
-    if (const int rc = check_device_range(c->device, heat->out->data, device_output_last(heat->out, src->w, src->h), ingest_elem_size(heat->out->dtype), "heat", &c->err)) return rc;
+    if (const int rc = check_tensor_memory(c->device, tensor_view(heat->out, src->w, src->h), "heat", &c->err)) return rc;
   TRY(pair_compare_state(c, who));
   pair_compare_drops(c);
-  TRY(wait_for_producer(c, src->img));
+  TRY(wait_for_producer(c, src->img->producer_stream));
   HIPCHK(c, ingest_linear(c->stream, src, c->w, c->h, c->lin[0], c->pitch, c->plane, c->d_max_bits + gz_ctx::kWordClamped));
   KCHK(c);
   const LinearTail tail = {win, clamped};
@@ -154,17 +140,13 @@ int gz_butteraugli_linear(int device, int w, int h, const gz_device_pixels* ref,
   const HeatRequest req{heat, good, bad};
   if (heat && check_heat_request(req, w, h) != GZ_OK) return GZ_E_ARG;
   const LinearSource src0 = linear_source(ref, scale, w, h), src1 = linear_source(other, scale, w, h);
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  CallerDevice keep(device);
   int rc = GZ_OK;
-  gz_ctx* c = create_context(device, w < 8 ? 8 : w, h < 8 ? 8 : h, nullptr, nullptr, 1.0f, &rc, &src0);
-  if (c) {
-    uint64_t altered = 0;
-    rc = compare_device_linear(c, &src1, distance, map, heat ? &req : nullptr, &altered, "gz_butteraugli_linear");
-    if (rc == GZ_OK && clamped) *clamped = c->orig_clamped + altered;   // (of both images)
-    gz_destroy(c);
-  }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
+  const CallContext ctx(create_context(device, w < 8 ? 8 : w, h < 8 ? 8 : h, nullptr, nullptr, 1.0f, &rc, &src0));
+  if (!ctx.c) return rc;
+  uint64_t altered = 0;
+  rc = compare_device_linear(ctx.c, &src1, distance, map, heat ? &req : nullptr, &altered, "gz_butteraugli_linear");
+  if (rc == GZ_OK && clamped) *clamped = ctx.c->orig_clamped + altered;   // (of both images)
   return rc;
 }
 

@@ -13,7 +13,7 @@ namespace {
 // The arguments alone: no device call (the library answers these without a GPU).
 static int check_float_output(const gz_device_output* out, int w, int h) {
   if (check_device_output(out, w, h) != GZ_OK) return GZ_E_ARG;
-  return out->dtype == GZ_DT_F32 || out->dtype == GZ_DT_F16 || out->dtype == GZ_DT_BF16 ? GZ_OK : GZ_E_ARG;
+  return tensor_float_dtype(out->dtype) ? GZ_OK : GZ_E_ARG;
 }
 static int check_sampled_pixels(const gz_device_pixels* img, int w, int h, int samples, float scale) {
   if (samples == GZ_SAMPLES_SRGB8) return check_device_pixels(img, w, h);
@@ -36,22 +36,6 @@ static gz_ctx* sampled_context(int device, int w, int h, const gz_device_pixels*
   return c;
 }
 
-// The stream contract of the outputs around the emit kernels on the context's stream: in front, the stream waits for
-// every consumer's stream; behind, every consumer's stream waits for the kernels.
-static int outputs_after_consumers(gz_ctx* c, std::initializer_list<void*> consumers) {
-  for (void* s : consumers) {
-    if (!s) continue;
-    if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
-    HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, s));
-  }
-  return GZ_OK;
-}
-static int consumers_after_outputs(gz_ctx* c, std::initializer_list<void*> consumers) {
-  for (void* s : consumers)
-    if (s) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, s));
-  return GZ_OK;
-}
-
 // k_emit_mask<T, MODE> for the element type of the destinations (one type for both: gz_mask_device converts a second
 // type in a second launch).
 template <int MODE, class T>
@@ -67,11 +51,7 @@ static void launch_mask_of_type(gz_ctx* c, const gz_device_output* mask, const g
 }
 template <int MODE>
 static void launch_mask(gz_ctx* c, int dtype, const gz_device_output* mask, const gz_device_output* dc, const gz_device_map* y) {
-  switch (dtype) {
-    case GZ_DT_F32: launch_mask_of_type<MODE, float>(c, mask, dc, y); break;
-    case GZ_DT_F16: launch_mask_of_type<MODE, ingest_f16>(c, mask, dc, y); break;
-    default: launch_mask_of_type<MODE, ingest_bf16>(c, mask, dc, y); break;
-  }
+  with_float_type(dtype, [&](auto tag) { launch_mask_of_type<MODE, typename decltype(tag)::type>(c, mask, dc, y); });
 }
 
 // Two scratch planes for image 0's half of DiffPrecompute: Malta's outputs, which nothing here computes.
@@ -83,9 +63,9 @@ static int mask_on_context(gz_ctx* c, const gz_device_pixels* img1, int samples,
   const hipStream_t stream = c->stream;
   for (const gz_device_output* o : {mask, dc})
     if (o)
-      if (const int rc = check_device_range(c->device, o->data, device_output_last(o, c->w, c->h), ingest_elem_size(o->dtype), "data", &c->err)) return rc;
+      if (const int rc = check_tensor_memory(c->device, tensor_view(o, c->w, c->h), "data", &c->err)) return rc;
   if (img1)
-    if (const int rc = check_device_pointer(c->device, img1, c->w, c->h, &c->err)) return rc;
+    if (const int rc = check_tensor_memory(c->device, tensor_view(img1, c->w, c->h), "data", &c->err)) return rc;
   MaskPrePack pk;
   {
     MaskIn in0[2];
@@ -99,7 +79,7 @@ static int mask_on_context(gz_ctx* c, const gz_device_pixels* img1, int samples,
   }
   const unsigned* altered = nullptr;
   if (img1) {
-    TRY(wait_for_producer(c, img1));
+    TRY(wait_for_producer(c, img1->producer_stream));
     if (samples == GZ_SAMPLES_LINEAR) {
       const LinearSource src = linear_source(img1, scale, c->w, c->h);
       void* res = nullptr;
@@ -109,13 +89,13 @@ static int mask_on_context(gz_ctx* c, const gz_device_pixels* img1, int samples,
       HIPCHK(c, hipMemcpyAsync(res, c->d_max_bits + gz_ctx::kWordClamped, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
       altered = (const unsigned*)res;
     } else {
-      launch_ingest(stream, img1, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+      launch_ingest(stream, tensor_view(img1, c->w, c->h), img1->background, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
       KCHK(c);
     }
     TRY(stage_opsin(c, stream));
   }
   TRY(stage_mask_blurs(c, stream, stream, pk));
-  TRY(outputs_after_consumers(c, {mask ? mask->consumer_stream : nullptr, dc ? dc->consumer_stream : nullptr}));
+  TRY(outputs_after_consumers(c, stream, &c->ev_emit, {mask ? mask->consumer_stream : nullptr, dc ? dc->consumer_stream : nullptr}));
   if (mask && dc && mask->dtype == dc->dtype) {
     launch_mask<kEmitMaskBoth>(c, mask->dtype, mask, dc, nullptr);
   } else {
@@ -123,7 +103,7 @@ static int mask_on_context(gz_ctx* c, const gz_device_pixels* img1, int samples,
     if (dc) launch_mask<kEmitMaskDc>(c, dc->dtype, nullptr, dc, nullptr);
   }
   KCHK(c);
-  TRY(consumers_after_outputs(c, {mask ? mask->consumer_stream : nullptr, dc ? dc->consumer_stream : nullptr}));
+  TRY(consumers_after_outputs(c, stream, c->ev_emit, {mask ? mask->consumer_stream : nullptr, dc ? dc->consumer_stream : nullptr}));
   HIPCHK(c, hipStreamSynchronize(stream));   // (the context's memory goes back to the pool behind this)
   if (altered) *clamped += *altered;
   return GZ_OK;
@@ -134,7 +114,7 @@ static int mask_on_context(gz_ctx* c, const gz_device_pixels* img1, int samples,
 // radius-20 pass pair, then the Y-only emit.  Nothing of the X plane runs.
 static int quant_on_context(gz_ctx* c, const gz_device_map* quant) {
   const hipStream_t stream = c->stream;
-  if (const int rc = check_device_range(c->device, quant->data, device_map_last(quant, c->w, c->h), ingest_elem_size(quant->dtype), "map", &c->err)) return rc;
+  if (const int rc = check_tensor_memory(c->device, tensor_view(quant, c->w, c->h), "map", &c->err)) return rc;
   const MaskIn y = {nullptr, c->lin[1], 0.0, 1.0, 1};
   const dim3 grid(gz_div_up(c->w, 1024), c->h, 1);
   {
@@ -164,29 +144,24 @@ static int quant_on_context(gz_ctx* c, const gz_device_map* quant) {
     PostStore<1> post; post.out[0] = c->myb2;
     TRY((blur_v<20, 1, PostStore<1>>(c, stream, ct, post, c->blur[B_MASKY1])));
   }
-  TRY(outputs_after_consumers(c, {quant->consumer_stream}));
+  TRY(outputs_after_consumers(c, stream, &c->ev_emit, {quant->consumer_stream}));
   launch_mask<kEmitMaskY>(c, quant->dtype, nullptr, nullptr, quant);
   KCHK(c);
-  TRY(consumers_after_outputs(c, {quant->consumer_stream}));
+  TRY(consumers_after_outputs(c, stream, c->ev_emit, {quant->consumer_stream}));
   HIPCHK(c, hipStreamSynchronize(stream));   // (the context's memory goes back to the pool behind this)
   return GZ_OK;
 }
 
 // xyb[] -> the three planes of `out`, each through k_emit_map at its own base.
 static int opsin_on_context(gz_ctx* c, const gz_device_output* out) {
-  if (const int rc = check_device_range(c->device, out->data, device_output_last(out, c->w, c->h), ingest_elem_size(out->dtype), "data", &c->err)) return rc;
-  TRY(outputs_after_consumers(c, {out->consumer_stream}));
-  const size_t elem = ingest_elem_size(out->dtype);
+  const TensorView v = tensor_view(out, c->w, c->h);
+  if (const int rc = check_tensor_memory(c->device, v, "data", &c->err)) return rc;
+  TRY(outputs_after_consumers(c, c->stream, &c->ev_emit, {out->consumer_stream}));
   for (int i = 0; i < 3; ++i) {
-    gz_device_map plane;
-    memset(&plane, 0, sizeof(plane));
-    plane.dtype = out->dtype;
-    plane.data = (char*)out->data + (size_t)i * (size_t)out->stride_c * elem;
-    plane.stride_y = out->stride_y; plane.stride_x = out->stride_x;
-    launch_map(c->stream, c->xyb[i], c->w, c->h, c->pitch, &plane);
+    launch_map(c->stream, c->xyb[i], c->w, c->h, c->pitch, tensor_select(v, 2, i));
     KCHK(c);
   }
-  TRY(consumers_after_outputs(c, {out->consumer_stream}));
+  TRY(consumers_after_outputs(c, c->stream, c->ev_emit, {out->consumer_stream}));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the context's memory goes back to the pool behind this)
   return GZ_OK;
 }
@@ -199,17 +174,12 @@ int gz_opsin_device(int device, int w, int h, const gz_device_pixels* img, int s
                     uint64_t* clamped) {
   if (w < 8 || h < 8) return GZ_E_ARG;   // (all of these before any device call)
   if (check_sampled_pixels(img, w, h, samples, scale) != GZ_OK || check_float_output(xyb, w, h) != GZ_OK) return GZ_E_ARG;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  CallerDevice keep(device);
   int rc = GZ_OK;
   unsigned long long altered = 0;
-  gz_ctx* c = sampled_context(device, w, h, img, samples, scale, &rc, &altered);
-  if (c) {
-    rc = opsin_on_context(c, xyb);
-    if (rc == GZ_OK && clamped) *clamped = altered;
-    gz_destroy(c);
-  }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
+  const CallContext ctx(sampled_context(device, w, h, img, samples, scale, &rc, &altered));
+  if (ctx.c) rc = opsin_on_context(ctx.c, xyb);
+  if (rc == GZ_OK && clamped) *clamped = altered;
   return rc;
 }
 
@@ -220,17 +190,12 @@ int gz_mask_device(int device, int w, int h, const gz_device_pixels* img0, const
   if (img1 && check_sampled_pixels(img1, w, h, samples, scale) != GZ_OK) return GZ_E_ARG;
   if (mask && check_float_output(mask, w, h) != GZ_OK) return GZ_E_ARG;
   if (mask_dc && check_float_output(mask_dc, w, h) != GZ_OK) return GZ_E_ARG;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  CallerDevice keep(device);
   int rc = GZ_OK;
   unsigned long long altered = 0;
-  gz_ctx* c = sampled_context(device, w, h, img0, samples, scale, &rc, &altered);
-  if (c) {
-    rc = mask_on_context(c, img1, samples, scale, mask, mask_dc, &altered);
-    if (rc == GZ_OK && clamped) *clamped = altered;   // (of both images)
-    gz_destroy(c);
-  }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
+  const CallContext ctx(sampled_context(device, w, h, img0, samples, scale, &rc, &altered));
+  if (ctx.c) rc = mask_on_context(ctx.c, img1, samples, scale, mask, mask_dc, &altered);
+  if (rc == GZ_OK && clamped) *clamped = altered;   // (of both images)
   return rc;
 }
 
@@ -238,17 +203,12 @@ int gz_adaptive_quantization(int device, int w, int h, const gz_device_pixels* i
                              uint64_t* clamped) {
   if (w < 16 || h < 16) return GZ_E_ARG;   // (the reference returns false; all of these before any device call)
   if (check_linear_pixels(img, w, h, scale) != GZ_OK || check_device_map(quant, w, h) != GZ_OK) return GZ_E_ARG;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
+  CallerDevice keep(device);
   int rc = GZ_OK;
   unsigned long long altered = 0;
-  gz_ctx* c = sampled_context(device, w, h, img, GZ_SAMPLES_LINEAR, scale, &rc, &altered);
-  if (c) {
-    rc = quant_on_context(c, quant);
-    if (rc == GZ_OK && clamped) *clamped = altered;
-    gz_destroy(c);
-  }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
+  const CallContext ctx(sampled_context(device, w, h, img, GZ_SAMPLES_LINEAR, scale, &rc, &altered));
+  if (ctx.c) rc = quant_on_context(ctx.c, quant);
+  if (rc == GZ_OK && clamped) *clamped = altered;
   return rc;
 }
 

@@ -7,55 +7,25 @@
 
 extern "C" {
 
-// The arguments alone: no device call (the library answers these without a GPU).
-static int check_device_map(const gz_device_map* map, int w, int h) {
-  if (!map || map->struct_size != (int)sizeof(gz_device_map) || !map->data) return GZ_E_ARG;
-  if (map->dtype != GZ_DT_F32 && map->dtype != GZ_DT_F16 && map->dtype != GZ_DT_BF16) return GZ_E_ARG;
-  if (map->stride_y < 0 || map->stride_x < 0) return GZ_E_ARG;
-  if (w <= 0 || h <= 0 || w >= (1 << 16) || h >= (1 << 16)) return GZ_E_ARG;
-  // the last element's offset (h-1) sy + (w-1) sx in 62 bits: every term is bounded before it is formed
-  const uint64_t lim = (1ull << 62) - 1;
-  const uint64_t sy = (uint64_t)map->stride_y, sx = (uint64_t)map->stride_x;
-  if ((h > 1 && sy > lim / (uint64_t)(h - 1)) || (w > 1 && sx > lim / (uint64_t)(w - 1))) return GZ_E_ARG;
-  if (sy * (uint64_t)(h - 1) + sx * (uint64_t)(w - 1) > lim) return GZ_E_ARG;
-  // No two of the w * h elements at one address: check_device_output's rule for two dimensions.
-  std::pair<uint64_t, uint64_t> dim[2] = {{sy, (uint64_t)h}, {sx, (uint64_t)w}};
-  std::sort(dim, dim + 2);
-  uint64_t least = 1;
-  for (const auto& d : dim) {
-    if (d.second == 1) continue;
-    if (d.first < least) return GZ_E_ARG;
-    least = d.first * d.second;
-  }
-  return GZ_OK;
-}
-
-static uint64_t device_map_last(const gz_device_map* map, int w, int h) {
-  return (uint64_t)map->stride_y * (uint64_t)(h - 1) + (uint64_t)map->stride_x * (uint64_t)(w - 1);
-}
-
-// k_emit_map on `stream`: plane (pitch floats per row) -> map (checked by the caller).
-static void launch_map(hipStream_t stream, const float* plane, int w, int h, int pitch, const gz_device_map* map) {
-  const long long sy = map->stride_y, sx = map->stride_x;
-  switch (map->dtype) {
-    case GZ_DT_F32: launch_emit_map(stream, plane, w, h, pitch, (float*)map->data, sy, sx); break;
-    case GZ_DT_F16: launch_emit_map(stream, plane, w, h, pitch, (ingest_f16*)map->data, sy, sx); break;
-    default: launch_emit_map(stream, plane, w, h, pitch, (ingest_bf16*)map->data, sy, sx); break;
-  }
+// k_emit_map on `stream`: plane (pitch floats per row) -> map (y, x: w x h, checked by the caller: check_device_map,
+// tensor.h -- or one plane of a checked output).
+static void launch_map(hipStream_t stream, const float* plane, int w, int h, int pitch, const TensorView& map) {
+  const long long sy = map.dim[0].stride, sx = map.dim[1].stride;
+  with_float_type(map.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    launch_emit_map(stream, plane, w, h, pitch, (T*)map.data, sy, sx);
+  });
 }
 
 // c->distmap -> map on the context's stream, under gz_device_output's stream contract in both directions (the
 // consumer's stream is waited for before the kernel and waits for it afterwards).  Nothing is waited for on the host.
 // win (may be NULL: the whole plane): the window of the plane that map, which is of ITS size, takes.
 static int emit_distmap(gz_ctx* c, const gz_device_map* map, const MapWindow* win = nullptr) {
-  if (map->consumer_stream) {
-    if (!c->ev_emit) TRY(own_event(c, &c->ev_emit));
-    HIPCHK(c, emit_after_consumer(c->stream, c->ev_emit, map->consumer_stream));
-  }
-  if (win) launch_map(c->stream, c->distmap + ((size_t)win->y0 * c->pitch + win->x0), win->w, win->h, c->pitch, map);
-  else launch_map(c->stream, c->distmap, c->w, c->h, c->pitch, map);
+  TRY(outputs_after_consumers(c, c->stream, &c->ev_emit, {map->consumer_stream}));
+  if (win) launch_map(c->stream, c->distmap + ((size_t)win->y0 * c->pitch + win->x0), win->w, win->h, c->pitch, tensor_view(map, win->w, win->h));
+  else launch_map(c->stream, c->distmap, c->w, c->h, c->pitch, tensor_view(map, c->w, c->h));
   KCHK(c);
-  if (map->consumer_stream) HIPCHK(c, consumer_after_emit(c->stream, c->ev_emit, map->consumer_stream));
+  TRY(consumers_after_outputs(c, c->stream, c->ev_emit, {map->consumer_stream}));
   return GZ_OK;
 }
 
@@ -117,20 +87,16 @@ static int compare_device_pixels(gz_ctx* c, const gz_device_pixels* other, float
   if (map && check_device_map(map, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   if (heat && check_heat_request(*heat, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   DeviceScope ds_(c);
-  if (const int rc = check_device_pointer(c->device, other, c->w, c->h, &c->err)) return rc;
+  if (const int rc = check_tensor_memory(c->device, tensor_view(other, c->w, c->h), "data", &c->err)) return rc;
   if (map)
-    if (const int rc = check_device_range(c->device, map->data, device_map_last(map, c->w, c->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
+    if (const int rc = check_tensor_memory(c->device, tensor_view(map, c->w, c->h), "map", &c->err)) return rc;
   if (heat)
-    if (const int rc = check_device_range(c->device, heat->out->data, device_output_last(heat->out, c->w, c->h), ingest_elem_size(heat->out->dtype), "heat", &c->err)) return rc;
+    if (const int rc = check_tensor_memory(c->device, tensor_view(heat->out, c->w, c->h), "heat", &c->err)) return rc;
   TRY(pair_compare_state(c, heat ? "gz_compare_device_pixels_heat" : "gz_compare_device_pixels"));
   pair_compare_drops(c);
-  if (other->producer_stream) {   // behind what the producer has enqueued so far, without waiting for it on the host
-    if (!c->ev_ingest) TRY(own_event(c, &c->ev_ingest));
-    HIPCHK(c, hipEventRecord(c->ev_ingest, (hipStream_t)other->producer_stream));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ingest, 0));
-  }
+  TRY(wait_for_producer(c, other->producer_stream));
   // the packed bytes go to the reconstruction's scratch: d_rgb is the original's, and stays
-  launch_ingest(c->stream, other, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
+  launch_ingest(c->stream, tensor_view(other, c->w, c->h), other->background, c->w, c->h, c->d_srgb_out, c->d_srgb_lut, c->lin[0], c->pitch, c->plane);
   KCHK(c);
   return pair_compare_tail(c, distance, map, nullptr, heat);   // (its synchronise: `other` is read when the call returns)
 }
@@ -161,7 +127,7 @@ int gz_distmap_device(gz_ctx* c, const gz_device_map* map) {
   if (!c) return GZ_E_ARG;
   if (check_device_map(map, c->w, c->h) != GZ_OK) return GZ_E_ARG;
   DeviceScope ds_(c);
-  if (const int rc = check_device_range(c->device, map->data, device_map_last(map, c->w, c->h), ingest_elem_size(map->dtype), "map", &c->err)) return rc;
+  if (const int rc = check_tensor_memory(c->device, tensor_view(map, c->w, c->h), "map", &c->err)) return rc;
   if (!c->have_map_plane) { c->err = "the last comparison stored no distance map"; return GZ_E_STATE; }
   TRY(emit_distmap(c, map));
   if (map->consumer_stream) return GZ_OK;   // (ordered on the device: nothing to wait for here)
@@ -171,14 +137,15 @@ int gz_distmap_device(gz_ctx* c, const gz_device_map* map) {
 
 #ifndef GZ_NO_PROBES
 namespace {
-struct ProbeMapScratch {   // the plane from the device pool and a pooled event, given back on every path
+struct ProbeMapScratch {   // the plane from the device pool and a pooled event (t: its record), given back on every path
+  gz_ctx t;
   void* plane = nullptr;
   hipEvent_t ev = nullptr;
-  ~ProbeMapScratch() { pool_free(plane); pool_event_destroy(ev); }
+  ~ProbeMapScratch() { pool_free(plane); release_owned(&t); }
 };
 int probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map) {
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
-  if (check_device_range(device, map->data, device_map_last(map, w, h), ingest_elem_size(map->dtype), "map", nullptr) != GZ_OK) return GZ_E_ARG;
+  if (check_tensor_memory(device, tensor_view(map, w, h), "map", nullptr) != GZ_OK) return GZ_E_ARG;
   ProbeMapScratch s;
   const size_t bytes = sizeof(float) * (size_t)w * h;
   {
@@ -187,13 +154,10 @@ int probe_emit_map(int device, const float* host_plane, int w, int h, const gz_d
   }
   const hipStream_t stream = (hipStream_t)0;
   if (hipMemcpy(s.plane, host_plane, bytes, hipMemcpyHostToDevice) != hipSuccess) return GZ_E_HIP;
-  if (map->consumer_stream) {
-    if (pool_event_create(&s.ev) != hipSuccess) { s.ev = nullptr; return GZ_E_HIP; }
-    if (emit_after_consumer(stream, s.ev, map->consumer_stream) != hipSuccess) return GZ_E_HIP;
-  }
-  launch_map(stream, (const float*)s.plane, w, h, w, map);
+  if (outputs_after_consumers(&s.t, stream, &s.ev, {map->consumer_stream}) != GZ_OK) return GZ_E_HIP;
+  launch_map(stream, (const float*)s.plane, w, h, w, tensor_view(map, w, h));
   int rc = hipGetLastError() == hipSuccess ? GZ_OK : GZ_E_HIP;
-  if (rc == GZ_OK && map->consumer_stream && consumer_after_emit(stream, s.ev, map->consumer_stream) != hipSuccess) rc = GZ_E_HIP;
+  if (rc == GZ_OK && consumers_after_outputs(&s.t, stream, s.ev, {map->consumer_stream}) != GZ_OK) rc = GZ_E_HIP;
   if (hipStreamSynchronize(stream) != hipSuccess) rc = GZ_E_HIP;   // (the plane goes back to the pool behind this)
   return rc;
 }
@@ -201,11 +165,8 @@ int probe_emit_map(int device, const float* host_plane, int w, int h, const gz_d
 
 int gz_probe_emit_map(int device, const float* host_plane, int w, int h, const gz_device_map* map) {
   if (!host_plane || check_device_map(map, w, h) != GZ_OK) return GZ_E_ARG;   // (before any device call)
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  const int rc = probe_emit_map(device, host_plane, w, h, map);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return rc;
+  CallerDevice keep(device);
+  return probe_emit_map(device, host_plane, w, h, map);
 }
 #endif  // GZ_NO_PROBES
 

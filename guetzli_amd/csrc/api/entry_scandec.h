@@ -73,8 +73,7 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
                 int16_t* host_coeffs, int16_t* host_input, int* large_coeff, gz_scan_result* result) {
   const int w = sc->w, h = sc->h;
   if (probe_device(device) != GZ_OK) return GZ_E_NO_DEVICE;
-  if (out && check_device_range(device, out->data, device_output_last(out, w, h), ingest_elem_size(out->dtype), "data", nullptr) != GZ_OK)
-    return GZ_E_ARG;
+  if (out && check_tensor_memory(device, tensor_view(out, w, h), "data", nullptr) != GZ_OK) return GZ_E_ARG;
   const size_t end = scandec_data_end(sc->data, (size_t)sc->len);
   g.end_bits = (unsigned)(end * 8);
   g.nsub = std::max(1, (int)((end + (size_t)g.subseq_bytes - 1) / (size_t)g.subseq_bytes));
@@ -82,12 +81,7 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   result->subsequences = g.nsub;
   DecodeScratch s;
   gz_ctx* c = &s.t;
-  c->device = device;
-  c->w = w; c->h = h;
-  c->bw = (w + 7) / 8; c->bh = (h + 7) / 8; c->nb = c->bw * c->bh;
-  c->pitch = w;
-  c->plane = (size_t)w * h;
-  set_frame(c, sc->chroma_factor);
+  s.set_frame_geometry(device, w, h, sc->chroma_factor);
   const int max_tiles = gz_div_up(g.nsub, kScanTile) + 1;
   const size_t upload = std::max<size_t>(end, 1);
   const ScanDecLayout l = scandec_layout(upload, g.nsub, nwg, rounds, g.total, scan_state_bytes(max_tiles));
@@ -106,13 +100,8 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
                                         {(void**)&c->d_srgb_out, (size_t)3 * w * h}, {(void**)&s.d_lut, sizeof(float) * 256}}));
   }
   uint8_t* const d = s.d_scan;
-  {
-    const hipError_t e = pool_stream_set_create(&s.ss, false, 0);
-    s.have_streams = e == hipSuccess;
-    if (e != hipSuccess) { stream_set_teardown(s.ss); s.ss = StreamSet(); (void)hipGetLastError(); return e == hipErrorOutOfMemory ? GZ_E_NOMEM : GZ_E_HIP; }
-  }
-  const hipStream_t stream = s.ss.own;
-  s.idle = false;
+  hipStream_t stream = nullptr;
+  TRY(s.open_streams(&stream));
   const ScanDecTables* d_T = (const ScanDecTables*)(d + l.tables);
   const uint8_t* d_data = d + l.data;
   ScanDecState st;
@@ -183,16 +172,13 @@ int decode_scan(int device, const gz_scan* sc, const ScanDecTables& T, ScanDecGe
   if (host_coeffs) HIPCHK(c, hipMemcpyAsync(host_coeffs, c->d_cand, (size_t)c->nblk * 128, hipMemcpyDeviceToHost, stream));
   if (host_input) HIPCHK(c, hipMemcpyAsync(host_input, c->d_cand, coeff_bytes, hipMemcpyDeviceToHost, stream));
   if (out) {
-    if (out->consumer_stream) {
-      TRY(own_event(c, &s.ev));
-      HIPCHK(c, emit_after_consumer(stream, s.ev, out->consumer_stream));
-    }
+    TRY(outputs_after_consumers(c, stream, &s.ev, {out->consumer_stream}));
     TRY(stage_reconstruct(c, stream, c->d_cand, nullptr, c->d_srgb_out));
-    if (out->dtype != GZ_DT_U8 && out->dtype != GZ_DT_U16)
+    if (tensor_float_dtype(out->dtype))
       HIPCHK(c, hipMemcpyAsync(s.d_lut, emit_lut(), sizeof(float) * 256, hipMemcpyHostToDevice, stream));
     launch_emit(stream, c->d_srgb_out, w, h, out, s.d_lut);
     KCHK(c);
-    if (out->consumer_stream) HIPCHK(c, consumer_after_emit(stream, s.ev, out->consumer_stream));
+    TRY(consumers_after_outputs(c, stream, s.ev, {out->consumer_stream}));
   }
   HIPCHK(c, hipStreamSynchronize(stream));   // (the temporaries go back to the pool behind this)
   s.idle = true;
@@ -213,11 +199,8 @@ int decode_scan_entry(int device, const gz_scan* sc, const gz_device_output* out
   int subseq = 0, rounds = 0;
   if (const int rc = check_scan(sc, &T, &g, &subseq, &rounds)) return rc;
   if (out && check_device_output(out, sc->w, sc->h) != GZ_OK) return GZ_E_ARG;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-  const int rc = decode_scan(device, sc, T, g, rounds, out, host_coeffs, host_input, large_coeff, result);
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);   // the caller's device stays current
-  return rc;
+  CallerDevice keep(device);
+  return decode_scan(device, sc, T, g, rounds, out, host_coeffs, host_input, large_coeff, result);
 }
 }  // namespace
 

@@ -21,6 +21,7 @@
 #include <string>
 #include <sched.h>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -51,6 +52,7 @@ using namespace gz;
 // functions of the headers above, instantiated where they are launched):
 #include "api/plans.h"          // blur plans, Malta normalisations, PsychoImage planes
 #include "api/context.h"        // pools, gz_ctx, error macros, plane arena
+#include "api/tensor.h"         // the callers' strided device tensors: one view, its checks, an adapter per ABI struct
 #include "api/chain.h"          // the Compare chain's stages on three streams
 #include "api/entry_context.h"  // gz_create / gz_destroy / ...
 #include "api/entry_compare.h"  // block path + gz_compare*

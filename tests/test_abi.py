@@ -119,6 +119,21 @@ def test_host_side_candidate_ranking(lib_path):
     assert off[-1] > 500
 
 
+def test_tensor_argument_rules_stand_alone(tmp_path):
+    """tests/cpp/tensor_args.cc: the one extent rule, distinct-addresses rule and last-offset function behind every
+    device-tensor entry (guetzli_amd/csrc/api/tensor.h) and the six ABI structs' adapters, compiled without HIP and without
+    the emulation -- every small view against brute force, the 62-bit boundary, each struct's own rules -- as a plain
+    program with AddressSanitizer and UBSan.  Its own process, nothing preloaded."""
+    import subprocess
+    exe = str(tmp_path / "tensor_args")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+                    "-Werror", os.path.join(ROOT, "tests", "cpp", "tensor_args.cc"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    print(out.stdout)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "tensor arguments: all as expected" in out.stdout
+
+
 def test_new_entry_points_reject_bad_arguments(lib_path):
     """Phase-B / JPEG-input / dct_double entry points: null context or buffers give GZ_E_ARG
     (never a crash, never a fallback)."""
