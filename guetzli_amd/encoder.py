@@ -10,6 +10,8 @@ import numpy as np
 
 import time
 
+from . import device_arrays as da
+from .device_arrays import is_device_resident   # (its home; importable and patchable here, as ever)
 from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_batch, device_map, device_map_batch, device_output, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,9 +171,7 @@ class HostLibrary:
         with the y and x strides; None: opaque), background = the bytes (r, g, b) such pixels are blended over:
         (v * a + bg * (255 - a) + 128) // 255.  Returns what process() returns."""
         code = DTYPE_CODES.get(dtype, dtype)
-        alpha = 0 if alpha_offset is None else int(ptr) + int(alpha_offset) * ITEMSIZE[code]
-        if alpha_offset is not None and not alpha:
-            raise ValueError("an alpha sample at address 0")
+        alpha = da.alpha_address(ptr, alpha_offset, ITEMSIZE[code])
         image = device_pixels(ptr, code, strides, stream, alpha, _background(background) or (0, 0, 0))
         return self._process(image, w, h, quality, target, device, True, try_420, force_420,
                              use_silver_screen, lookahead, new_model, want_trace)
@@ -401,84 +401,6 @@ def blend_on_background(pixels, background):
     return ((v * a + bg * (255 - a) + 128) // 255).astype(np.uint8)
 
 
-def is_device_resident(x):
-    """A torch tensor on a GPU, or any object that exports __cuda_array_interface__."""
-    return bool(getattr(x, "is_cuda", False)) or hasattr(x, "__cuda_array_interface__")
-
-
-def _layout_strides(shape, strides, layout, background=None):
-    """(w, h, (stride_y, stride_x, stride_c), alpha offset or None) of an image of `shape` with element `strides`:
-    2-D is grey (the one value for all three channels), 3-D is "HWC" or "CHW" with 3 channels, 1 (grey) or -- only
-    with background= -- 2 (grey + alpha) or 4 (RGBA).  layout=None takes whichever of the first / last dimension is
-    3 and refuses a shape where both are; where neither is, whichever is 1 (with background=: 1, 2 or 4), by the same
-    rule."""
-    if len(shape) == 2:
-        (h, w), (sy, sx) = shape, strides
-        return w, h, (sy, sx, 0), None
-    if len(shape) != 3:
-        raise ValueError(f"an image has 2 or 3 dimensions, not {len(shape)}")
-    need_background = f"shape {tuple(shape)}: pixels with alpha are blended only over a background that is named: background=(r, g, b)"
-    if layout is None:
-        first, last = shape[0] == 3, shape[2] == 3
-        if not first and not last:
-            counts = (1,) if background is None else (1, 2, 4)
-            first, last = shape[0] in counts, shape[2] in counts
-            if not first and not last:
-                if background is None and (shape[0] in (2, 4) or shape[2] in (2, 4)):
-                    raise ValueError(need_background)
-                raise ValueError(f"shape {tuple(shape)}: neither the first nor the last dimension is 3"
-                                 + (", 1, 2 or 4" if background is not None else " or 1"))
-        if first and last:
-            raise ValueError(f"shape {tuple(shape)} is ambiguous: say layout='HWC' or layout='CHW'")
-        layout = "CHW" if first else "HWC"
-    if layout == "HWC":
-        (h, w, ch), (sy, sx, sc) = shape, strides
-    elif layout == "CHW":
-        (ch, h, w), (sc, sy, sx) = shape, strides
-    else:
-        raise ValueError(f"layout {layout!r}: 'HWC', 'CHW' or None")
-    if ch in (2, 4) and background is None:
-        raise ValueError(need_background)
-    if ch not in (1, 2, 3, 4):
-        raise ValueError(f"shape {tuple(shape)} has {ch} channels in layout {layout}, not 1, 2, 3 or 4")
-    alpha = (ch - 1) * sc if ch in (2, 4) else None   # the last channel
-    return w, h, (sy, sx, sc if ch >= 3 else 0), alpha
-
-
-def _device_source(x, layout, device, background=None):
-    """(ptr, w, h, dtype name, element strides, producer stream, device ordinal, alpha offset) of a device-resident image."""
-    if getattr(x, "is_cuda", False):   # a torch tensor
-        import torch
-        name = str(x.dtype).replace("torch.", "")
-        if name not in DTYPE_CODES:
-            raise TypeError(f"dtype {x.dtype}: uint8, uint16, float32, float16 or bfloat16")
-        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        if device is not None and device != ordinal:
-            raise ValueError(f"the tensor lives on device {ordinal}, device={device} was asked for")
-        w, h, strides, alpha = _layout_strides(tuple(x.shape), tuple(x.stride()), layout, background)
-        return x.data_ptr(), w, h, name, strides, torch.cuda.current_stream(x.device).cuda_stream, ordinal, alpha
-    cai = x.__cuda_array_interface__
-    dt = np.dtype(cai["typestr"])
-    if dt.name not in DTYPE_CODES:   # (numpy has no bfloat16: such arrays come as torch tensors)
-        raise TypeError(f"dtype {dt}: uint8, uint16, float32 or float16")
-    shape = tuple(cai["shape"])
-    if cai.get("strides") is None:
-        byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
-    else:
-        byte_strides = tuple(cai["strides"])
-    if any(b % dt.itemsize for b in byte_strides):
-        raise ValueError("strides that are no multiple of the element size")
-    w, h, strides, alpha = _layout_strides(shape, tuple(b // dt.itemsize for b in byte_strides), layout, background)
-    # the interface's stream: None / absent = nothing to wait for; 1 = the legacy default stream, with which the
-    # context's (blocking) streams synchronise by themselves: nothing to hand over; 2 = the per-thread default stream,
-    # which orders itself against nobody: handed over as it is -- it is hipStreamPerThread's handle too, and it names the
-    # stream of the thread that makes the call (process_many, whose calls run on other threads, refuses it)
-    stream = cai.get("stream") or 0
-    if stream == 1:
-        stream = 0
-    return cai["data"][0], w, h, dt.name, strides, stream, 0 if device is None else device, alpha
-
-
 PER_THREAD_STREAM = 2   # hipStreamPerThread: the default stream of whichever thread uses the handle
 
 
@@ -487,76 +409,6 @@ class _Job:
 
     def __init__(self, run, producer=0, keep=None):
         self.run, self.producer, self.keep = run, producer, keep   # keep: the object that owns the device memory
-
-
-def _strides_alias(strides, counts):
-    """gz_device_output's test: with the dimensions ordered by stride, a stride smaller than the extent (stride *
-    count) of the dimension before it, or smaller than 1, lets two elements share an address.  A dimension of one
-    element does not count."""
-    least = 1
-    for stride, count in sorted(zip(strides, counts)):
-        if count == 1:
-            continue
-        if stride < least:
-            return True
-        least = stride * count
-    return False
-
-
-def _device_destination(x, w, h, layout, device):
-    """(ptr, dtype name, element strides (y, x, c), consumer stream, device ordinal) of the device-resident image `x`
-    that is to receive w x h decoded pixels in `layout`."""
-    if layout not in ("HWC", "CHW"):
-        raise ValueError(f"layout {layout!r}: 'HWC' or 'CHW'")
-    want = (h, w, 3) if layout == "HWC" else (3, h, w)
-    if getattr(x, "is_cuda", False):   # a torch tensor
-        import torch
-        name = str(x.dtype).replace("torch.", "")
-        if name not in DTYPE_CODES:
-            raise TypeError(f"dtype {x.dtype}: uint8, uint16, float32, float16 or bfloat16")
-        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        if device is not None and device != ordinal:
-            raise ValueError(f"the tensor lives on device {ordinal}, device={device} was asked for")
-        shape, strides = tuple(x.shape), tuple(x.stride())
-        ptr, stream = x.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream
-    else:
-        cai = x.__cuda_array_interface__
-        dt = np.dtype(cai["typestr"])
-        if dt.name not in DTYPE_CODES:
-            raise TypeError(f"dtype {dt}: uint8, uint16, float32 or float16")
-        if cai["data"][1]:
-            raise ValueError("out= is read-only (its __cuda_array_interface__ says so)")
-        name, shape = dt.name, tuple(cai["shape"])
-        if cai.get("strides") is None:
-            byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
-        else:
-            byte_strides = tuple(cai["strides"])
-        if any(b % dt.itemsize for b in byte_strides):
-            raise ValueError("strides that are no multiple of the element size")
-        strides = tuple(b // dt.itemsize for b in byte_strides)
-        stream = cai.get("stream") or 0   # (as _device_source reads it)
-        if stream == 1:
-            stream = 0
-        ptr, ordinal = cai["data"][0], 0 if device is None else device
-    if shape != want:
-        raise ValueError(f"out= has shape {shape}, the JPEG decodes to {want} in layout {layout}")
-    sy, sx, sc = strides if layout == "HWC" else (strides[1], strides[2], strides[0])
-    if min(sy, sx, sc) < 0:
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
-    if _strides_alias((sy, sx, sc), (h, w, 3)):
-        raise ValueError(f"out= has strides {strides} under which two of its elements share an address (an expanded view?)")
-    return ptr, name, (sy, sx, sc), stream, ordinal
-
-
-def _new_device_tensor(w, h, dtype, layout, ordinal):
-    """A fresh torch tensor on GPU `ordinal` for w x h decoded pixels, from the calling thread's current stream."""
-    import torch
-    name = str(dtype).replace("torch.", "")
-    if name not in DTYPE_CODES:
-        raise TypeError(f"dtype {dtype}: uint8, uint16, float32, float16 or bfloat16")
-    if layout not in ("HWC", "CHW"):
-        raise ValueError(f"layout {layout!r}: 'HWC' or 'CHW'")
-    return torch.empty((h, w, 3) if layout == "HWC" else (3, h, w), dtype=getattr(torch, name), device=f"cuda:{ordinal}")
 
 
 def decode(jpeg, out=None, dtype="uint8", layout="HWC", device=None, stream=None, entropy="host"):
@@ -604,18 +456,19 @@ def _decode(jpeg, out, dtype, layout, device, stream, entropy, subseq_bytes=0, m
     w, h = _jpeg_dimensions(jpeg)   # (the frame header alone: the stream is read once, by the decode, which checks the size)
     if w <= 0 or h <= 0:
         raise ValueError("not a JPEG: no frame header")
+    shape = da.image_shape(w, h, layout)   # (layout=None is refused: only decoded= and heatmap= guess)
     if out is None:
         if device is None:
             import torch
             device = torch.cuda.current_device()
-        out = _new_device_tensor(w, h, dtype, layout, device)
-    ptr, name, strides, consumer, ordinal = _device_destination(out, w, h, layout, device)
-    consumer = consumer if stream is None else int(stream)
+        out = da.new_tensor(shape, dtype, device)
+    dst = da.image_destination(out, w, h, layout, da.DTYPES, device, "out=")
+    consumer = da.stream_or(stream, dst.stream)
     if entropy == "host":   # (the call every decode made before there was a choice)
-        lib.decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h))
+        lib.decode_jpeg_device(jpeg, dst.ptr, dst.dtype, dst.strides, stream=consumer, device=dst.ordinal, size=(w, h))
         return out, none
-    return out, lib.decode_jpeg_device_entropy(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h), entropy=entropy,
-                                               subseq_bytes=subseq_bytes, max_sync_rounds=max_sync_rounds)
+    return out, lib.decode_jpeg_device_entropy(jpeg, dst.ptr, dst.dtype, dst.strides, stream=consumer, device=dst.ordinal, size=(w, h),
+                                               entropy=entropy, subseq_bytes=subseq_bytes, max_sync_rounds=max_sync_rounds)
 
 
 def _with_decoded(job, decoded, w, h, ordinal):
@@ -623,19 +476,13 @@ def _with_decoded(job, decoded, w, h, ordinal):
     mechanism -- into decoded= (True: a fresh uint8 [h][w][3] tensor on the encode's device).  Allocation and consumer
     stream are taken here, in the CALLER's thread."""
     if decoded is True:
-        decoded = _new_device_tensor(w, h, "uint8", "HWC", ordinal)
-    elif not is_device_resident(decoded):
-        raise TypeError("decoded=: True, or a device-resident image to fill")
-    layout = "HWC"
-    shape = tuple(decoded.shape) if hasattr(decoded, "shape") else tuple(decoded.__cuda_array_interface__["shape"])
-    if len(shape) == 3 and shape[0] == 3 and shape[2] != 3:
-        layout = "CHW"
-    ptr, name, strides, consumer, ordinal = _device_destination(decoded, w, h, layout, ordinal)
+        decoded = da.new_tensor((h, w, 3), "uint8", ordinal)
+    dst = da.image_destination(decoded, w, h, None, da.DTYPES, ordinal, "decoded=")
 
     def run(**kw):
         jpeg, info = job.run(**kw)
         t0 = time.perf_counter()
-        load_host().decode_jpeg_device(jpeg, ptr, name, strides, stream=consumer, device=ordinal, size=(w, h))
+        load_host().decode_jpeg_device(jpeg, dst.ptr, dst.dtype, dst.strides, stream=dst.stream, device=dst.ordinal, size=(w, h))
         info.setdefault("timers", {})["decode_output"] = time.perf_counter() - t0
         info["decoded"] = decoded
         return jpeg, info
@@ -647,7 +494,8 @@ def _prepared(rgb, layout, device, stream, background=None, decoded=None):
     if decoded is not None and decoded is not False:
         job = _prepared(rgb, layout, device, stream, background)
         if is_device_resident(rgb):
-            _, w, h, _, _, _, ordinal, _ = _device_source(rgb, layout, device, _background(background))
+            src = da.read(rgb, device, "rgb")
+            (w, h, _, _), ordinal = da.source(src, layout, _background(background)), src.ordinal
         else:
             (h, w), ordinal = np.shape(rgb)[:2], 0 if device is None else device
         return _with_decoded(job, decoded, w, h, ordinal)
@@ -662,13 +510,11 @@ def _prepared(rgb, layout, device, stream, background=None, decoded=None):
             if px.dtype == np.uint8 and px.ndim == 3 and px.shape[2] in (2, 4):
                 rgb = blend_on_background(px, background)
         return _Job(lambda **kw: load_host().process(rgb, device=0 if device is None else device, **kw))
-    ptr, w, h, dtype, strides, producer, ordinal, alpha = _device_source(rgb, layout, device, background)
-    if stream is not None:
-        producer = int(stream)
-    if any(s < 0 for s in strides) or (alpha or 0) < 0:
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
+    src = da.read(rgb, device, "rgb")
+    w, h, strides, alpha = da.source(src, layout, background)
+    producer = da.stream_or(stream, src.stream)
     blend = {} if alpha is None else {"alpha_offset": alpha, "background": background}
-    return _Job(lambda **kw: load_host().process_device(ptr, w, h, dtype, strides, stream=producer, device=ordinal, **blend, **kw),
+    return _Job(lambda **kw: load_host().process_device(src.ptr, w, h, src.dtype, strides, stream=producer, device=src.ordinal, **blend, **kw),
                 producer, rgb)
 
 
@@ -732,7 +578,7 @@ def process_jpeg(data, quality=95.0, entropy="host", **kw):
 
 
 # ---- the butteraugli distance of two images (capi: gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device) ----
-MAP_DTYPES = ("float32", "float16", "bfloat16")
+MAP_DTYPES = LINEAR_DTYPES = da.FLOAT_DTYPES
 
 
 def _pair_library():
@@ -741,59 +587,19 @@ def _pair_library():
     return load()
 
 
-def _map_destination(x, w, h, device):
-    """(ptr, dtype name, element strides (y, x), consumer stream, device ordinal) of the device-resident 2-D image `x`
-    that is to receive a w x h distance map: _device_destination for one plane of floats."""
-    if getattr(x, "is_cuda", False):   # a torch tensor
-        import torch
-        name = str(x.dtype).replace("torch.", "")
-        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        if device is not None and device != ordinal:
-            raise ValueError(f"distmap= lives on device {ordinal}, the images on device {device}")
-        shape, strides = tuple(x.shape), tuple(x.stride())
-        ptr, stream = x.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream
-    elif hasattr(x, "__cuda_array_interface__"):
-        cai = x.__cuda_array_interface__
-        dt = np.dtype(cai["typestr"])
-        if cai["data"][1]:
-            raise ValueError("distmap= is read-only (its __cuda_array_interface__ says so)")
-        name, shape = dt.name, tuple(cai["shape"])
-        if cai.get("strides") is None:
-            byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
-        else:
-            byte_strides = tuple(cai["strides"])
-        if any(b % dt.itemsize for b in byte_strides):
-            raise ValueError("strides that are no multiple of the element size")
-        strides = tuple(b // dt.itemsize for b in byte_strides)
-        stream = cai.get("stream") or 0   # (as _device_source reads it)
-        if stream == 1:
-            stream = 0
-        ptr, ordinal = cai["data"][0], 0 if device is None else device
-    else:
-        raise TypeError("distmap=: True, or a device-resident 2-D image to fill")
-    if name not in MAP_DTYPES:
-        raise TypeError(f"distmap= has dtype {name}: float32, float16 or bfloat16")
-    if shape != (h, w):
-        raise ValueError(f"distmap= has shape {shape}, the images' map is {(h, w)}")
-    if min(strides) < 0:
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
-    if _strides_alias(strides, (h, w)):
-        raise ValueError(f"distmap= has strides {strides} under which two of its elements share an address (an expanded view?)")
-    return ptr, name, strides, stream, ordinal
+def _map_output(x, shape, device, stream, what="distmap="):
+    """The device-resident `x` that is to receive float planes of `shape` -- [h][w], or [n][h][w] -> capi.GzDeviceMap /
+    GzDeviceMapBatch with the consumer's stream (stream=, or the one `x` was made on)."""
+    dst = da.destination(x, shape, MAP_DTYPES, device, what)
+    describe = device_map if len(shape) == 2 else device_map_batch
+    return describe(dst.ptr, DTYPE_CODES[dst.dtype], dst.strides, da.stream_or(stream, dst.stream))
 
 
-def _new_heat_tensor(w, h, ordinal):
-    """A fresh uint8 [h][w][3] torch tensor on GPU `ordinal`, from the calling thread's current stream."""
-    return _new_device_tensor(w, h, "uint8", "HWC", ordinal)
-
-
-def _heat_destination(x, w, h, device):
-    """_device_destination of a heat map's destination: [h][w][3], or [3][h][w] where the shape says so."""
-    if not is_device_resident(x):
-        raise TypeError("heatmap=: True, or a device-resident image to fill")
-    shape = tuple(x.shape) if hasattr(x, "shape") else tuple(x.__cuda_array_interface__["shape"])
-    layout = "CHW" if len(shape) == 3 and shape[0] == 3 and shape[2] != 3 else "HWC"
-    return _device_destination(x, w, h, layout, device)
+def _image_output(x, w, h, layout, device, stream, what, dtypes=da.DTYPES):
+    """The device-resident `x` that is to receive w x h x 3 samples in `layout` (None: [h][w][3], or [3][h][w] where its
+    shape says so) -> capi.GzDeviceOutput with the consumer's stream."""
+    dst = da.image_destination(x, w, h, layout, dtypes, device, what)
+    return device_output(dst.ptr, DTYPE_CODES[dst.dtype], dst.strides, da.stream_or(stream, dst.stream))
 
 
 def _heat_thresholds(good, bad):
@@ -809,32 +615,15 @@ def _heat_thresholds(good, bad):
 
 def _heat_source(x):
     """(ptr, w, h, pitch in floats, device ordinal, what keeps the memory alive) of a float32 2-D distance map on a GPU."""
-    if getattr(x, "is_cuda", False):   # a torch tensor
-        import torch
-        if x.dtype != torch.float32 or x.dim() != 2:
-            raise TypeError(f"a distance map is a 2-D float32 image, not {tuple(x.shape)} of {x.dtype}")
-        h, w = x.shape
-        if (w > 1 and x.stride(1) != 1) or (h > 1 and x.stride(0) < w):
-            x = x.contiguous()
-        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        return x.data_ptr(), w, h, max(x.stride(0), w), ordinal, x
-    if not hasattr(x, "__cuda_array_interface__"):
-        raise TypeError("a distance map is a device-resident 2-D float32 image")
-    cai = x.__cuda_array_interface__
-    dt, shape = np.dtype(cai["typestr"]), tuple(cai["shape"])
-    if dt != np.float32 or len(shape) != 2:
-        raise TypeError(f"a distance map is a 2-D float32 image, not {shape} of {dt}")
-    h, w = shape
-    sy, sx = (4 * w, 4) if cai.get("strides") is None else tuple(cai["strides"])
-    if (w > 1 and sx != 4) or (h > 1 and (sy % 4 or sy < 4 * w)):
-        raise ValueError(f"a distance map with byte strides {(sy, sx)}: make it contiguous in x first")
-    return cai["data"][0], w, h, max(sy // 4, w), 0, x
-
-
-def _new_map_tensor(w, h, ordinal):
-    """A fresh float32 [h][w] torch tensor on GPU `ordinal`, from the calling thread's current stream."""
-    import torch
-    return torch.empty((h, w), dtype=torch.float32, device=f"cuda:{ordinal}")
+    src = da.read(x, None, "the distance map", dtypes=None)
+    if src.dtype != "float32" or len(src.shape) != 2:
+        raise TypeError(f"a distance map is a 2-D float32 image, not {src.shape} of {src.dtype}")
+    (h, w), (sy, sx) = src.shape, src.strides
+    if (w > 1 and sx != 1) or (h > 1 and sy < w):
+        if not hasattr(x, "contiguous"):   # (a torch tensor is copied; what an interface object offers for that is not known)
+            raise ValueError(f"a distance map with byte strides {(4 * sy, 4 * sx)}: make it contiguous in x first")
+        return _heat_source(x.contiguous())
+    return src.ptr, w, h, max(sy, w), src.ordinal, src.owner
 
 
 class _PairImage:
@@ -846,8 +635,8 @@ class _PairImage:
         self.linear, self.scale = linear, scale   # linear: pixels are raw linear intensity 0..255 after `scale`, not sRGB samples
 
 
-def _pair_image(x, layout, device, stream, background):
-    """`x` as process() accepts it -> _PairImage.  No device call."""
+def _pair_image(x, layout, device, stream, background, what="image"):
+    """`x` (the caller's parameter `what`) as process() accepts it -> _PairImage.  No device call."""
     background = _background(background)
     if not is_device_resident(x):
         if layout not in (None, "HWC"):
@@ -861,26 +650,12 @@ def _pair_image(x, layout, device, stream, background):
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError(f"host pixels are [h][w][3], not {rgb.shape}")
         return _PairImage(rgb.shape[1], rgb.shape[0], rgb=rgb)
-    ptr, w, h, dtype, strides, producer, ordinal, alpha = _device_source(x, layout, device, background)
-    if stream is not None:
-        producer = int(stream)
-    if any(s < 0 for s in strides) or (alpha or 0) < 0:
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
-    code = DTYPE_CODES[dtype]
-    alpha_ptr = 0 if alpha is None else int(ptr) + int(alpha) * ITEMSIZE[code]
-    if alpha is not None and not alpha_ptr:
-        raise ValueError("an alpha sample at address 0")
-    return _PairImage(w, h, pixels=device_pixels(ptr, code, strides, producer, alpha_ptr, background or (0, 0, 0)),
-                      ordinal=ordinal, keep=x)
-
-
-LINEAR_DTYPES = ("float32", "float16", "bfloat16")
-
-
-def _upload_linear(array, ordinal):
-    """Host floats -> a torch tensor on GPU `ordinal`, on the calling thread's current stream."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array)).to(f"cuda:{ordinal}")
+    src = da.read(x, device, what)
+    w, h, strides, alpha = da.source(src, layout, background)
+    code = DTYPE_CODES[src.dtype]
+    pixels = device_pixels(src.ptr, code, strides, da.stream_or(stream, src.stream), da.alpha_address(src.ptr, alpha, ITEMSIZE[code]),
+                           background or (0, 0, 0))
+    return _PairImage(w, h, pixels=pixels, ordinal=src.ordinal, keep=x)
 
 
 def _linear_scale(scale):
@@ -890,9 +665,9 @@ def _linear_scale(scale):
     return s
 
 
-def _linear_image(x, layout, device, stream, scale):
-    """`x` as a LINEAR float image -> _PairImage: a GPU tensor / __cuda_array_interface__ object of float32, float16 or
-    bfloat16 in any layout and strides process() takes, three channels or one; host float32 / float16 arrays are
+def _linear_image(x, layout, device, stream, scale, what="image"):
+    """`x` (the caller's parameter `what`) as a LINEAR float image -> _PairImage: a GPU tensor / __cuda_array_interface__
+    object of float32, float16 or bfloat16 in any layout and strides process() takes, three channels or one; host float32 / float16 arrays are
     uploaded first.  ValueError for everything else.  No device call but that upload."""
     scale = _linear_scale(scale)
     if not is_device_resident(x):
@@ -901,23 +676,14 @@ def _linear_image(x, layout, device, stream, scale):
             raise ValueError(f"dtype {a.dtype}: a linear image is float32, float16 or bfloat16 (no integers; convert float64 yourself: it is a rounding)")
         if a.ndim not in (2, 3):
             raise ValueError(f"an image has 2 or 3 dimensions, not {a.ndim}")
-        x = _upload_linear(a, 0 if device is None else device)
+        x = da.upload(a, 0 if device is None else device)
+    src = da.read(x, device, what, dtypes=LINEAR_DTYPES, error=ValueError)
     try:
-        ptr, w, h, dtype, strides, producer, ordinal, _ = _device_source(x, layout, device, None)
-    except TypeError as e:
-        raise ValueError(str(e)) from None
-    except ValueError as e:
-        if "alpha" in str(e):
-            raise ValueError("a linear image has three channels, or one (grey): alpha is not supported") from None
-        raise
-    if dtype not in LINEAR_DTYPES:
-        raise ValueError(f"dtype {dtype}: a linear image is float32, float16 or bfloat16")
-    if stream is not None:
-        producer = int(stream)
-    if any(s < 0 for s in strides):
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
-    return _PairImage(w, h, pixels=device_pixels(ptr, DTYPE_CODES[dtype], strides, producer), ordinal=ordinal, keep=x,
-                      linear=True, scale=scale)
+        w, h, strides, _ = da.source(src, layout)
+    except da.AlphaRefused:
+        raise ValueError("a linear image has three channels, or one (grey): alpha is not supported") from None
+    return _PairImage(w, h, pixels=device_pixels(src.ptr, DTYPE_CODES[src.dtype], strides, da.stream_or(stream, src.stream)),
+                      ordinal=src.ordinal, keep=x, linear=True, scale=scale)
 
 
 def _pair_sizes(ref, other):
@@ -949,9 +715,9 @@ class Comparator:
         if self.linear:
             if background is not None:
                 raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
-            ref = _linear_image(reference, layout, device, stream, self.scale)
+            ref = _linear_image(reference, layout, device, stream, self.scale, "reference")
         else:
-            ref = _pair_image(reference, layout, device, stream, background)
+            ref = _pair_image(reference, layout, device, stream, background, "reference")
         _pair_sizes(ref, None)
         self._open(ref, ref.ordinal if ref.ordinal is not None else (0 if device is None else device))
 
@@ -988,13 +754,11 @@ class Comparator:
 
     def _destination(self, distmap, stream):
         """distmap= -> (what compare returns as the map, capi.GzDeviceMap) -- (None, None) without one."""
-        from .capi import device_map
         if distmap is None or distmap is False:
             return None, None
         if distmap is True:
-            distmap = _new_map_tensor(self.w, self.h, self.device)
-        ptr, name, strides, consumer, _ = _map_destination(distmap, self.w, self.h, self.device)
-        return distmap, device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+            distmap = da.new_tensor((self.h, self.w), "float32", self.device)
+        return distmap, _map_output(distmap, (self.h, self.w), self.device, stream)
 
     def _heat_destination(self, heatmap, good, bad, stream):
         """heatmap= -> (what compare returns as the heat map, capi.GzDeviceOutput, good, bad) -- None without one."""
@@ -1002,9 +766,8 @@ class Comparator:
             return None
         good, bad = _heat_thresholds(good, bad)
         if heatmap is True:
-            heatmap = _new_heat_tensor(self.w, self.h, self.device)
-        ptr, name, strides, consumer, _ = _heat_destination(heatmap, self.w, self.h, self.device)
-        return heatmap, device_output(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)), good, bad
+            heatmap = da.new_tensor((self.h, self.w, 3), "uint8", self.device)
+        return heatmap, _image_output(heatmap, self.w, self.h, None, self.device, stream, "heatmap="), good, bad
 
     def _compare(self, other, out, dmap, heat=None):
         if self._ctx is None:
@@ -1046,10 +809,10 @@ class Comparator:
         if self.linear if linear is None else linear:
             if background is not None:
                 raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
-            other = _linear_image(distorted, layout, self.device, stream, self.scale if scale is None else scale)
+            other = _linear_image(distorted, layout, self.device, stream, self.scale if scale is None else scale, "distorted")
             consumer = stream
         else:
-            other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background)
+            other = _pair_image(distorted, layout, self.device if is_device_resident(distorted) else None, stream, background, "distorted")
             consumer = stream if is_device_resident(distorted) else None
         _pair_sizes(_PairImage(self.w, self.h), other)
         heat = self._heat_destination(heatmap, good, bad, consumer)
@@ -1069,18 +832,18 @@ def butteraugli(reference, distorted, distmap=None, layout=None, device=None, st
     ValueError, before anything is computed: sizes that differ, sizes under 8 x 8, images on different devices.
     heatmap=, good=, bad=: the map's heat map, appended to the return value (see Comparator.compare).
     For many images against one reference, Comparator keeps the reference's half of the work."""
-    ref = _pair_image(reference, layout, device, stream if is_device_resident(reference) else None, background)
+    ref = _pair_image(reference, layout, device, stream if is_device_resident(reference) else None, background, "reference")
     known = ref.ordinal if ref.ordinal is not None else device
     other = _pair_image(distorted, layout, known if is_device_resident(distorted) else None,
-                        stream if is_device_resident(distorted) else None, background)
+                        stream if is_device_resident(distorted) else None, background, "distorted")
     _pair_sizes(ref, other)
     ordinal = known if known is not None else (other.ordinal if other.ordinal is not None else 0)
     if distmap is not None and distmap is not False and distmap is not True:
-        _map_destination(distmap, ref.w, ref.h, ordinal)   # (refused before the reference is worked on)
+        da.destination(distmap, (ref.h, ref.w), MAP_DTYPES, ordinal, "distmap=")   # (refused before the reference is worked on)
     if heatmap is not None and heatmap is not False:
         _heat_thresholds(good, bad)
         if heatmap is not True:
-            _heat_destination(heatmap, ref.w, ref.h, ordinal)
+            da.image_destination(heatmap, ref.w, ref.h, None, da.DTYPES, ordinal, "heatmap=")
     with Comparator._of(ref, ordinal) as cmp:
         consumer = stream if (ref.pixels is not None or other.pixels is not None) else None
         heat = cmp._heat_destination(heatmap, good, bad, consumer)
@@ -1092,64 +855,29 @@ BATCH_MAX_PIXELS = 1500000   # gz_butteraugli_batch: w * h below this
 BATCH_DTYPES = ("uint8", "float32", "float16", "bfloat16")
 
 
-def _device_array(x, device, what):
-    """(ptr, shape, element strides, dtype name, the stream it was made on, device ordinal, read-only) of a GPU tensor or
-    __cuda_array_interface__ object."""
-    if getattr(x, "is_cuda", False):   # a torch tensor
-        import torch
-        ordinal = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        if device is not None and device != ordinal:
-            raise ValueError(f"{what} lives on device {ordinal}, device {device} was asked for")
-        return (x.data_ptr(), tuple(x.shape), tuple(x.stride()), str(x.dtype).replace("torch.", ""),
-                torch.cuda.current_stream(x.device).cuda_stream, ordinal, False)
-    cai = x.__cuda_array_interface__
-    dt, shape = np.dtype(cai["typestr"]), tuple(cai["shape"])
-    if cai.get("strides") is None:
-        byte_strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
-    else:
-        byte_strides = tuple(cai["strides"])
-    if any(b % dt.itemsize for b in byte_strides):
-        raise ValueError("strides that are no multiple of the element size")
-    stream = cai.get("stream") or 0   # (as _device_source reads it)
-    return (cai["data"][0], shape, tuple(b // dt.itemsize for b in byte_strides), dt.name, 0 if stream == 1 else stream,
-            0 if device is None else device, bool(cai["data"][1]))
-
-
 def _batch_images(x, layout, device, stream, what, one_image_too=False):
     """A batch [N,3,H,W] / [N,H,W,3] (with one_image_too also one image, 2-D or 3-D: n = 1) -> (capi.GzDeviceBatch, n, w, h, ordinal, keep).
     Host arrays are uploaded first, on the calling thread's current stream."""
     if not is_device_resident(x):
-        x = _upload_linear(np.asarray(x), 0 if device is None else device)
-    ptr, shape, strides, dtype, producer, ordinal, _ = _device_array(x, device, what)
-    if dtype not in BATCH_DTYPES:
-        raise ValueError(f"{what} has dtype {dtype}: a batch takes uint8, float32, float16 or bfloat16 (16-bit integer samples: "
+        x = da.upload(np.asarray(x), 0 if device is None else device)
+    src = da.read(x, device, what, dtypes=None)
+    if src.dtype not in BATCH_DTYPES:
+        raise ValueError(f"{what} has dtype {src.dtype}: a batch takes uint8, float32, float16 or bfloat16 (16-bit integer samples: "
                          "compare the images one by one with butteraugli())")
-    if len(shape) == 4:
-        n, sn, shape, strides = shape[0], strides[0], shape[1:], strides[1:]
+    if len(src.shape) == 4:
+        n, sn, image = src.shape[0], src.strides[0], src._replace(shape=src.shape[1:], strides=src.strides[1:])
         if n < 1:
             raise ValueError(f"{what} is an empty batch")
-    elif len(shape) in (2, 3) and one_image_too:
-        n, sn = 1, 0
+    elif len(src.shape) in (2, 3) and one_image_too:
+        n, sn, image = 1, 0, src
     else:
-        raise ValueError(f"{what} has {len(shape)} dimensions: a batch is [N,3,H,W] or [N,H,W,3]")
+        raise ValueError(f"{what} has {len(src.shape)} dimensions: a batch is [N,3,H,W] or [N,H,W,3]")
     try:
-        w, h, (sy, sx, sc), _ = _layout_strides(shape, strides, layout)
-    except ValueError as e:
-        if "alpha" not in str(e):
-            raise
-        raise ValueError(f"{what} of shape {tuple(shape)}: a batch takes 3 channels, or 1 (grey) -- no alpha; blend the images "
+        w, h, strides, _ = da.source(image, layout, outer=(sn,))
+    except da.AlphaRefused:
+        raise ValueError(f"{what} of shape {image.shape}: a batch takes 3 channels, or 1 (grey) -- no alpha; blend the images "
                          "first, or compare them one by one with butteraugli(background=)") from None
-    if min(sn, sy, sx, sc) < 0:
-        raise ValueError("negative strides (a flipped view): make it contiguous first")
-    if stream is not None:
-        producer = int(stream)
-    return device_batch(ptr, DTYPE_CODES[dtype], (sn, sy, sx, sc), producer), n, w, h, ordinal, x
-
-
-def _new_batch_tensor(shape, ordinal):
-    """A fresh float32 torch tensor of `shape` on GPU `ordinal`, from the calling thread's current stream."""
-    import torch
-    return torch.empty(shape, dtype=torch.float32, device=f"cuda:{ordinal}")
+    return device_batch(src.ptr, DTYPE_CODES[src.dtype], (sn,) + strides, da.stream_or(stream, src.stream)), n, w, h, src.ordinal, x
 
 
 def butteraugli_batch(reference, distorted, distmap=None, layout=None, device=None, stream=None, scratch_bytes=0):
@@ -1181,23 +909,10 @@ def butteraugli_batch(reference, distorted, distmap=None, layout=None, device=No
                          "use Comparator (one reference, many images) or butteraugli()")
     maps = out = None
     if distmap is not None and distmap is not False:
-        out = _new_batch_tensor((n, h, w), ordinal) if distmap is True else distmap
-        if not is_device_resident(out):
-            raise TypeError("distmap=: True, or a device-resident [N,H,W] tensor to fill")
-        ptr, shape, strides, dtype, consumer, _, readonly = _device_array(out, ordinal, "distmap=")
-        if readonly:
-            raise ValueError("distmap= is read-only (its __cuda_array_interface__ says so)")
-        if dtype not in MAP_DTYPES:
-            raise TypeError(f"distmap= has dtype {dtype}: float32, float16 or bfloat16")
-        if shape != (n, h, w):
-            raise ValueError(f"distmap= has shape {shape}, the batch's maps are {(n, h, w)}")
-        if min(strides) < 0:
-            raise ValueError("negative strides (a flipped view): make it contiguous first")
-        if _strides_alias(strides, (n, h, w)):
-            raise ValueError(f"distmap= has strides {strides} under which two of its elements share an address (an expanded view?)")
-        maps = device_map_batch(ptr, DTYPE_CODES[dtype], strides, consumer if stream is None else int(stream))
-    dist = _new_batch_tensor((n,), ordinal)
-    dptr = _device_array(dist, ordinal, "distances")[0]
+        out = da.new_tensor((n, h, w), "float32", ordinal) if distmap is True else distmap
+        maps = _map_output(out, (n, h, w), ordinal, stream)
+    dist = da.new_tensor((n,), "float32", ordinal)
+    dptr = da.read(dist, ordinal, "the distances").ptr
     _pair_library().butteraugli_batch(ref, other, w, h, n, dptr, n_ref=n_ref, maps=maps, scratch_bytes=int(scratch_bytes), device=ordinal)
     del keep0, keep1
     return dist if out is None else (dist, out)
@@ -1220,21 +935,19 @@ def butteraugli_linear(reference, distorted, scale=1.0, distmap=None, heatmap=No
     ValueError, before anything is computed: sizes that differ, integer dtypes, four channels, images on different
     devices."""
     scale = _linear_scale(scale)
-    ref = _linear_image(reference, layout, device, stream, scale)
-    other = _linear_image(distorted, layout, ref.ordinal, stream, scale)
+    ref = _linear_image(reference, layout, device, stream, scale, "reference")
+    other = _linear_image(distorted, layout, ref.ordinal, stream, scale, "distorted")
     if (other.w, other.h) != (ref.w, ref.h):
         raise ValueError(f"the images differ in size: {ref.w} x {ref.h} against {other.w} x {other.h}")
     w, h, ordinal = ref.w, ref.h, ref.ordinal
     out = dmap = heat = None
     if distmap is not None and distmap is not False:
-        out = _new_map_tensor(w, h, ordinal) if distmap is True else distmap
-        ptr, name, strides, consumer, _ = _map_destination(out, w, h, ordinal)
-        dmap = device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+        out = da.new_tensor((h, w), "float32", ordinal) if distmap is True else distmap
+        dmap = _map_output(out, (h, w), ordinal, stream)
     if heatmap is not None and heatmap is not False:
         good, bad = _heat_thresholds(good, bad)
-        hout = _new_heat_tensor(w, h, ordinal) if heatmap is True else heatmap
-        ptr, name, strides, consumer, _ = _heat_destination(hout, w, h, ordinal)
-        heat = (hout, device_output(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)))
+        hout = da.new_tensor((h, w, 3), "uint8", ordinal) if heatmap is True else heatmap
+        heat = (hout, _image_output(hout, w, h, None, ordinal, stream, "heatmap="))
     d, clamped = _pair_library().butteraugli_linear(ref.pixels, other.pixels, w, h, scale, dmap, None if heat is None else heat[1],
                                                     good if heat else 0.0, bad if heat else 0.0, device=ordinal)
     if strict and clamped:
@@ -1265,26 +978,24 @@ def heatmap(distmap, good=None, bad=None, out=None, dtype="uint8", layout="HWC",
     good, bad = _heat_thresholds(good, bad)
     ptr, w, h, pitch, ordinal, keep = _heat_source(distmap)
     if out is None:
-        out = _new_device_tensor(w, h, dtype, layout, ordinal)
-    optr, name, strides, consumer, _ = _heat_destination(out, w, h, ordinal)
-    _pair_library().heatmap_from_map_device(ptr, w, h, pitch, good, bad,
-                                            device_output(optr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream)), device=ordinal)
+        out = da.new_tensor(da.image_shape(w, h, layout), dtype, ordinal)
+    _pair_library().heatmap_from_map_device(ptr, w, h, pitch, good, bad, _image_output(out, w, h, None, ordinal, stream, "out="), device=ordinal)
     del keep
     return out
 
 
 # ---- butteraugli's masking on the GPU: the opsin image, Mask, the quantisation field ----
-def _masking_image(x, linear, image_layout, device, stream, background, scale):
+def _masking_image(x, linear, image_layout, device, stream, background, scale, what="image"):
     """`x` as butteraugli() (linear=False) or butteraugli_linear() (linear=True) takes an image -> _PairImage with
     device-resident pixels: host arrays are uploaded first."""
     if linear:
         if background is not None:
             raise ValueError("background= goes with 8-bit pixels: a linear image has no alpha")
-        return _linear_image(x, image_layout, device, stream, scale)
+        return _linear_image(x, image_layout, device, stream, scale, what)
     if not is_device_resident(x):
         host = _pair_image(x, image_layout, None, None, background)      # (its checks, and the blend of host alpha)
-        x, image_layout, background = _upload_linear(host.rgb, 0 if device is None else device), "HWC", None
-    return _pair_image(x, image_layout, device, stream, background)
+        x, image_layout, background = da.upload(host.rgb, 0 if device is None else device), "HWC", None
+    return _pair_image(x, image_layout, device, stream, background, what)
 
 
 def _masking_size(img, least, what):
@@ -1294,22 +1005,12 @@ def _masking_size(img, least, what):
 
 def _float_destination(out, w, h, dtype, layout, ordinal, stream, name="out="):
     """out= (None: a fresh tensor of `dtype` in `layout`) -> (the tensor, capi.GzDeviceOutput) for w x h x 3 floats."""
-    if dtype not in MAP_DTYPES and out is None:
-        raise TypeError(f"dtype {dtype}: float32, float16 or bfloat16")
+    shape = da.image_shape(w, h, layout)
     if out is None:
-        out = _new_device_tensor(w, h, dtype, layout, ordinal)
-    elif not is_device_resident(out):
-        raise TypeError(f"{name} a device-resident image to fill")
-    ptr, found, strides, consumer, _ = _device_destination(out, w, h, layout, ordinal)
-    if found not in MAP_DTYPES:
-        raise TypeError(f"{name} has dtype {found}: float32, float16 or bfloat16")
-    return out, device_output(ptr, DTYPE_CODES[found], strides, consumer if stream is None else int(stream))
-
-
-def _new_plane_tensor(w, h, dtype, ordinal):
-    """A fresh [h][w] torch tensor of a float `dtype` on GPU `ordinal`, from the calling thread's current stream."""
-    import torch
-    return torch.empty((h, w), dtype=getattr(torch, dtype), device=f"cuda:{ordinal}")
+        if dtype not in MAP_DTYPES:
+            raise TypeError(f"dtype {dtype}: float32, float16 or bfloat16")
+        out = da.new_tensor(shape, dtype, ordinal)
+    return out, _image_output(out, w, h, layout, ordinal, stream, name, MAP_DTYPES)
 
 
 def _strict_clamp(strict, clamped, scale, what):
@@ -1347,8 +1048,8 @@ def mask(reference, distorted=None, dc=False, linear=False, scale=1.0, out=None,
     out= / out_dc=, dtype=, layout=, stream= and the 8 x 8 lower bound as for opsin_dynamics(); both images have one size
     and live on one GPU."""
     scale = _linear_scale(scale)
-    ref = _masking_image(reference, linear, image_layout, device, stream, background, scale)
-    other = None if distorted is None else _masking_image(distorted, linear, image_layout, ref.ordinal, stream, background, scale)
+    ref = _masking_image(reference, linear, image_layout, device, stream, background, scale, "reference")
+    other = None if distorted is None else _masking_image(distorted, linear, image_layout, ref.ordinal, stream, background, scale, "distorted")
     _masking_size(ref, 8, "Mask")
     if other is not None and (other.w, other.h) != (ref.w, ref.h):
         raise ValueError(f"the images differ in size: {ref.w} x {ref.h} against {other.w} x {other.h}")
@@ -1369,17 +1070,13 @@ def adaptive_quantization(image, scale=1.0, out=None, dtype="float32", layout=No
     CLAMPED (strict=True raises if any was).  ValueError, before anything is computed: an image under 16 x 16, where the
     reference gives up."""
     scale = _linear_scale(scale)
-    img = _linear_image(image, layout, device, stream, scale)
+    img = _linear_image(image, layout, device, stream, scale, "image")
     _masking_size(img, 16, "the quantisation field")
     if out is None:
         if dtype not in MAP_DTYPES:
             raise TypeError(f"dtype {dtype}: float32, float16 or bfloat16")
-        out = _new_plane_tensor(img.w, img.h, dtype, img.ordinal)
-    try:
-        ptr, name, strides, consumer, _ = _map_destination(out, img.w, img.h, img.ordinal)
-    except (TypeError, ValueError) as e:
-        raise type(e)(str(e).replace("distmap=", "out=")) from None
-    quant = device_map(ptr, DTYPE_CODES[name], strides, consumer if stream is None else int(stream))
+        out = da.new_tensor((img.h, img.w), dtype, img.ordinal)
+    quant = _map_output(out, (img.h, img.w), img.ordinal, stream, "out=")
     clamped = _pair_library().adaptive_quantization(img.pixels, img.w, img.h, quant, scale, device=img.ordinal)
     _strict_clamp(strict, clamped, scale, "the image")
     return out

@@ -300,15 +300,12 @@ def test_every_allocation_failing_in_turn(L):
 
 
 # ------------------------------------------------------------------ the Python surface ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__) over numpy memory: in the emulation that is
-    device memory."""
+import fake_device  # noqa: E402
 
-    def __init__(self, array, readonly=False):
-        self.array = array
-        self.shape = array.shape
-        self.__cuda_array_interface__ = {"shape": array.shape, "typestr": array.dtype.str, "data": (array.ctypes.data, readonly),
-                                         "version": 3, "strides": array.strides, "stream": None}
+
+def FakeDeviceArray(array, readonly=False):
+    """fake_device's, under the array's own strides: these tests hand over slices and crops."""
+    return fake_device.FakeDeviceArray(array, readonly, strides=array.strides)
 
 
 @pytest.fixture()
@@ -316,7 +313,7 @@ def emulated(monkeypatch, L):
     """guetzli_amd.butteraugli_batch on the emulated library, with numpy memory for the tensors it allocates."""
     from guetzli_amd import encoder
     monkeypatch.setattr(encoder, "_pair_library", lambda: L)
-    monkeypatch.setattr(encoder, "_new_batch_tensor", lambda shape, ordinal: FakeDeviceArray(np.full(shape, 7, np.float32)))
+    fake_device.install(monkeypatch)
 
 
 def test_butteraugli_batch(emulated):

@@ -358,14 +358,8 @@ def test_every_allocation_failing_in_turn(L):
 
 
 # ------------------------------------------------------------------ the Python surface ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__) over numpy memory: in the emulation that is
-    device memory."""
-
-    def __init__(self, array, readonly=False, strides=None):
-        self.array = array
-        self.__cuda_array_interface__ = {"shape": array.shape, "typestr": array.dtype.str, "data": (array.ctypes.data, readonly),
-                                         "version": 3, "strides": strides, "stream": None}
+import fake_device  # noqa: E402
+from fake_device import FakeDeviceArray  # noqa: E402
 
 
 @pytest.fixture()
@@ -373,7 +367,7 @@ def emulated(monkeypatch, L):
     """guetzli_amd.butteraugli / Comparator on the emulated library, with numpy memory for the maps they allocate."""
     from guetzli_amd import encoder
     monkeypatch.setattr(encoder, "_pair_library", lambda: L)
-    monkeypatch.setattr(encoder, "_new_map_tensor", lambda w, h, ordinal: FakeDeviceArray(np.full((h, w), 7, np.float32)))
+    fake_device.install(monkeypatch)
 
 
 def test_butteraugli_and_comparator(emulated):

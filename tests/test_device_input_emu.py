@@ -258,12 +258,7 @@ def test_argument_errors_come_before_any_device_call(product):
 
 
 # ------------------------------------------------------------------ the Python dispatch ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__): never dereferenced by these tests."""
-
-    def __init__(self, shape, typestr, stream=None):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (0x7F0000000000, False), "version": 3,
-                                         "strides": None, "stream": stream}
+from fake_device import FakeDeviceAddress as FakeDeviceArray  # noqa: E402
 
 
 class StubHost:

@@ -377,29 +377,16 @@ def test_argument_errors_come_before_any_device_call(product):
 
 
 # ------------------------------------------------------------------ the Python surface ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__) over numpy memory: in the emulation that is
-    device memory."""
-
-    def __init__(self, array, readonly=False, strides=None, shape=None, stream=None):
-        self.array = array
-        self.__cuda_array_interface__ = {"shape": shape or array.shape, "typestr": array.dtype.str, "data": (array.ctypes.data, readonly),
-                                         "version": 3, "strides": strides, "stream": stream}
+import fake_device  # noqa: E402
+from fake_device import FakeDeviceArray  # noqa: E402
 
 
 @pytest.fixture()
 def emulated(monkeypatch, host):
     """guetzli_amd's module-level functions on the emulated libraries, with numpy memory for the tensors they allocate."""
     from guetzli_amd import encoder
-    made = []
-
-    def allocate(w, h, dtype, layout, ordinal):
-        a = np.full((h, w, 3) if layout == "HWC" else (3, h, w), 7, np.dtype(str(dtype)))   # (numpy's types: no bfloat16 here)
-        made.append(a)
-        return FakeDeviceArray(a)
     monkeypatch.setattr(encoder, "_default", host)
-    monkeypatch.setattr(encoder, "_new_device_tensor", allocate)
-    return made
+    fake_device.install(monkeypatch)
 
 
 @pytest.mark.parametrize("w,h", [(40, 40), (16, 16)])

@@ -229,15 +229,8 @@ def test_every_launch_and_allocation_failing_in_turn(L, which):
 
 
 # ------------------------------------------------------------------ the Python surface ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__) over numpy memory: in the emulation that is
-    device memory."""
-
-    def __init__(self, array, strides=None):
-        self.array = array
-        self.shape = array.shape
-        self.__cuda_array_interface__ = {"shape": array.shape, "typestr": array.dtype.str, "data": (array.ctypes.data, False),
-                                         "version": 3, "strides": strides, "stream": None}
+import fake_device  # noqa: E402
+from fake_device import FakeDeviceArray  # noqa: E402
 
 
 @pytest.fixture()
@@ -245,11 +238,8 @@ def emulated(monkeypatch, L):
     """guetzli_amd.opsin_dynamics / mask / adaptive_quantization on the emulated library, with numpy memory for what they
     allocate."""
     from guetzli_amd import encoder
-    shape = lambda w, h, layout: (h, w, 3) if layout == "HWC" else (3, h, w)
     monkeypatch.setattr(encoder, "_pair_library", lambda: L)
-    monkeypatch.setattr(encoder, "_new_device_tensor", lambda w, h, dtype, layout, ordinal: FakeDeviceArray(np.full(shape(w, h, layout), 7, dtype)))
-    monkeypatch.setattr(encoder, "_new_plane_tensor", lambda w, h, dtype, ordinal: FakeDeviceArray(np.full((h, w), 7, dtype)))
-    monkeypatch.setattr(encoder, "_upload_linear", lambda a, ordinal: FakeDeviceArray(np.ascontiguousarray(a)))
+    fake_device.install(monkeypatch)
 
 
 def test_the_python_functions(emulated):

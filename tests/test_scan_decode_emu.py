@@ -405,25 +405,16 @@ def test_the_four_passes_in_order_on_one_stream(L, judged):
 
 
 # ------------------------------------------------------------------ the Python surface ----
-class FakeDeviceArray:
-    """An object that says it lives on a GPU (__cuda_array_interface__) over numpy memory: in the emulation that is
-    device memory."""
-
-    def __init__(self, array, strides=None):
-        self.array = array
-        self.__cuda_array_interface__ = {"shape": array.shape, "typestr": array.dtype.str, "data": (array.ctypes.data, False),
-                                         "version": 3, "strides": strides, "stream": None}
+import fake_device  # noqa: E402
+from fake_device import FakeDeviceArray  # noqa: E402
 
 
 @pytest.fixture()
 def emulated(monkeypatch, host):
     """guetzli_amd's module-level functions on the emulated libraries, with numpy memory for the tensors they allocate."""
     from guetzli_amd import encoder
-
-    def allocate(w, h, dtype, layout, ordinal):
-        return FakeDeviceArray(np.full((h, w, 3) if layout == "HWC" else (3, h, w), 7, np.dtype(str(dtype))))
     monkeypatch.setattr(encoder, "_default", host)
-    monkeypatch.setattr(encoder, "_new_device_tensor", allocate)
+    fake_device.install(monkeypatch)
 
 
 def test_decode_and_decode_info(emulated, judged):
