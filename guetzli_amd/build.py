@@ -20,7 +20,7 @@ HEADERS = ["gz_common.h", "gz_math.h", "gz_kernels_block.h", "gz_kernels_blur.h"
            "gz_kernels_order.h", "gz_kernels_rank.h", "gz_kernels_ingest.h", "gz_kernels_ingestlin.h", "gz_kernels_emit.h", "gz_kernels_emitmap.h", "gz_kernels_emitheat.h", "gz_kernels_emitmask.h", "gz_kernels_scandec.h", "gz_host_weights.h", "tables_generated.h", "order_tables_generated.h",
            # gz_api.hip by concern (one translation unit)
            "api/plans.h", "api/context.h", "api/tensor.h", "api/chain.h", "api/entry_context.h", "api/entry_compare.h",
-           "api/entry_phaseb.h", "api/entry_entropy.h", "api/entry_frame.h", "api/entry_decode.h", "api/entry_scandec.h", "api/entry_heat.h", "api/entry_pair.h", "api/entry_linear.h", "api/entry_batch.h", "api/entry_mask.h", "api/entry_search.h", "api/entry_probes.h"]
+           "api/entry_phaseb.h", "api/entry_entropy.h", "api/entry_frame.h", "api/entry_decode.h", "api/entry_scandec.h", "api/entry_heat.h", "api/entry_pair.h", "api/entry_linear.h", "api/entry_batch.h", "api/entry_scandec_batch.h", "api/entry_mask.h", "api/entry_search.h", "api/entry_probes.h"]
 ARCH = "gfx950"
 # -vectorize-slp=false: left to itself the compiler packs adjacent scalar f32 adds / multiplies
 # into v_pk_*_f32 pairs; those issue at the same lane rate as the scalar forms on gfx950

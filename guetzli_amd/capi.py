@@ -142,6 +142,19 @@ def device_batch(ptr, dtype, strides, stream=0):
     return GzDeviceBatch(C.sizeof(GzDeviceBatch), int(dtype), int(ptr) or None, sn, sy, sx, sc, int(stream) or None)
 
 
+class GzDeviceOutputBatch(C.Structure):
+    """gz_device_output_batch of include/guetzli_amd.h: n strided images of one size in device memory that are written."""
+    _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_n", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64), ("stride_c", C.c_int64), ("consumer_stream", _P), ("n", _I)]
+
+
+def device_output_batch(ptr, dtype, strides, n, stream=0):
+    """A GzDeviceOutputBatch: ptr = device address of element (0, 0, 0, 0), dtype = GZ_DT_*, strides = (n, y, x, c) in
+    elements, n = its images, stream = the hipStream_t that used the memory before and reads it afterwards (0: none)."""
+    sn, sy, sx, sc = (int(v) for v in strides)
+    return GzDeviceOutputBatch(C.sizeof(GzDeviceOutputBatch), int(dtype), int(ptr) or None, sn, sy, sx, sc, int(stream) or None, int(n))
+
+
 class GzDeviceMapBatch(C.Structure):
     """gz_device_map_batch of include/guetzli_amd.h: where n distance maps go."""
     _fields_ = [("struct_size", _I), ("dtype", _I), ("data", _P), ("stride_n", C.c_int64), ("stride_y", C.c_int64),
@@ -181,6 +194,7 @@ SIGNATURES = {
     "gz_decode_scan": (_I, [_I, _P, _P, _P]),
     "gz_decode_scan_device": (_I, [_I, _P, _P, _P]),
     "gz_decode_scan_input": (_I, [_I, _P, _P, _P, _P]),
+    "gz_decode_scan_batch_device": (_I, [_I, _I, _P, _P, _P, _P, C.c_size_t]),
     "gz_compare_device_pixels": (_I, [_P, _P, _P, _P]),
     "gz_compare_rgb": (_I, [_P, _P, _P, _P]),
     "gz_distmap_device": (_I, [_P, _P]),
@@ -538,6 +552,23 @@ class Library:
         res = GzScanResult()
         self.check(self.lib.gz_decode_scan_device(device, C.byref(scan), C.byref(output), C.byref(res)))
         return self._scan_result(res)
+
+    def decode_scan_batch_device(self, scans, slots, output, scratch_bytes=0, device=0, results=None):
+        """gz_decode_scan_batch_device: the pixels of scans[i] (scan_spec(...)) into image slots[i] of `output`
+        (device_output_batch(...)) where its status is "DECODED" -> the gz_scan_results as dicts.  results: a list that
+        receives them whether the call succeeds or not."""
+        n = len(scans)
+        arr = (GzScan * max(n, 1))()
+        for i, sc in enumerate(scans):
+            C.memmove(C.byref(arr, i * C.sizeof(GzScan)), C.byref(sc), C.sizeof(GzScan))
+        res = (GzScanResult * max(n, 1))()
+        sl = (_I * max(n, 1))(*[int(v) for v in slots])
+        try:
+            self.check(self.lib.gz_decode_scan_batch_device(device, n, arr, sl, C.byref(output), res, int(scratch_bytes)))
+        finally:
+            if results is not None:
+                results[:] = [self._scan_result(res[i]) for i in range(n)]
+        return [self._scan_result(res[i]) for i in range(n)]
 
     def decode_scan_input(self, scan, device=0):
         """gz_decode_scan_input: the scan as the host READER leaves it -> (per component the quantised coefficients int16

@@ -1,5 +1,5 @@
-// A caller's strided device tensor as the entries see it: ONE internal view of the six ABI structs (gz_device_image,
-// gz_device_pixels, gz_device_output, gz_device_map, gz_device_batch, gz_device_map_batch), the arithmetic on it -- the
+// A caller's strided device tensor as the entries see it: ONE internal view of the seven ABI structs (gz_device_image,
+// gz_device_pixels, gz_device_output, gz_device_map, gz_device_batch, gz_device_map_batch, gz_device_output_batch), the arithmetic on it -- the
 // extent rule, the distinct-addresses rule, the last offset -- and one adapter per struct.
 // Host code without a device call and without a gz_ctx: tests/cpp/tensor_args.cc compiles this file alone.
 // (in gz_api.hip: included behind context.h)
@@ -123,6 +123,13 @@ inline TensorView tensor_view(const gz_device_batch* p, int w, int h, int n) {
   v.stream = p->producer_stream;
   return v;
 }
+inline TensorView tensor_view(const gz_device_output_batch* p, int w, int h) {
+  TensorView v;
+  v.data = p->data; v.dtype = p->dtype; v.nd = 4;
+  v.dim[0] = {p->stride_n, p->n}; v.dim[1] = {p->stride_y, h}; v.dim[2] = {p->stride_x, w}; v.dim[3] = {p->stride_c, 3};
+  v.stream = p->consumer_stream;
+  return v;
+}
 inline TensorView tensor_view(const gz_device_map_batch* p, int w, int h, int n) {
   TensorView v;
   v.data = p->data; v.dtype = p->dtype; v.nd = 3;
@@ -162,6 +169,11 @@ inline int check_device_batch(const gz_device_batch* b, int w, int h, int n) {
 inline int check_device_map_batch(const gz_device_map_batch* m, int w, int h, int n) {
   if (!m || m->struct_size != (int)sizeof(gz_device_map_batch)) return GZ_E_ARG;
   return tensor_check(tensor_view(m, w, h, n), GZ_DT_F32, GZ_DT_BF16, true);
+}
+// The images of an output batch are its n gz_device_outputs: every dtype of those, and no address twice among them all.
+inline int check_device_output_batch(const gz_device_output_batch* b, int w, int h) {
+  if (!b || b->struct_size != (int)sizeof(gz_device_output_batch) || !tensor_plane_size(w, h) || b->n < 1) return GZ_E_ARG;
+  return tensor_check(tensor_view(b, w, h), GZ_DT_U8, GZ_DT_U16, true);
 }
 // gz_device_image is gz_device_pixels without alpha: what the three older entries accept stays what it was (their
 // struct_size, no GZ_DT_U16), the rest is the code behind the newer ones.

@@ -65,6 +65,7 @@ using namespace gz;
 #include "api/entry_pair.h"     // gz_compare_device_pixels / gz_compare_rgb / gz_distmap_device (image pairs, the map on the device)
 #include "api/entry_linear.h"   // gz_create_from_device_linear / gz_set_linear_device / gz_compare_device_linear / gz_butteraugli_linear (linear float images)
 #include "api/entry_batch.h"    // gz_butteraugli_batch (n image pairs through one chain: the kernels' batched forms)
+#include "api/entry_scandec_batch.h"   // gz_decode_scan_batch_device (n scans through the launches of one device decode)
 #include "api/entry_mask.h"     // gz_opsin_device / gz_mask_device / gz_adaptive_quantization (the masking images on the device)
 #include "api/entry_search.h"   // gz_block_zeroing_orders*, gz_compare_blocks
 #include "api/entry_probes.h"   // gz_probe_* (diagnostics)

@@ -139,7 +139,8 @@ GZ_DEVFN void idct3_to_rgb(const int (*s_in)[64], int (*s_col)[64], int lane, in
 // (six 2-byte loads per lane, held in registers): twice the bytes in flight per wavefront.  Round 3's
 // one-strip workgroups waited for their loads 73 % of their cycles (SQ_WAIT_ANY) at 2.6 TB/s.
 // (strips_per_wg is the caller's: 4 where that still leaves several workgroups per CU.)
-__global__ __launch_bounds__(256) void k_reconstruct(
+// The body of k_reconstruct and of its batched form (both below it): blockIdx.x is the workgroup of ONE frame.
+GZ_DEVFN void reconstruct_body(
     const int16_t* __restrict__ coeffs, int w, int h, int bw, int nb, int pitch,
     size_t pstride, const float* __restrict__ srgb_lut, float* __restrict__ lin,
     uint8_t* __restrict__ srgb, unsigned* __restrict__ clear_word, int strips_per_wg) {
@@ -253,6 +254,21 @@ __global__ __launch_bounds__(256) void k_reconstruct(
     // (the next strip's first barrier stands between these reads of s_px / s_u8 and its writes
     // to them, which come two barriers later)
   }
+}
+__global__ __launch_bounds__(256) void k_reconstruct(
+    const int16_t* __restrict__ coeffs, int w, int h, int bw, int nb, int pitch,
+    size_t pstride, const float* __restrict__ srgb_lut, float* __restrict__ lin,
+    uint8_t* __restrict__ srgb, unsigned* __restrict__ clear_word, int strips_per_wg) {
+  reconstruct_body(coeffs, w, h, bw, nb, pitch, pstride, srgb_lut, lin, srgb, clear_word, strips_per_wg);
+}
+// The batched form for a decode's packed pixels (gz_decode_scan_batch_device): gridDim.y = the frames of the launch,
+// frame j the one in arena arena[j] -- coefficient arenas coeff_stride int16 apart, packed images srgb_stride bytes.
+__global__ __launch_bounds__(256) void k_reconstruct_batch(
+    const int16_t* __restrict__ coeffs, int w, int h, int bw, int nb, uint8_t* __restrict__ srgb, int strips_per_wg,
+    const int* __restrict__ arena, size_t coeff_stride, size_t srgb_stride) {
+  const size_t a = (size_t)arena[blockIdx.y];
+  reconstruct_body(coeffs + a * coeff_stride, w, h, bw, nb, w, (size_t)w * h, nullptr, nullptr, srgb + a * srgb_stride, nullptr,
+                   strips_per_wg);
 }
 
 // ------------------------------------------------------------ reconstruct: patches --
@@ -369,10 +385,9 @@ __global__ __launch_bounds__(256) void k_idct_blocks(const int16_t* __restrict__
 //
 // k_chroma_samples: integer IDCT of every block of the two subsampled components into two
 // u8 sample planes [cbh*8][cbw*8] (Cb, then Cr, plane stride cbw*8*cbh*8).
-__global__ __launch_bounds__(256) void k_chroma_samples(const int16_t* __restrict__ cb_blocks,
-                                                        const int16_t* __restrict__ cr_blocks,
-                                                        int cbw, int nbc,
-                                                        uint8_t* __restrict__ samples) {
+// (the body of k_chroma_samples and of its batched form, both below it: blockIdx.x is the workgroup of ONE frame)
+GZ_DEVFN void chroma_samples_body(const int16_t* __restrict__ cb_blocks, const int16_t* __restrict__ cr_blocks, int cbw, int nbc,
+                                  uint8_t* __restrict__ samples) {
   __shared__ int s_in[2][kBlocksPerWG][64];
   __shared__ int s_col[2][kBlocksPerWG][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -402,6 +417,21 @@ __global__ __launch_bounds__(256) void k_chroma_samples(const int16_t* __restric
     samples[c * pl + o] = (uint8_t)clamp255((acc + (257 << 17)) >> 18);
   }
 }
+__global__ __launch_bounds__(256) void k_chroma_samples(const int16_t* __restrict__ cb_blocks,
+                                                        const int16_t* __restrict__ cr_blocks,
+                                                        int cbw, int nbc,
+                                                        uint8_t* __restrict__ samples) {
+  chroma_samples_body(cb_blocks, cr_blocks, cbw, nbc, samples);
+}
+// gridDim.y = the frames of the launch, frame j in arena arena[j] (k_reconstruct_batch); coeffs: the arenas' base, cb_at
+// and cr_at the two components' first coefficient in an arena; the sample planes of two arenas lie samp_stride bytes apart.
+__global__ __launch_bounds__(256) void k_chroma_samples_batch(const int16_t* __restrict__ coeffs, size_t cb_at, size_t cr_at, int cbw, int nbc,
+                                                              uint8_t* __restrict__ samples, const int* __restrict__ arena,
+                                                              size_t coeff_stride, size_t samp_stride) {
+  const size_t a = (size_t)arena[blockIdx.y];
+  const int16_t* co = coeffs + a * coeff_stride;
+  chroma_samples_body(co + cb_at, co + cr_at, cbw, nbc, samples + a * samp_stride);
+}
 
 // Upsampled, rounded pixel (ToPixels) of a 2x2-subsampled component at (x, y) from its sample
 // plane (row pitch sw); mxs, mys = (w-1)/2, (h-1)/2.
@@ -418,7 +448,8 @@ GZ_DEVFN int chroma420_pixel(const uint8_t* __restrict__ sp, int sw, int mxs, in
 
 // k_reconstruct for a 4:2:0 frame: luma IDCT of a strip of 8 blocks as in k_reconstruct (which
 // follows below), chroma from the sample planes of k_chroma_samples, whole rows out.
-__global__ __launch_bounds__(256) void k_reconstruct420(
+// (the body of k_reconstruct420 and of its batched form, both below it: blockIdx.x is the workgroup of ONE frame)
+GZ_DEVFN void reconstruct420_body(
     const int16_t* __restrict__ ycoeffs, const uint8_t* __restrict__ samples, int w, int h, int bw,
     int nb, int cbw, int cbh, int pitch, size_t pstride, const float* __restrict__ srgb_lut,
     float* __restrict__ lin, uint8_t* __restrict__ srgb, unsigned* __restrict__ clear_word) {
@@ -506,6 +537,20 @@ __global__ __launch_bounds__(256) void k_reconstruct420(
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void k_reconstruct420(
+    const int16_t* __restrict__ ycoeffs, const uint8_t* __restrict__ samples, int w, int h, int bw,
+    int nb, int cbw, int cbh, int pitch, size_t pstride, const float* __restrict__ srgb_lut,
+    float* __restrict__ lin, uint8_t* __restrict__ srgb, unsigned* __restrict__ clear_word) {
+  reconstruct420_body(ycoeffs, samples, w, h, bw, nb, cbw, cbh, pitch, pstride, srgb_lut, lin, srgb, clear_word);
+}
+// gridDim.y = the frames of the launch, frame j in arena arena[j]: k_reconstruct_batch's and k_chroma_samples_batch's strides.
+__global__ __launch_bounds__(256) void k_reconstruct420_batch(
+    const int16_t* __restrict__ coeffs, const uint8_t* __restrict__ samples, int w, int h, int bw, int nb, int cbw, int cbh,
+    uint8_t* __restrict__ srgb, const int* __restrict__ arena, size_t coeff_stride, size_t samp_stride, size_t srgb_stride) {
+  const size_t a = (size_t)arena[blockIdx.y];
+  reconstruct420_body(coeffs + a * coeff_stride, samples + a * samp_stride, w, h, bw, nb, cbw, cbh, w, (size_t)w * h, nullptr, nullptr,
+                      srgb + a * srgb_stride, nullptr);
 }
 
 // ------------------------------------------------------------------------ quantize --

@@ -51,12 +51,26 @@ template <> struct emit_reads_lut<uint16_t> { static constexpr bool value = fals
 //   kIngestElementwise      element by element, as the partial group at the end of a row is in every instantiation
 // No path writes an element other than the (y, x, c) it converts: the destination may be a crop inside a larger
 // tensor, and its neighbours stay as they are.
-template <class T, int WIDE>
+// B... (empty, or one EmitBatch): the batched form, gridDim.y = the images of the launch -- image j is packed image
+// arena[j] of the scratch (rgb_stride bytes apart) and image slot[j] of the caller's tensor (stride_n elements apart);
+// WIDE is the caller's word for every one of them.
+struct EmitBatch {
+  const int* arena;
+  const int* slot;
+  size_t rgb_stride;
+  long long stride_n;
+};
+template <class T, int WIDE, class... B>
 __global__ __launch_bounds__(256) void k_emit_rgb(const uint8_t* __restrict__ rgb, int w, int h, T* __restrict__ data,
                                                   long long sy, long long sx, long long sc,
-                                                  const float* __restrict__ lut) {
+                                                  const float* __restrict__ lut, B... batch) {
   static_assert(WIDE == kIngestElementwise || WIDE == kIngestPlanarRows || WIDE == kIngestInterleavedRows, "k_emit_rgb: an unknown store path");
   constexpr int P = 16 / (int)sizeof(T);
+  if constexpr (sizeof...(B) > 0) {
+    const EmitBatch eb = (batch, ...);
+    rgb += (size_t)eb.arena[blockIdx.y] * eb.rgb_stride;
+    data += (long long)eb.slot[blockIdx.y] * eb.stride_n;
+  }
   __shared__ float s_lut[256];
   if constexpr (emit_reads_lut<T>::value) {   // (every thread of the block gets here)
     s_lut[threadIdx.x] = lut[threadIdx.x];
@@ -130,6 +144,27 @@ static inline void launch_emit_rgb(hipStream_t stream, const uint8_t* rgb, int w
       break;
     default:
       GZ_LAUNCH((k_emit_rgb<T, kIngestElementwise>), grid, block, stream, rgb, w, h, data, sy, sx, sc, lut);
+      break;
+  }
+}
+// The batched form: `count` images, image j from packed image arena[j] into image slot[j] of the tensor.  The 16-byte
+// stores need every image's base aligned: the first one's, and stride_n a multiple of the vector's elements.
+template <class T>
+static inline void launch_emit_rgb_batch(hipStream_t stream, const uint8_t* rgb, int w, int h, T* data, long long sn, long long sy,
+                                         long long sx, long long sc, const float* lut, const int* arena, const int* slot, int count,
+                                         size_t rgb_stride) {
+  constexpr int P = 16 / (int)sizeof(T);
+  const dim3 grid((unsigned)(((size_t)((w + P - 1) / P) * h + 255) / 256), (unsigned)count), block(256);
+  const EmitBatch eb = {arena, slot, rgb_stride, sn};
+  switch (sn % P == 0 ? ingest_wide_mode(data, sizeof(T), sy, sx, sc) : (int)kIngestElementwise) {
+    case kIngestPlanarRows:
+      GZ_LAUNCH((k_emit_rgb<T, kIngestPlanarRows, EmitBatch>), grid, block, stream, rgb, w, h, data, sy, sx, sc, lut, eb);
+      break;
+    case kIngestInterleavedRows:
+      GZ_LAUNCH((k_emit_rgb<T, kIngestInterleavedRows, EmitBatch>), grid, block, stream, rgb, w, h, data, sy, sx, sc, lut, eb);
+      break;
+    default:
+      GZ_LAUNCH((k_emit_rgb<T, kIngestElementwise, EmitBatch>), grid, block, stream, rgb, w, h, data, sy, sx, sc, lut, eb);
       break;
   }
 }

@@ -200,15 +200,17 @@ GZ_DEVFN void scandec_load_fast(uint16_t (*fast)[512], const ScanDecTables* __re
 }
 
 // Passes 1a / 1b.  FIRST: blind start, no boundary read; otherwise lane 0 of workgroup b > 0 enters with bnd_in[b - 1].
+// wg: the workgroup's index within its stream -- blockIdx.x of a launch over one stream; the state and the boundary
+// arrays are the stream's own (element 0 is its lane 0, its workgroup 0).
 template <bool FIRST>
 GZ_DEVFN void scandec_sync_body(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T, const ScanDecGeom& g,
                                 const ScanDecState& st, const unsigned long long* __restrict__ bnd_in,
-                                unsigned long long* __restrict__ bnd_out, unsigned* __restrict__ changed) {
+                                unsigned long long* __restrict__ bnd_out, unsigned* __restrict__ changed, int wg) {
   __shared__ uint16_t s_fast[kScanDecTables][512];
   __shared__ unsigned long long s_exit[kScanDecLanes];
   __shared__ int s_flag[2];
   const int t = threadIdx.x;
-  const int lane = (int)blockIdx.x * kScanDecLanes + t;
+  const int lane = wg * kScanDecLanes + t;
   const bool active = lane < g.nsub;
   scandec_load_fast(s_fast, T);
   if (t == 0) s_flag[0] = s_flag[1] = 0;
@@ -237,7 +239,7 @@ GZ_DEVFN void scandec_sync_body(const uint8_t* __restrict__ data, const ScanDecT
   for (int r = 0; r < kScanDecLanes; ++r) {
     unsigned long long in = my_in;
     if (t > 0) in = s_exit[t - 1];
-    else if (!FIRST && blockIdx.x > 0) in = bnd_in[blockIdx.x - 1];
+    else if (!FIRST && wg > 0) in = bnd_in[wg - 1];
     __syncthreads();   // every lane has read its neighbour's exit state, and last round's flag
     if (t == 0) s_flag[(r + 1) & 1] = 0;
     if (active && in != my_in) {
@@ -261,19 +263,19 @@ GZ_DEVFN void scandec_sync_body(const uint8_t* __restrict__ data, const ScanDecT
     st.count[lane] = cnt;
   }
   if (t == kScanDecLanes - 1 || lane == g.nsub - 1) {
-    bnd_out[blockIdx.x] = my_out;
+    bnd_out[wg] = my_out;
     if (!FIRST && my_out != was_out) atomicOr(changed, 1u);
   }
 }
 
 __global__ __launch_bounds__(256) void k_scandec_sync_first(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
                                                             ScanDecGeom g, ScanDecState st, unsigned long long* __restrict__ bnd_out) {
-  scandec_sync_body<true>(data, T, g, st, nullptr, bnd_out, nullptr);
+  scandec_sync_body<true>(data, T, g, st, nullptr, bnd_out, nullptr, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_scandec_sync_next(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
                                                            ScanDecGeom g, ScanDecState st, const unsigned long long* __restrict__ bnd_in,
                                                            unsigned long long* __restrict__ bnd_out, unsigned* __restrict__ changed) {
-  scandec_sync_body<false>(data, T, g, st, bnd_in, bnd_out, changed);
+  scandec_sync_body<false>(data, T, g, st, bnd_in, bnd_out, changed, (int)blockIdx.x);
 }
 
 // Where block b of the scan goes: its component, and its first coefficient in the frame layout or -1 (MCU padding).
@@ -325,17 +327,19 @@ __constant__ unsigned char kScanDecNatural[64] = {
 
 // Pass 3.  res[0]: the first error (block << 3 | reason, 0xffffffff: none), res[1]: the bit behind the last block's last
 // symbol (0xffffffff: the scan never got there), INPUT: res[2] the large-coefficient word (zero when the kernel starts).
-// coeffs and dcd are zero when the kernel starts.
+// coeffs and dcd are zero when the kernel starts.  wg as in scandec_sync_body; off[lane] - off_base is the lane's first
+// block (off_base: what the prefix sums hold at the stream's lane 0 -- 0 where they cover one stream).
 template <bool INPUT>
 GZ_DEVFN void scandec_write_body(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T, const ScanDecGeom& g,
                                  const unsigned long long* __restrict__ entry, const unsigned long long* __restrict__ off,
-                                 int16_t* __restrict__ coeffs, int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
+                                 int16_t* __restrict__ coeffs, int16_t* __restrict__ dcd, unsigned* __restrict__ res, int wg,
+                                 unsigned long long off_base) {
   __shared__ uint16_t s_fast[kScanDecTables][512];
   scandec_load_fast(s_fast, T);
   __syncthreads();
-  const int lane = (int)blockIdx.x * kScanDecLanes + (int)threadIdx.x;
+  const int lane = wg * kScanDecLanes + (int)threadIdx.x;
   if (lane >= g.nsub) return;
-  const unsigned long long first = off[lane];
+  const unsigned long long first = off[lane] - off_base;
   if (first >= (unsigned long long)g.total) return;
   int b = (int)first;
   const unsigned long long in = entry[lane];
@@ -380,13 +384,13 @@ __global__ __launch_bounds__(256) void k_scandec_write(const uint8_t* __restrict
                                                        const unsigned long long* __restrict__ entry,
                                                        const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
                                                        int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
-  scandec_write_body<false>(data, T, g, entry, off, coeffs, dcd, res);
+  scandec_write_body<false>(data, T, g, entry, off, coeffs, dcd, res, (int)blockIdx.x, 0ull);
 }
 __global__ __launch_bounds__(256) void k_scandec_write_input(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
                                                              ScanDecGeom g, const unsigned long long* __restrict__ entry,
                                                              const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
                                                              int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
-  scandec_write_body<true>(data, T, g, entry, off, coeffs, dcd, res);
+  scandec_write_body<true>(data, T, g, entry, off, coeffs, dcd, res, (int)blockIdx.x, 0ull);
 }
 
 // Pass 4: one workgroup per component; a thread sums a run of ceil(n / 256) of the component's blocks in scan order.
@@ -437,6 +441,65 @@ __global__ __launch_bounds__(256) void k_scandec_dc(const int16_t* __restrict__ 
 __global__ __launch_bounds__(256) void k_scandec_dc_input(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T, ScanDecGeom g,
                                                           int16_t* __restrict__ coeffs, unsigned* __restrict__ res) {
   scandec_dc_body<true>(dcd, T, g, coeffs, res);
+}
+
+// ------------------------------------------------------------------------------------------------ batches ----
+// N streams of one frame size through ONE launch of each pass (gz_decode_scan_batch_device, api/entry_scandec_batch.h).
+// The streams lie in one buffer, each at a 16-byte aligned offset; stream i has its own tables T[i] and its descriptor:
+// its geometry (end_bits and nsub its own; bit offsets stay relative to its own first byte, 32 bits), and where its
+// parts begin in the arrays the streams share.  Every stream's lanes are padded to whole workgroups, so a workgroup
+// belongs to ONE stream -- wg_image[blockIdx.x] -- and its LDS tables are that stream's; entry, exit, count and the
+// prefix sums span the padded lanes, of which the padding is inactive and counts 0 blocks (count is zero when the
+// first kernel starts).  The bodies are the single stream's, on pointers moved to the stream's first lane, workgroup
+// and block: no lane of one stream reads or writes a word of another's, and lane 0 of a stream's first workgroup has
+// no workgroup before it, whatever lies in front of it in the arrays.
+struct ScanDecImage {
+  ScanDecGeom g;
+  unsigned long long data_at;    // its first byte in the streams' buffer
+  unsigned long long coeff_at;   // its coefficient arena (frame layout), in int16 from the arenas' base
+  int wg0;                       // its first workgroup
+  int lane0;                     // its first lane in the padded lane space: wg0 * kScanDecLanes
+  int block0;                    // its first block in the DC differences
+  int nwg;                       // its workgroups
+};
+
+__global__ __launch_bounds__(256) void k_scandec_sync_first_batch(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
+                                                                  const ScanDecImage* __restrict__ images, const int* __restrict__ wg_image,
+                                                                  ScanDecState st, unsigned long long* __restrict__ bnd_out) {
+  const int i = wg_image[blockIdx.x];
+  const ScanDecImage im = images[i];
+  const ScanDecState mine = {st.entry + im.lane0, st.exit + im.lane0, st.count + im.lane0};
+  scandec_sync_body<true>(data + im.data_at, T + i, im.g, mine, nullptr, bnd_out + im.wg0, nullptr, (int)blockIdx.x - im.wg0);
+}
+// changed: one word per stream, zero when the kernel starts.  A stream of one workgroup has nothing to do here.
+__global__ __launch_bounds__(256) void k_scandec_sync_next_batch(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
+                                                                 const ScanDecImage* __restrict__ images, const int* __restrict__ wg_image,
+                                                                 ScanDecState st, const unsigned long long* __restrict__ bnd_in,
+                                                                 unsigned long long* __restrict__ bnd_out, unsigned* __restrict__ changed) {
+  const int i = wg_image[blockIdx.x];
+  const ScanDecImage im = images[i];
+  if (im.nwg == 1) return;   // (the whole workgroup)
+  const ScanDecState mine = {st.entry + im.lane0, st.exit + im.lane0, st.count + im.lane0};
+  scandec_sync_body<false>(data + im.data_at, T + i, im.g, mine, bnd_in + im.wg0, bnd_out + im.wg0, changed + i, (int)blockIdx.x - im.wg0);
+}
+// off: the prefix sums over ALL padded lanes; res: four words per stream.  (the output mode only)
+__global__ __launch_bounds__(256) void k_scandec_write_batch(const uint8_t* __restrict__ data, const ScanDecTables* __restrict__ T,
+                                                             const ScanDecImage* __restrict__ images, const int* __restrict__ wg_image,
+                                                             const unsigned long long* __restrict__ entry,
+                                                             const unsigned long long* __restrict__ off, int16_t* __restrict__ coeffs,
+                                                             int16_t* __restrict__ dcd, unsigned* __restrict__ res) {
+  const int i = wg_image[blockIdx.x];
+  const ScanDecImage im = images[i];
+  scandec_write_body<false>(data + im.data_at, T + i, im.g, entry + im.lane0, off + im.lane0, coeffs + im.coeff_at, dcd + im.block0,
+                            res + 4 * i, (int)blockIdx.x - im.wg0, off[im.lane0]);
+}
+// grid (component, stream): one workgroup per pair.
+__global__ __launch_bounds__(256) void k_scandec_dc_batch(const int16_t* __restrict__ dcd, const ScanDecTables* __restrict__ T,
+                                                          const ScanDecImage* __restrict__ images, int16_t* __restrict__ coeffs,
+                                                          unsigned* __restrict__ res) {
+  const int i = (int)blockIdx.y;
+  const ScanDecImage im = images[i];
+  scandec_dc_body<false>(dcd + im.block0, T + i, im.g, coeffs + im.coeff_at, res + 4 * i);
 }
 
 // ---------------------------------------------------------------------------------------------- host side ----
@@ -516,6 +579,25 @@ inline void launch_scandec_write_input(hipStream_t stream, const uint8_t* data, 
 inline void launch_scandec_dc_input(hipStream_t stream, int ncomp, const int16_t* dcd, const ScanDecTables* T, const ScanDecGeom& g,
                                     int16_t* coeffs, unsigned* res) {
   GZ_LAUNCH(k_scandec_dc_input, dim3(ncomp), dim3(kScanDecLanes), stream, dcd, T, g, coeffs, res);
+}
+// The batched forms: nwg workgroups in all, n streams.
+inline void launch_scandec_sync_first_batch(hipStream_t stream, int nwg, const uint8_t* data, const ScanDecTables* T, const ScanDecImage* images,
+                                            const int* wg_image, const ScanDecState& st, unsigned long long* bnd_out) {
+  GZ_LAUNCH(k_scandec_sync_first_batch, dim3(nwg), dim3(kScanDecLanes), stream, data, T, images, wg_image, st, bnd_out);
+}
+inline void launch_scandec_sync_next_batch(hipStream_t stream, int nwg, const uint8_t* data, const ScanDecTables* T, const ScanDecImage* images,
+                                           const int* wg_image, const ScanDecState& st, const unsigned long long* bnd_in,
+                                           unsigned long long* bnd_out, unsigned* changed) {
+  GZ_LAUNCH(k_scandec_sync_next_batch, dim3(nwg), dim3(kScanDecLanes), stream, data, T, images, wg_image, st, bnd_in, bnd_out, changed);
+}
+inline void launch_scandec_write_batch(hipStream_t stream, int nwg, const uint8_t* data, const ScanDecTables* T, const ScanDecImage* images,
+                                       const int* wg_image, const unsigned long long* entry, const unsigned long long* off, int16_t* coeffs,
+                                       int16_t* dcd, unsigned* res) {
+  GZ_LAUNCH(k_scandec_write_batch, dim3(nwg), dim3(kScanDecLanes), stream, data, T, images, wg_image, entry, off, coeffs, dcd, res);
+}
+inline void launch_scandec_dc_batch(hipStream_t stream, int ncomp, int n, const int16_t* dcd, const ScanDecTables* T, const ScanDecImage* images,
+                                    int16_t* coeffs, unsigned* res) {
+  GZ_LAUNCH(k_scandec_dc_batch, dim3(ncomp, n), dim3(kScanDecLanes), stream, dcd, T, images, coeffs, res);
 }
 
 }  // namespace gz

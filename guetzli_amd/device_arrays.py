@@ -198,6 +198,14 @@ def image_destination(x, w, h, layout, dtypes, device, what):
     return rec._replace(strides=rec.strides if layout == "HWC" else rec.strides[1:] + rec.strides[:1])
 
 
+def batch_destination(x, n, w, h, layout, dtypes, device, what):
+    """destination() for n images of w x h x 3 samples, [n] + image_shape(w, h, layout), with the strides as (n, y, x, c)."""
+    shape = (n,) + image_shape(w, h, layout)
+    rec = check_destination(read(x, device, what, dtypes=None), shape, dtypes, what)
+    st = rec.strides
+    return rec._replace(strides=st if layout == "HWC" else (st[0],) + st[2:] + st[1:2])
+
+
 # ---- the seams: a fresh tensor, a host array brought over ----
 def new_tensor(shape, dtype, ordinal):
     """A fresh torch tensor of `shape` and `dtype` (a name, or torch's own) on GPU `ordinal`, from the calling thread's

@@ -12,7 +12,7 @@ import time
 
 from . import device_arrays as da
 from .device_arrays import is_device_resident   # (its home; importable and patchable here, as ever)
-from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_batch, device_map, device_map_batch, device_output, device_pixels
+from .capi import GZ_DT_BF16, GZ_DT_F16, GZ_DT_F32, GZ_DT_U8, GZ_DT_U16, GZ_SAMPLES_LINEAR, GZ_SAMPLES_SRGB8, GzDevicePixels, device_batch, device_map, device_map_batch, device_output, device_output_batch, device_pixels
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_HOST_LIB = os.path.join(HERE, "libguetzli_amd_host.so")
@@ -91,6 +91,10 @@ class HostLibrary:
             if hasattr(self.lib, name):   # (... and one built before JPEG input could come from it has neither of these)
                 getattr(self.lib, name).restype = C.c_long
                 getattr(self.lib, name).argtypes = args
+        if hasattr(self.lib, "gzh_decode_jpeg_batch_device"):   # (... and one built before batches were decoded lacks this one)
+            self.lib.gzh_decode_jpeg_batch_device.restype = C.c_long
+            self.lib.gzh_decode_jpeg_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                              C.c_uint64, C.c_void_p, C.c_void_p]
         self.lib.gzh_butteraugli_score_for_quality.restype = C.c_double
         self.lib.gzh_butteraugli_score_for_quality.argtypes = [C.c_double]
 
@@ -243,6 +247,29 @@ class HostLibrary:
             raise RuntimeError("guetzli_amd.DecodeJpegToRGB failed (see stderr)" if n == -1 else
                                "guetzli_amd.DecodeJpegToRGB raised a C++ exception (see stderr)")
         return self._entropy_info(info)
+
+    def decode_jpeg_batch_device(self, jpegs, ptr, dtype, strides, size, stream=0, device=0, entropy="device", subseq_bytes=0,
+                                 max_sync_rounds=0, scratch_bytes=0):
+        """guetzli_amd::DecodeJpegBatchToRGB: the raw form.  jpegs: N bytes objects of size = (w, h) pixels each; ptr = address,
+        in the memory of GPU `device`, of element (0, 0, 0, 0) of the N x h x w x 3 tensor they decode into; strides = (n, y,
+        x, c) in elements.  Returns the N entropy infos of decode_jpeg_device_entropy.  ValueError names the file that was
+        refused."""
+        n = len(jpegs)
+        bufs = [np.frombuffer(bytes(j), np.uint8) for j in jpegs]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (C.c_long * n)(*[b.size for b in bufs])
+        out = device_output_batch(ptr, DTYPE_CODES.get(dtype, dtype), strides, n, stream)
+        info, failed = (C.c_int64 * (6 * n))(), C.c_int(-1)
+        w, h = size
+        rc = self.lib.gzh_decode_jpeg_batch_device(ptrs, lens, n, device, C.addressof(out), w, h,
+                                                   self._entropy_mode(entropy, subseq_bytes, max_sync_rounds), int(scratch_bytes), info,
+                                                   C.byref(failed))
+        if rc != 0:
+            if rc == -1 and failed.value >= 0:
+                raise ValueError(f"jpegs[{failed.value}] is not a JPEG this library decodes to {w} x {h} pixels (see stderr)")
+            raise RuntimeError("guetzli_amd.DecodeJpegBatchToRGB failed (see stderr)" if rc == -1 else
+                               "guetzli_amd.DecodeJpegBatchToRGB raised a C++ exception (see stderr)")
+        return [self._entropy_info(info[6 * i:6 * i + 6]) for i in range(n)]
 
     def decode_jpeg_coeffs(self, data, entropy="host", device=0, subseq_bytes=0, max_sync_rounds=0):
         """The dequantised coefficients DecodeJpegToRGB hands to the device, by either entropy path: (int16 [blocks][64] in
@@ -469,6 +496,60 @@ def _decode(jpeg, out, dtype, layout, device, stream, entropy, subseq_bytes=0, m
         return out, none
     return out, lib.decode_jpeg_device_entropy(jpeg, dst.ptr, dst.dtype, dst.strides, stream=consumer, device=dst.ordinal, size=(w, h),
                                                entropy=entropy, subseq_bytes=subseq_bytes, max_sync_rounds=max_sync_rounds)
+
+
+def decode_batch(jpegs, out=None, dtype="uint8", layout="HWC", device=None, stream=None, entropy="device", scratch_bytes=0):
+    """decode() of N JPEGs of ONE decoded size into one tensor on the GPU, [N,H,W,3] ("HWC") or [N,3,H,W] ("CHW"): image i
+    is, bit for bit, decode(jpegs[i]).  entropy="device" (this function's default, and its reason to exist): the baseline
+    scans of the whole batch are read on the GPU by ONE launch of every kernel of the device's Huffman decoder per sampling
+    (grey, 4:4:4, 4:2:0) instead of one set of launches and host round trips per file -- a minibatch of thumbnails costs
+    little more than one of them.  Files whose scan that decoder does not take (restart intervals, progressive, other
+    samplings) or reaches no verdict on are read by the host into their image, silently: mixed batches are fine.
+    entropy="host": every file by the host's reader.
+    jpegs: a sequence of bytes-likes; ValueError where their frame headers differ in size (it names the sizes and the
+    first odd index), or where a file is refused (it names the index).  out=: a 4-D GPU tensor, or an object with
+    __cuda_array_interface__, of that shape under ANY non-negative strides without aliasing -- x[::2], crops -- and any
+    dtype of decode(); it is filled without touching what surrounds it, and returned.  device, stream, the element
+    conversions: decode()'s.  scratch_bytes= caps the device memory of the call's temporaries (default 2 GiB; about 200
+    bytes per pixel at 4:4:4, 100 at 4:2:0, plus the streams): a batch that needs more runs in chunks, with the same
+    results."""
+    return _decode_batch(jpegs, out, dtype, layout, device, stream, entropy, scratch_bytes)[0]
+
+
+def decode_batch_info(jpegs, out=None, dtype="uint8", layout="HWC", device=None, stream=None, entropy="device", scratch_bytes=0,
+                      subseq_bytes=0, max_sync_rounds=0):
+    """decode_batch() that says what it did -> (pixels, infos): infos[i] as decode_info()'s dict for jpegs[i], without
+    "decoded"."""
+    return _decode_batch(jpegs, out, dtype, layout, device, stream, entropy, scratch_bytes, subseq_bytes, max_sync_rounds)
+
+
+def _decode_batch(jpegs, out, dtype, layout, device, stream, entropy, scratch_bytes, subseq_bytes=0, max_sync_rounds=0):
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy={entropy!r}: 'host' or 'device'")
+    if isinstance(jpegs, (bytes, bytearray, memoryview)):
+        raise TypeError("jpegs is a sequence of JPEGs, not one: decode() takes one")
+    jpegs = [bytes(j) for j in jpegs]
+    if not jpegs:
+        raise ValueError("jpegs is an empty batch")
+    sizes = [_jpeg_dimensions(j) for j in jpegs]   # (the frame headers alone: the decode checks the size each stream really has)
+    w, h = sizes[0]
+    if w <= 0 or h <= 0:
+        raise ValueError("jpegs[0] is not a JPEG: no frame header")
+    odd = next((i for i, s in enumerate(sizes) if s != sizes[0]), None)
+    if odd is not None:
+        raise ValueError(f"the JPEGs differ in size: jpegs[{odd}] holds {sizes[odd][0]} x {sizes[odd][1]} pixels, jpegs[0] {w} x {h}")
+    n = len(jpegs)
+    shape = (n,) + da.image_shape(w, h, layout)
+    if out is None:
+        if device is None:
+            import torch
+            device = torch.cuda.current_device()
+        out = da.new_tensor(shape, dtype, device)
+    dst = da.batch_destination(out, n, w, h, layout, da.DTYPES, device, "out=")
+    infos = load_host().decode_jpeg_batch_device(jpegs, dst.ptr, dst.dtype, dst.strides, (w, h), stream=da.stream_or(stream, dst.stream),
+                                                 device=dst.ordinal, entropy=entropy, subseq_bytes=subseq_bytes,
+                                                 max_sync_rounds=max_sync_rounds, scratch_bytes=scratch_bytes)
+    return out, infos
 
 
 def _with_decoded(job, decoded, w, h, ordinal):

@@ -247,6 +247,37 @@ long gzh_decode_jpeg_device_entropy(const uint8_t* data, long len, int device, c
   GZH_GUARD_END
 }
 
+// DecodeJpegBatchToRGB: the n JPEGs data[i] (lens[i] bytes) of w x h pixels each into the n images of `out`, a
+// gz_device_output_batch (include/guetzli_amd.h) on GPU `device`; mode as above, scratch_bytes = the device call's
+// scratch_cap_bytes; info[6 n] (CopyDecodeInfo per image; may be NULL).  0, or -1 (message on stderr) with *failed (may be
+// NULL) the index of the file that was refused, -1 where the arguments were.
+long gzh_decode_jpeg_batch_device(const uint8_t* const* data, const long* lens, int n, int device, const gz_device_output_batch* out, int w,
+                                  int h, const int* mode, uint64_t scratch_bytes, int64_t* info, int* failed) {
+  GZH_GUARD_BEGIN
+  if (failed) *failed = -1;
+  if (!data || !lens || n < 1 || w < 0 || h < 0) return -1;
+  if (!out || out->struct_size != (int)sizeof(gz_device_output_batch) || out->n != n) {
+    fprintf(stderr, "guetzli_amd: gzh_decode_jpeg_batch_device: not a gz_device_output_batch of this library and of n images\n");
+    return -1;
+  }
+  std::vector<std::string> jpegs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!data[i] || lens[i] < 0) return -1;
+    jpegs[(size_t)i].assign((const char*)data[i], (size_t)lens[i]);
+  }
+  guetzli_amd::DeviceOutputBatch o;
+  o.dtype = out->dtype;
+  o.data = out->data;
+  o.stride_n = out->stride_n; o.stride_y = out->stride_y; o.stride_x = out->stride_x; o.stride_c = out->stride_c;
+  o.consumer_stream = out->consumer_stream;
+  std::vector<guetzli_amd::DecodeInfo> infos;
+  const bool ok = guetzli_amd::DecodeJpegBatchToRGB(jpegs, device, o, w, h, EntropyFrom(mode), &infos, failed, (size_t)scratch_bytes);
+  if (info)
+    for (size_t i = 0; i < infos.size(); ++i) CopyDecodeInfo(infos[i], info + 6 * i);
+  return ok ? 0 : -1;
+  GZH_GUARD_END
+}
+
 // The stream's dequantised coefficients in the frame layout (what DecodeJpegToRGB hands to the device) by either entropy
 // path: returns their count (copied if it fits `cap` elements), -1 if the stream is refused; whf[3] = width, height,
 // chroma factor; info as above.  meta (optional, meta_cap bytes): what the reader kept beside the coefficients -- every

@@ -482,7 +482,12 @@ struct Decoder {
       memcpy(rq.quant[i], jpg->quant[found].values, sizeof(rq.quant[i]));
     }
     size_t end = 0;
-    if (!(*scan_decoder)(rq, &end) || end > rest) return false;
+    if (!(*scan_decoder)(rq, &end)) return false;
+    if (end == kScanDecoderStop) {   // the decoder has what it wanted: the parse ends here (Run)
+      jpg->stopped_at_scan = true;
+      return true;
+    }
+    if (end > rest) return false;
     *pos += end;
     jpg->scan_decoded_elsewhere = true;
     return true;
@@ -631,6 +636,7 @@ struct Decoder {
           else return fail("unsupported marker");
       }
       if (!ok) return false;
+      if (jpg->stopped_at_scan) return true;
     } while (marker != 0xd9);
     if (!found_sof) return fail("no SOF marker");
     if (scan_decoder && !jpg->scan_decoded_elsewhere) AllocateCoeffs();

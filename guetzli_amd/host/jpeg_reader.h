@@ -42,6 +42,7 @@ struct JpegInput {
   std::vector<std::string> com_data;    // segment with its length bytes, :411-422
   std::string tail_data;                // bytes after EOI (:1046-1049)
   bool scan_decoded_elsewhere = false;  // a ScanDecoder took the scan: `coeffs` of the components are EMPTY (never allocated)
+  bool stopped_at_scan = false;         // a ScanDecoder ended the parse at its scan (kScanDecoderStop): the headers in front of it, no more
 
   bool Is444() const;                   // jpeg_data.cc:36-46
   bool Is420() const;                   // jpeg_data.cc:24-34
@@ -62,7 +63,11 @@ struct ScanRequest {
 // true: the decoder has produced the scan's coefficients (dequantised, wherever its owner wants them) exactly as the
 // block loop would have, and *end_offset is where BitReader::Finish would leave the parser, from `data`: the parser goes
 // on there, so whatever follows gets the verdict it always got.  false: the block loop runs as if there were no decoder.
+// true with *end_offset = kScanDecoderStop: the decoder only wanted to see the request (a batch collects the scans of
+// many files before it decodes any).  ReadJpeg returns true at once, with JpegInput::stopped_at_scan set and nothing read
+// behind the scan's header: no coefficients, no tail, none of the checks at the end of the file.
 typedef std::function<bool(const ScanRequest&, size_t* end_offset)> ScanDecoder;
+constexpr size_t kScanDecoderStop = (size_t)-1;
 
 // false on anything the stream does not allow; *error (optional) gets a short description.  scan_decoder (optional) is
 // offered every eligible scan.

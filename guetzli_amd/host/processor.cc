@@ -23,6 +23,8 @@ extern "C" int gz_decode_coeffs(int device, const int16_t* coeffs, int w, int h,
 extern "C" int gz_decode_scan(int device, const gz_scan* scan, int16_t* host_coeffs, gz_scan_result* result) __attribute__((weak));
 extern "C" int gz_decode_scan_device(int device, const gz_scan* scan, const gz_device_output* out, gz_scan_result* result) __attribute__((weak));
 extern "C" int gz_decode_scan_input(int device, const gz_scan* scan, int16_t* host_coeffs, int* large_coeff, gz_scan_result* result) __attribute__((weak));
+extern "C" int gz_decode_scan_batch_device(int device, int n, const gz_scan* scans, const int* slots, const gz_device_output_batch* out,
+                                           gz_scan_result* results, size_t scratch_cap_bytes) __attribute__((weak));
 
 namespace guetzli_amd {
 
@@ -590,17 +592,37 @@ struct DeviceScan {
   const gz_device_output* out = nullptr;   // pixels straight into the caller's image ...
   std::vector<int16_t>* coeffs = nullptr;  // ... or coefficients to the host
   int expect_w = 0, expect_h = 0;
+  // A batch (DecodeJpegBatchToRGB) asks the device for many files at once, so the hook runs twice per file: collecting --
+  // the request is kept as the gz_scan the device takes, and the parse stops -- and, after the device call, replaying: the
+  // hook answers with that call's return code and result for this scan.
+  gz_scan* collect = nullptr;
+  bool collected = false;
+  const gz_scan_result* replay = nullptr;
+  int replay_rc = 0;
   DecodeInfo info;
   bool operator()(const ScanRequest& rq, size_t* end_offset) {
-    if (out ? !gz_decode_scan_device : !gz_decode_scan) return false;
+    if (collect || replay ? !gz_decode_scan_batch_device : out ? !gz_decode_scan_device : !gz_decode_scan) return false;
     if ((expect_w > 0 || expect_h > 0) && (rq.width != expect_w || rq.height != expect_h)) return false;   // (refused below)
     if (rq.ncomp == 3 && !HasYCbCrColorSpace(*rq.so_far)) return false;
+    if (collect) {
+      ScanFromRequest(rq, opt, collect);
+      collected = true;
+      *end_offset = kScanDecoderStop;
+      return true;
+    }
     static thread_local gz_scan sc;
-    ScanFromRequest(rq, opt, &sc);
+    if (!replay) ScanFromRequest(rq, opt, &sc);
     gz_scan_result res;
     memset(&res, 0, sizeof(res));
     int rc;
-    if (out) {
+    if (replay) {
+      rc = replay_rc;
+      res = *replay;
+      if (rc != GZ_OK) {   // (the batch's call failed, and has said so once for all its scans)
+        info.rc = rc;
+        return false;
+      }
+    } else if (out) {
       rc = gz_decode_scan_device(device, &sc, out, &res);
     } else {
       const int f = rq.chroma_factor;
@@ -624,6 +646,9 @@ struct DeviceScan {
   }
 };
 
+// (the second half of DecodedCoeffs: what a JpegInput the reader has filled holds)
+bool FrameCoeffs(const JpegInput& jpg, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs);
+
 bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs,
                    DeviceScan* scan = nullptr, JpegInput* meta = nullptr) {
   JpegInput local;
@@ -635,6 +660,11 @@ bool DecodedCoeffs(const std::string& data, int* w_out, int* h_out, int* factor_
     return false;
   }
   if (scan) scan->info.device_path = jpg.scan_decoded_elsewhere;
+  if (jpg.stopped_at_scan) return true;   // (a collecting hook: nothing was decoded, and nothing is asked for yet)
+  return FrameCoeffs(jpg, w_out, h_out, factor_out, coeffs);
+}
+
+bool FrameCoeffs(const JpegInput& jpg, int* w_out, int* h_out, int* factor_out, std::vector<int16_t>* coeffs) {
   const size_t ncomp = jpg.components.size();
   if (!(ncomp == 1 || (ncomp == 3 && HasYCbCrColorSpace(jpg) && (jpg.Is420() || jpg.Is444())))) {   // DecodeJpegToRGB is empty
     fprintf(stderr, "Unsupported input JPEG file (e.g. unsupported downsampling mode).\n");
@@ -711,10 +741,8 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
   return DecodeJpegToRGB(jpeg, device, out, w_out, h_out, expect_w, expect_h, EntropyOptions(), nullptr);
 }
 
-bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w_out, int* h_out, int expect_w,
-                     int expect_h, const EntropyOptions& entropy, DecodeInfo* info) {
-  int w = 0, h = 0, factor = 1;
-  std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
+namespace {
+gz_device_output OutputOf(const DeviceOutput& out) {
   gz_device_output o;
   memset(&o, 0, sizeof(o));
   o.struct_size = (int)sizeof(o);
@@ -722,17 +750,21 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
   o.data = out.data;
   o.stride_y = out.stride_y; o.stride_x = out.stride_x; o.stride_c = out.stride_c;
   o.consumer_stream = out.consumer_stream;
-  DeviceScan scan;
-  scan.device = device;
-  scan.opt = entropy;
-  scan.out = &o;
-  scan.expect_w = expect_w; scan.expect_h = expect_h;
-  const bool ok = DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs, entropy.device ? &scan : nullptr);
-  if (info) *info = scan.info;
+  return o;
+}
+
+// One JPEG into `o` with the reader's hook in the state the caller has given it (nullptr: the host reads the scan).  A
+// collecting hook that took the scan ends the call there: nothing is decoded yet.
+bool DecodeToOutput(const std::string& jpeg, int device, const gz_device_output& o, int* w_out, int* h_out, int expect_w, int expect_h,
+                    DeviceScan* scan) {
+  int w = 0, h = 0, factor = 1;
+  std::vector<int16_t>& coeffs = DecodeScratchCoeffs();
+  const bool ok = DecodedCoeffs(jpeg, &w, &h, &factor, &coeffs, scan);
   if (!ok) return false;
+  if (scan && scan->collected) return true;
   if (w_out) *w_out = w;
   if (h_out) *h_out = h;
-  if (scan.info.device_path) return true;   // (the pixels are in `out`; the size was checked in front of the device call)
+  if (scan && scan->info.device_path) return true;   // (the pixels are in `o`; the size was checked in front of the device call)
   if ((expect_w > 0 || expect_h > 0) && (w != expect_w || h != expect_h)) {
     fprintf(stderr, "guetzli_amd: the JPEG holds %d x %d pixels, the destination was made for %d x %d\n", w, h, expect_w, expect_h);
     return false;
@@ -740,6 +772,123 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
   if (!gz_decode_coeffs_device) return DecodeFailed("device-resident output (not in this device library)", GZ_E_STATE);
   const int rc = gz_decode_coeffs_device(device, coeffs.data(), w, h, factor, &o);
   return rc == GZ_OK ? true : DecodeFailed("gz_decode_coeffs_device", rc);
+}
+}  // namespace
+
+bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& out, int* w_out, int* h_out, int expect_w,
+                     int expect_h, const EntropyOptions& entropy, DecodeInfo* info) {
+  const gz_device_output o = OutputOf(out);
+  DeviceScan scan;
+  scan.device = device;
+  scan.opt = entropy;
+  scan.out = &o;
+  scan.expect_w = expect_w; scan.expect_h = expect_h;
+  const bool ok = DecodeToOutput(jpeg, device, o, w_out, h_out, expect_w, expect_h, entropy.device ? &scan : nullptr);
+  if (info) *info = scan.info;
+  return ok;
+}
+
+bool DecodeJpegBatchToRGB(const std::vector<std::string>& jpegs, int device, const DeviceOutputBatch& out, int expect_w, int expect_h,
+                          const EntropyOptions& entropy, std::vector<DecodeInfo>* infos, int* failed, size_t scratch_cap_bytes) {
+  const int n = (int)jpegs.size();
+  if (infos) infos->assign((size_t)n, DecodeInfo());
+  if (failed) *failed = -1;
+  auto fail = [failed](int i) {
+    if (failed) *failed = i;
+    fprintf(stderr, "guetzli_amd: image %d of the batch could not be decoded\n", i);
+    return false;
+  };
+  if (n < 1) return true;
+  if (expect_w <= 0 || expect_h <= 0) {   // the batch's size is the first file's
+    if (!JpegSize(jpegs[0], &expect_w, &expect_h)) return fail(0);
+  }
+  const size_t elem = out.dtype == DeviceImage::kU8 ? 1 : out.dtype == DeviceImage::kF32 ? 4 : 2;
+  auto image = [&](int i) {
+    DeviceOutput one;
+    one.dtype = out.dtype;
+    one.data = (char*)out.data + (size_t)i * (size_t)out.stride_n * elem;
+    one.stride_y = out.stride_y; one.stride_x = out.stride_x; one.stride_c = out.stride_c;
+    one.consumer_stream = out.consumer_stream;
+    return OutputOf(one);
+  };
+  std::vector<DeviceScan> hooks((size_t)n);
+  std::vector<gz_scan> scans;
+  std::vector<int> owner;   // scans[k] is image owner[k]'s
+  std::vector<gz_scan_result> verdicts;
+  std::vector<int> call_rc;
+  if (entropy.device && gz_decode_scan_batch_device) {
+    // the collecting pass: every file up to its scan; a file whose scan is not offered is read to its end and decoded here
+    scans.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      scans.emplace_back();
+      DeviceScan& hook = hooks[(size_t)i];
+      hook.device = device;
+      hook.opt = entropy;
+      hook.expect_w = expect_w; hook.expect_h = expect_h;
+      hook.collect = &scans.back();
+      const gz_device_output o = image(i);
+      hook.out = &o;
+      const bool ok = DecodeToOutput(jpegs[(size_t)i], device, o, nullptr, nullptr, expect_w, expect_h, &hook);
+      hook.out = nullptr;
+      hook.collect = nullptr;
+      if (!ok) return fail(i);
+      if (hook.collected) owner.push_back(i); else scans.pop_back();
+    }
+    // one device call per sampling: grey, 4:4:4, 4:2:0
+    verdicts.resize(scans.size());
+    call_rc.assign(scans.size(), GZ_OK);
+    gz_device_output_batch ob;
+    memset(&ob, 0, sizeof(ob));
+    ob.struct_size = (int)sizeof(ob);
+    ob.dtype = out.dtype;
+    ob.data = out.data;
+    ob.stride_n = out.stride_n; ob.stride_y = out.stride_y; ob.stride_x = out.stride_x; ob.stride_c = out.stride_c;
+    ob.consumer_stream = out.consumer_stream;
+    ob.n = n;
+    for (int group = 0; group < 3; ++group) {
+      const int ncomp = group == 0 ? 1 : 3, factor = group == 2 ? 2 : 1;
+      std::vector<gz_scan> members;
+      std::vector<int> slots, at;
+      for (size_t k = 0; k < scans.size(); ++k)
+        if (scans[k].ncomp == ncomp && scans[k].chroma_factor == factor) {
+          members.push_back(scans[k]);
+          slots.push_back(owner[k]);
+          at.push_back((int)k);
+        }
+      if (members.empty()) continue;
+      std::vector<gz_scan_result> res(members.size());
+      const int rc = gz_decode_scan_batch_device(device, (int)members.size(), members.data(), slots.data(), &ob, res.data(), scratch_cap_bytes);
+      if (rc != GZ_OK)
+        fprintf(stderr, "guetzli_amd: the device's batched scan decoder failed (%s): the host reads the scans it left\n", gz_strerror(rc));
+      for (size_t k = 0; k < members.size(); ++k) {
+        verdicts[(size_t)at[k]] = res[k];
+        call_rc[(size_t)at[k]] = res[k].subsequences != 0 ? GZ_OK : rc;   // (a chunk in front of the failure has its verdicts)
+      }
+    }
+    // the resuming pass: the reader again, the hook answering with the verdict -- what lies behind the scan is judged as
+    // ever, and a scan without the status DECODED is read by the host into its image
+    for (size_t k = 0; k < scans.size(); ++k) {
+      const int i = owner[k];
+      DeviceScan& hook = hooks[(size_t)i];
+      const gz_device_output o = image(i);
+      hook.out = &o;
+      hook.collected = false;
+      hook.replay = &verdicts[k];
+      hook.replay_rc = call_rc[k];
+      const bool ok = DecodeToOutput(jpegs[(size_t)i], device, o, nullptr, nullptr, expect_w, expect_h, &hook);
+      hook.out = nullptr;
+      hook.replay = nullptr;
+      if (!ok) return fail(i);
+    }
+    if (infos)
+      for (int i = 0; i < n; ++i) (*infos)[(size_t)i] = hooks[(size_t)i].info;
+    return true;
+  }
+  for (int i = 0; i < n; ++i) {
+    const gz_device_output o = image(i);
+    if (!DecodeToOutput(jpegs[(size_t)i], device, o, nullptr, nullptr, expect_w, expect_h, nullptr)) return fail(i);
+  }
+  return true;
 }
 
 bool DecodeJpegCoeffs(const std::string& jpeg, int device, const EntropyOptions& entropy, int* w, int* h, int* factor,

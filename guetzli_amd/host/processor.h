@@ -128,6 +128,25 @@ bool DecodeJpegToRGB(const std::string& jpeg, int device, const DeviceOutput& ou
                      const EntropyOptions& entropy, DecodeInfo* info = nullptr);
 bool DecodeJpegToRGB(const std::string& jpeg, int device, std::vector<uint8_t>* rgb, int* w, int* h, const EntropyOptions& entropy,
                      DecodeInfo* info = nullptr);
+// N JPEGs of ONE decoded size into the N images of a strided tensor on GPU `device` (gz_device_output_batch: element
+// (i, y, x, c) at data[i*stride_n + y*stride_y + x*stride_x + c*stride_c], no two elements at one address): image i is,
+// bit for bit, what DecodeJpegToRGB(jpegs[i], ...) writes, and (*infos)[i] what it reports.  With entropy.device the
+// eligible scans of the whole batch are read by ONE device call per sampling (gz_decode_scan_batch_device: grey, 4:4:4,
+// 4:2:0 -- three at the most): every file is parsed up to its scan, the device decodes, and every file is parsed again
+// with the verdict in hand, so that whatever follows the scan is judged as ever.  A file whose scan is not eligible, or
+// got a status other than DECODED, or whose device call failed (one line on stderr), is read by the host into its image,
+// silently.  expect_w, expect_h: the size `out` was made for (0: the first file's).  A file the reader refuses, or of
+// another size, fails the call -- *failed (optional) is its index -- and `out` then holds no guarantee.
+// scratch_cap_bytes: gz_decode_scan_batch_device's.
+struct DeviceOutputBatch {
+  int dtype = DeviceImage::kU8;
+  void* data = nullptr;
+  int64_t stride_n = 0, stride_y = 0, stride_x = 0, stride_c = 0;
+  void* consumer_stream = nullptr;
+};
+bool DecodeJpegBatchToRGB(const std::vector<std::string>& jpegs, int device, const DeviceOutputBatch& out, int expect_w, int expect_h,
+                          const EntropyOptions& entropy, std::vector<DecodeInfo>* infos = nullptr, int* failed = nullptr,
+                          size_t scratch_cap_bytes = 0);
 // The stream's dequantised coefficients in the frame layout of include/guetzli_amd.h (what DecodeJpegToRGB hands to the
 // device), *factor the chroma subsampling factor; meta (optional) receives what the reader kept beside them.
 struct JpegInput;

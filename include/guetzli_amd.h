@@ -551,6 +551,43 @@ int gz_butteraugli_batch(int device, int w, int h, int n, const gz_device_batch*
                          const gz_device_batch* other, float* distances, float* host_distances,
                          const gz_device_map_batch* maps, size_t scratch_cap_bytes);
 
+/* Batches: N baseline scans of one frame size through the launches of ONE device decode -
+ * gz_decode_scan_device costs per call, not per byte: its kernels are latency-bound, and the host reads a word per
+ * synchronisation round and the verdict at the end.  gz_decode_scan_batch_device decodes n scans of ONE w, h, ncomp and
+ * chroma_factor with one launch of every kernel for all of them: the streams lie in one buffer, every
+ * stream's lanes are padded to whole workgroups, the host reads n words per round and n verdicts at the end, and the
+ * pixels of the scans that decoded leave through batched forms of the reconstruction and emit kernels.
+ * gz_device_output_batch: n strided images in device memory that are WRITTEN -- gz_device_batch's fields, the number of
+ * images, and gz_device_output's rules: element (i, y, x, c) at data[i*stride_n + y*stride_y + x*stride_x + c*stride_c], strides in
+ * ELEMENTS and >= 0, no two elements of the n * h * w * 3 at one address; every gz_device_output dtype;
+ * consumer_stream as gz_device_output's, in both directions.
+ * scans[i] (tables, quantisers, data, len its own; subseq_bytes and max_sync_rounds must be the same in all of them)
+ * fills image slots[i] of `out`, 0 <= slots[i] < out->n, no slot twice.  results[i] is exactly what
+ * gz_decode_scan_device(device, &scans[i], image slots[i], ...) writes -- status, subsequences, sync_rounds (the rounds
+ * THIS stream needed: a property of the stream, not of the batch), end_offset -- and so are the pixels; a scan whose
+ * status is not GZ_SCAN_DECODED has no byte of its image written, and the other scans do not depend on it.
+ * scratch_cap_bytes (0: 2 GiB): the most device memory the call's temporaries may take.  Per image: the stream's bytes,
+ * 9.5 KiB of tables, 28 bytes per lane (a lane is subseq_bytes of the stream, padded to 256 lanes), 2 bytes per block of
+ * the scan, and the frame: 128 bytes per coefficient block (192 B per pixel at 4:4:4, 96 at 4:2:0), 3 bytes per pixel
+ * packed, at 4:2:0 another 0.5.  More scans than fit run as chunks of as many as fit, with the same results; a scan
+ * that does not fit alone is GZ_E_ARG.  Temporaries come from the device pool, all of a chunk's or none.
+ * GZ_E_ARG (before any device call): gz_decode_scan's per scan; n < 1, NULL scans, slots, out or results, scans that
+ * differ in w, h, ncomp, chroma_factor, subseq_bytes or max_sync_rounds, a slot out of range or named twice, a wrong
+ * struct_size, an unknown dtype, a negative stride, aliasing strides.  Any other error: the results of the scans that
+ * had no verdict yet are left at "no verdict" (status GZ_SCAN_NOT_CONVERGED, sync_rounds 0) and their images hold
+ * unspecified values in their elements; the caller reads those scans itself. */
+typedef struct gz_device_output_batch {
+  int struct_size;            /* sizeof(gz_device_output_batch) */
+  int dtype;                  /* GZ_DT_U8 / GZ_DT_F32 / GZ_DT_F16 / GZ_DT_BF16 / GZ_DT_U16 */
+  void* data;                 /* device address of element (0,0,0,0) */
+  int64_t stride_n, stride_y, stride_x, stride_c;   /* elements, >= 0, no two elements at one address */
+  void* consumer_stream;      /* hipStream_t that used the memory before and reads it after; NULL = none */
+  int n;                      /* images, >= 1 */
+} gz_device_output_batch;
+int gz_decode_scan_batch_device(int device, int n, const gz_scan* scans, const int* slots,
+                                const gz_device_output_batch* out, gz_scan_result* results,
+                                size_t scratch_cap_bytes);
+
 /* Masking: Mask, the opsin image and the quantisation field, on the device ---------------
  * What butteraugli.h offers beside the distance: OpsinDynamicsImage(rgb), the XYB image; Mask(xyb0, xyb1, &mask,
  * &mask_dc) (butteraugli.cc:1741-1817), the visual-masking images that say where an error of a given size is visible;
